@@ -1,16 +1,20 @@
 #!/usr/bin/env python
 """bench.py -- the hot path's headline metric on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps 50] [--warmup 5]        (N > 1: launches its own N ranks, one per GPU)
+    python bench.py [--gpus N] [--steps 50] [--warmup 5] [--dump-outputs DIR] [--full]   (N > 1: launches its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W                (the same job under an outside launcher)
+
+A plain run does what the headline needs and nothing else: it sets up the matrix, warms up, times the K steps, writes y of the last step when
+--dump-outputs is given (DIR/y.npy with its row numbers in DIR/y_rows.npy, float64; a fixed seeded sample of at most 2^21 rows when y is longer) and
+prints the line.  Everything listed under "Beside it" below, the live PMC traffic of the roofline included, runs with --full only.
 
 Workload (BASELINE.json): the 3-D 7-point Poisson matrix on a 512^3 grid in CSR (test/test3.c entry order, f64 values, i32 indices), generated
 directly in HBM.  A "step" is one y = A*x through lis_matvec() of liblis_amd.so in the REFERENCE LAYOUT mode (lis_amd_set_reference_layout): the kernel
 streams the reference's own arrays -- 4 B index[] + 8 B value[] per non-zero, ptr[], y, x gathered: the loop of src/matvec/lis_matvec_csr.c:97-109 on
 SURVEY 8d's 12 nnz + 20 n + 4 bytes -- on a NON-TRIVIAL x (x_i = frac(i * golden ratio) - 0.5).  That is the line's `value`, `ms_per_step` and `roofline`
 (`frac` <= 1 by construction: exactly those bytes over the kernel's HIP-event time over 8 TB/s; `traffic` = this run's own PMC counters).
-Beside it, each labelled with what it applies to:
+Beside it (--full), each labelled with what it applies to:
   x_equals_one           the same kernel on the reference's x = 1 (test/spmvtest3.c), with its closed-form norm check
   krylov                 CG+Jacobi / BiCGSTAB / BiCG / GMRES(30) iterations per second in the same mode: iter / itime of lis_solver_get_timeex (lis_solver.c:902-908)
   structured_fast_path   what lis_matvec runs for THIS matrix by default -- the plan found a constant-coefficient box stencil and marches it without reading the
@@ -42,6 +46,8 @@ BASELINE_CONFIGS = {           # BASELINE.json `configs`, verbatim: every leg un
     "config4": "SuiteSparse Queen_4147 (irregular CSR), GMRES(30), 1 MI355X — merge-path load-balance",
     "config5": "3D 7-pt Poisson n=256^3 in ELL and DIA formats, CG, 1 MI355X — format sweep vs CSR",
 }
+DUMP_ROWS = 1 << 21           # --dump-outputs: at most this many rows of y (values and row numbers, float64: 32 MB in all)
+DUMP_SEED = 20261016          # the rows sampled when y is longer: the same in every run of the same grid
 SOLVERS = (("cg_jacobi", "-i cg -p jacobi"), ("bicgstab_none", "-i bicgstab -p none"),
            ("bicg_none", "-i bicg -p none"),            # Lis's default solver: needs A^T (built in HBM on first use)
            ("gmres30_none", "-i gmres -restart 30 -p none"))
@@ -68,6 +74,12 @@ def parse():
                     help="the slowest grid dimension when it is not --grid (whole job): `--planes 64` on one GPU is the slab ONE rank of the 8-rank strong-scaling job "
                          "owns (512 x 512 x 64 rows) -- the per-rank kernel times tools/scale_predict.py builds the predicted curve from.  Not the headline workload: "
                          "`config.workload` says so")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the x = 1 and default-form legs, Krylov rates, per-config legs, the 27-point stencil, the box "
+                         "yardstick, the CPU baseline, the live PMC traffic, the N > 1 halo timings and the setup split (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write y of the last one to DIR/y.npy and the rows it holds to DIR/y_rows.npy (float64; every row up to "
+                         "2^21 rows, else a fixed seeded sample of at most 2^21 rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the committed profiles/ figure instead of two rocprofv3 --pmc passes of this run (about 15 s)")
     ap.add_argument("--no-solvers", action="store_true")
@@ -75,7 +87,18 @@ def parse():
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config legs (config1, 2, 4, 5; rank 0, N = 1 only)")
     ap.add_argument("--launch-check", action="store_true",
                     help="bring-up of the launch path without a GPU: form the process group, gather the ranks, print one JSON line, exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_rows(n):
+    """the global rows of y that --dump-outputs writes, ascending: all n of them up to DUMP_ROWS, else a fixed sample drawn with DUMP_SEED"""
+    import numpy as np
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_ROWS, dtype=np.int64))
 
 
 def self_launch(args):
@@ -229,32 +252,56 @@ def main():
             part = np.modf(np.arange(lo.value + s0, lo.value + s0 + cnt, dtype=np.float64) * 0.6180339887498949)[0] - 0.5
             assert lib.lis_vector_set_values2(capi.LIS_INS_VALUE, lo.value + s0, cnt, part.ctypes.data_as(capi.P_DBL), v) == 0
 
+    def dump_outputs(out_dir, v):
+        """--dump-outputs: what lis_matvec handed its caller in the last timed step -- v at the rows of dump_rows(n_global), gathered on rank 0 in row order --
+        as out_dir/y.npy, and those rows as out_dir/y_rows.npy (float64, exact far beyond 2^31)"""
+        rows = dump_rows(n_global)
+        lo = C.c_int(); hi = C.c_int()
+        assert lib.lis_vector_get_range(v, C.byref(lo), C.byref(hi)) == 0
+        mine = rows[(rows >= lo.value) & (rows < hi.value)]
+        local = np.empty(hi.value - lo.value)
+        assert lib.lis_vector_get_values(v, lo.value, hi.value - lo.value, local.ctypes.data_as(capi.P_DBL)) == 0
+        vals = local[mine - lo.value]
+        del local
+        if world > 1:                                     # (the ranks hold ascending row blocks)
+            parts = [None] * world
+            dist.all_gather_object(parts, vals)
+            vals = np.concatenate(parts)
+        if rank == 0:
+            assert vals.shape == rows.shape
+            os.makedirs(out_dir, exist_ok=True)
+            np.save(os.path.join(out_dir, "y.npy"), vals.astype(np.float64))
+            np.save(os.path.join(out_dir, "y_rows.npy"), rows.astype(np.float64))
+
     dll.lis_amd_synchronize()
     t_setup = time.perf_counter()
     A = poisson(L, N, N)                                  # the DEFAULT plan (row split, index codes, row patterns, value records): what a Lis program gets
     dll.lis_amd_synchronize()
     setup_ms = (time.perf_counter() - t_setup) * 1e3
     n_local, nnz_local = A.contents.n, A.contents.nnz
-    # the generator alone, into scratch arrays: what is left of setup_ms is the plan -- a one-off per matrix, paid at assemble / convert time
+    # --full: the generator alone, into scratch arrays: what is left of setup_ms is the plan -- a one-off per matrix, paid at assemble / convert time
     gen_ms = None
-    try:
-        from lis_amd import DeviceArray as _DA
-        s_ptr, s_idx, s_val = _DA(n_local + 5, np.int32), _DA(nnz_local + 4, np.int32), _DA(nnz_local + 2, np.float64)
-        lo_r, hi_r = A.contents.is_, A.contents.ie
-        check(lib.liship_poisson3d_csr(L, N, N, lo_r, hi_r, 0, s_ptr.ptr, s_idx.ptr, s_val.ptr, None))     # (first call: code load)
-        dll.lis_amd_synchronize()
-        t_gen = time.perf_counter()
-        check(lib.liship_poisson3d_csr(L, N, N, lo_r, hi_r, 0, s_ptr.ptr, s_idx.ptr, s_val.ptr, None))
-        dll.lis_amd_synchronize()
-        gen_ms = (time.perf_counter() - t_gen) * 1e3
-        s_ptr.free(); s_idx.free(); s_val.free()
-    except Exception:
-        gen_ms = None
+    if args.full:
+        try:
+            from lis_amd import DeviceArray as _DA
+            s_ptr, s_idx, s_val = _DA(n_local + 5, np.int32), _DA(nnz_local + 4, np.int32), _DA(nnz_local + 2, np.float64)
+            lo_r, hi_r = A.contents.is_, A.contents.ie
+            check(lib.liship_poisson3d_csr(L, N, N, lo_r, hi_r, 0, s_ptr.ptr, s_idx.ptr, s_val.ptr, None))     # (first call: code load)
+            dll.lis_amd_synchronize()
+            t_gen = time.perf_counter()
+            check(lib.liship_poisson3d_csr(L, N, N, lo_r, hi_r, 0, s_ptr.ptr, s_idx.ptr, s_val.ptr, None))
+            dll.lis_amd_synchronize()
+            gen_ms = (time.perf_counter() - t_gen) * 1e3
+            s_ptr.free(); s_idx.free(); s_val.free()
+        except Exception:
+            gen_ms = None
     nnz_global = 7 * n_global - 2 * (N * N + 2 * L * N)
 
-    x1, xg, y, yc, b = vec(A), vec(A), vec(A), vec(A), vec(A)
+    x1, xg, y = vec(A), vec(A), vec(A)                    # (x1 serves the --full legs only; made first in every run, so that xg and y are placed alike)
     assert lib.lis_vector_set_all(1.0, x1) == 0
     golden_x(xg, n_local)
+    if args.full:
+        yc, b = vec(A), vec(A)
 
     stream = dll.lis_amd_stream()
     timer = C.c_void_p()
@@ -484,10 +531,71 @@ def main():
     dt, kernel_ms = timed_products(A, xg, y, args.steps)
     ms_per_step = dt / args.steps * 1e3
     gflops = 2.0 * nnz_global * args.steps / dt / 1e9
-    assert lib.lis_vector_copy(y, yc) == 0                # kept: the default form below must reproduce it bit for bit
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y)                # y of the last timed step, before any other leg writes y
     roofline = roofline_of(REF, kernel_ms, "_contract_form",
-                           "ANY CSR matrix with short rows: nothing about the matrix is assumed or precomputed beyond the row split (12 B per non-zero + 20 B per row streamed)")
+                           "ANY CSR matrix with short rows: nothing about the matrix is assumed or precomputed beyond the row split (12 B per non-zero + 20 B per row streamed)",
+                           live=args.full)
     roofline["xcd_strip_rows"] = int(dll.lis_amd_matrix_strip_rows(A))     # rows per plane the XCD strips are cut from (0: natural block order)
+
+    def headline_line():
+        """the fields of the line a plain run prints; --full adds the side legs to them"""
+        return {
+            "metric": "SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n=512^3" if (N == 512 and not slab) else f"SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n={L}x{N}x{N}" if slab else f"SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n={N}^3",
+            "value": round(gflops, 2), "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": (f"3-D 7-point Poisson {N}^3" if L == N else f"3-D 7-point Poisson {N}^3 per GPU (grid {N} x {N} x {L})") +
+                                   ", CSR f64/i32 (test3.c entry order), y=A*x via lis_matvec streaming the reference's own value[] / index[] / ptr[] arrays (12 B per non-zero + 20 B per row), "
+                                   "x_i = frac(i * 0.618...) - 0.5",
+                       "n": n_global, "nnz": nnz_global, "mode": "lis_amd_set_reference_layout(1)",
+                       "parallelism": f"row-block x{world}" + ((" + RCCL halo" if comm_used == "rccl" else " + gloo-callback halo (bring-up, not a measurement)") if world > 1 else "")},
+            "roofline": roofline,
+            "full": args.full,
+            "reading_guide": ("`value` / `ms_per_step` / `roofline`: lis_matvec on the 512^3 CSR matrix in the reference layout mode -- spmv_csr_rowgather_kernel streams the reference's own "
+                              "index[] / value[] / ptr[] arrays, SURVEY 8d's 12 B per non-zero + 20 B per row, on a non-trivial x; `frac` is exactly those bytes / the kernel's HIP-event time / "
+                              "8 TB/s, <= 1 by construction, and `traffic` is " + ("this run's own PMC count of the same kernel.  `krylov`: the solver loops in the same mode.  "
+                              "`structured_fast_path`: what the library does for THIS matrix by default (a constant-coefficient box stencil: matrix-free marching) -- the same bits, "
+                              "priced on its own bytes, not a CSR-roofline claim.  `configs`: one leg per BASELINE.json config.  Every `frac` in the line is bytes-the-kernel-is-asked-to-move / "
+                              "its measured time / 8 TB/s (0 < frac <= 1, asserted); `contract_frac` prices SURVEY 8d's layout over the same time and exceeds 1 exactly where a derived form reads fewer bytes."
+                              if args.full else "the committed profiles/ count of the same kernel.  The side legs (x = 1, Krylov, the default form, the configs, the CPU baseline) run with --full.")),
+            "setup": {"generate_and_plan_ms": round(setup_ms, 1), "generate_ms": None if gen_ms is None else round(gen_ms, 1),
+                      "plan_build_ms": None if gen_ms is None else round(max(setup_ms - gen_ms, 0.0), 1),
+                      "plan_build_in_products": None if gen_ms is None else round(max(setup_ms - gen_ms, 0.0) / max(ms_per_step, 1e-9), 1),
+                      "note": "one-off per matrix, outside the timed region (the reference pays its own at lis_matrix_assemble / _convert): the matrix generated in HBM, then "
+                              "the DEFAULT plan -- merge-path row split, one-byte column codes, row patterns, value records, the dominant pattern (DESIGN.md 4); "
+                              "plan_build_in_products = how many timed (reference-layout) products it costs (the split: --full)"},
+            "preroll": args.preroll,          # untimed clock-ramp launches before the W warm-up steps (a cold process: +7 %)
+            "degraded": bool(world > 1 and comm_used != "rccl"),   # True: the RCCL communicator could not be formed, NOT a measurement
+            "rccl_ranks": world if (world > 1 and comm_used == "rccl" and int(dll.lis_amd_comm_kind()) == 1) else (0 if world > 1 else None),
+            "self_launched": os.environ.get("LIS_AMD_BENCH_SELF_LAUNCHED") == "1",
+        }
+
+    def finish(out):
+        """rank 0 checks and prints the line; every rank leaves the job"""
+        if rank == 0:
+            # the HEADLINE's fraction is a hard rule (SURVEY 8d's bytes over the timed kernel: above 1 the kernel is not doing the work); a side leg whose working set sits in
+            # the 256 MB Infinity Cache (a slab run, a small --grid) can legitimately beat the HBM peak: reported in the line, not fatal to it
+            assert_fracs_physical({"roofline": out["roofline"]}, shared_gpu=out["degraded"])
+            assert alg_bytes / (ms_per_step * 1e-3) <= HBM_PEAK_GBS * 1e9, "SURVEY 8d bytes / ms_per_step exceeds the HBM peak: the timed kernel is not doing the work"
+            bad = []
+            collect_unphysical_fracs(out, "line", bad, shared_gpu=out["degraded"])
+            out["fracs_outside_0_1"] = bad        # [] in every run at the headline size
+            if bad:
+                print(f"bench.py: fractions outside (0, 1] in side legs (cache-resident working sets?): {bad}", file=sys.stderr, flush=True)
+            emit(out)
+        degraded = world > 1 and comm_used != "rccl" and args.comm == "rccl"
+        if world > 1:
+            dll.lis_amd_comm_finalize()
+            dist.destroy_process_group()
+        if degraded:
+            sys.exit(3)                   # the line above says "degraded": true; a driver that only looks at the exit code sees it too
+
+    if not args.full:
+        finish(headline_line() if rank == 0 else None)
+        return
+
+    assert lib.lis_vector_copy(y, yc) == 0                # kept: the default form below must reproduce it bit for bit
     x_one = leg(A, x1, y, args.steps, nnz_global)
     check_a_times_one("reference layout, x = 1")
     x_one["x"] = "x = 1 (test/spmvtest3.c): the same kernel, the same bytes; the multipliers see one mantissa pattern and the clocks run a few per cent higher"
@@ -593,59 +701,20 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(np, N)
 
+    out = None
     if rank == 0:
-        out = {
-            "metric": "SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n=512^3" if (N == 512 and not slab) else f"SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n={L}x{N}x{N}" if slab else f"SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n={N}^3",
-            "value": round(gflops, 2), "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": (f"3-D 7-point Poisson {N}^3" if L == N else f"3-D 7-point Poisson {N}^3 per GPU (grid {N} x {N} x {L})") +
-                                   ", CSR f64/i32 (test3.c entry order), y=A*x via lis_matvec streaming the reference's own value[] / index[] / ptr[] arrays (12 B per non-zero + 20 B per row), "
-                                   "x_i = frac(i * 0.618...) - 0.5",
-                       "n": n_global, "nnz": nnz_global, "mode": "lis_amd_set_reference_layout(1)",
-                       "parallelism": f"row-block x{world}" + ((" + RCCL halo" if comm_used == "rccl" else " + gloo-callback halo (bring-up, not a measurement)") if world > 1 else "")},
-            "roofline": roofline,
+        out = headline_line()
+        out.update({
             "x_equals_one": x_one,
             "krylov": krylov,
             "structured_fast_path": fast,
             "configs": configs,
-            "reading_guide": ("`value` / `ms_per_step` / `roofline`: lis_matvec on the 512^3 CSR matrix in the reference layout mode -- spmv_csr_rowgather_kernel streams the reference's own "
-                              "index[] / value[] / ptr[] arrays, SURVEY 8d's 12 B per non-zero + 20 B per row, on a non-trivial x; `frac` is exactly those bytes / the kernel's HIP-event time / "
-                              "8 TB/s, <= 1 by construction, and `traffic` is this run's own PMC count of the same kernel.  `krylov`: the solver loops in the same mode.  "
-                              "`structured_fast_path`: what the library does for THIS matrix by default (a constant-coefficient box stencil: matrix-free marching) -- the same bits, "
-                              "priced on its own bytes, not a CSR-roofline claim.  `configs`: one leg per BASELINE.json config.  Every `frac` in the line is bytes-the-kernel-is-asked-to-move / "
-                              "its measured time / 8 TB/s (0 < frac <= 1, asserted); `contract_frac` prices SURVEY 8d's layout over the same time and exceeds 1 exactly where a derived form reads fewer bytes."),
-            "setup": {"generate_and_plan_ms": round(setup_ms, 1), "generate_ms": None if gen_ms is None else round(gen_ms, 1),
-                      "plan_build_ms": None if gen_ms is None else round(max(setup_ms - gen_ms, 0.0), 1),
-                      "plan_build_in_products": None if gen_ms is None else round(max(setup_ms - gen_ms, 0.0) / max(ms_per_step, 1e-9), 1),
-                      "note": "one-off per matrix, outside the timed region (the reference pays its own at lis_matrix_assemble / _convert): the matrix generated in HBM, then "
-                              "the DEFAULT plan -- merge-path row split, one-byte column codes, row patterns, value records, the dominant pattern (DESIGN.md 4); "
-                              "plan_build_in_products = how many timed (reference-layout) products it costs"},
-            "preroll": args.preroll,          # untimed clock-ramp launches before the W warm-up steps (a cold process: +7 %)
-            "degraded": bool(world > 1 and comm_used != "rccl"),   # True: the RCCL communicator could not be formed, NOT a measurement
-            "rccl_ranks": world if (world > 1 and comm_used == "rccl" and int(dll.lis_amd_comm_kind()) == 1) else (0 if world > 1 else None),
-            "self_launched": os.environ.get("LIS_AMD_BENCH_SELF_LAUNCHED") == "1",
             "multi_gpu": multi,
             "box_yardstick": yard,            # what a pure streaming kernel with the product's read : write ratio reaches on THIS box (no gather, no index): the practical ceiling behind `roofline.frac`
             "stencil27": extras,              # beside the headline: the 27-point stencil (spmvtest3b / HPCG) through the round-3 kernels; not part of `value`
             "cpu_baseline": cpu,
-        }
-        # the HEADLINE's fraction is a hard rule (SURVEY 8d's bytes over the timed kernel: above 1 the kernel is not doing the work); a side leg whose working set sits in
-        # the 256 MB Infinity Cache (a slab run, a small --grid) can legitimately beat the HBM peak: reported in the line, not fatal to it
-        assert_fracs_physical({"roofline": out["roofline"]}, shared_gpu=out["degraded"])
-        assert alg_bytes / (ms_per_step * 1e-3) <= HBM_PEAK_GBS * 1e9, "SURVEY 8d bytes / ms_per_step exceeds the HBM peak: the timed kernel is not doing the work"
-        bad = []
-        collect_unphysical_fracs(out, "line", bad, shared_gpu=out["degraded"])
-        out["fracs_outside_0_1"] = bad        # [] in every run at the headline size
-        if bad:
-            print(f"bench.py: fractions outside (0, 1] in side legs (cache-resident working sets?): {bad}", file=sys.stderr, flush=True)
-        emit(out)
-    degraded = world > 1 and comm_used != "rccl" and args.comm == "rccl"
-    if world > 1:
-        dll.lis_amd_comm_finalize()
-        dist.destroy_process_group()
-    if degraded:
-        sys.exit(3)                   # the line above says "degraded": true; a driver that only looks at the exit code sees it too
+        })
+    finish(out)
 
 
 # ============================================================================================================================ per-config legs

@@ -38,7 +38,7 @@ def test_bench_launches_its_own_ranks():
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--grid", "64",
-                        "--preroll", "5", "--solver-iters", "20"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--preroll", "5", "--solver-iters", "20", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -47,6 +47,7 @@ def test_bench_line_has_the_contract_fields():
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
+    assert d["full"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["higher_is_better"] is True
     assert d["unit"] == "GFLOP/s" and d["dtype"] == "f64" and d["data"] == "synthetic" and d["vs_baseline"] is None
     assert "workload" in d["config"] and d["value"] > 0 and d["ms_per_step"] > 0
@@ -133,6 +134,36 @@ def test_bench_line_has_the_contract_fields():
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_its_y(tmp_path):
+    """Without --full the line carries the headline alone (no side legs run), --steps sets the timed steps, and --dump-outputs writes y of the last timed step:
+    at 64^3 every row, equal bit for bit to the CPU oracle's product on the same x."""
+    import numpy as np
+    import orc
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--grid", "64", "--preroll", "5",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), p.stdout
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["metric"] == "SpMV GFLOP/s, CSR, 3-D 7-pt Poisson n=64^3" and d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    n, nnz = d["config"]["n"], d["config"]["nnz"]
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2.0 * nnz / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"]
+    r = d["roofline"]
+    assert r["kernel"] == "spmv_csr_rowgather_kernel" and r["bytes_per_launch"] == 12 * nnz + 20 * n + 4 and 0 < r["frac"] <= 1.0
+    for key in ("x_equals_one", "krylov", "structured_fast_path", "configs", "multi_gpu", "box_yardstick", "stencil27", "cpu_baseline"):
+        assert key not in d, key
+    assert d["fracs_outside_0_1"] == []
+    y, rows = np.load(out / "y.npy"), np.load(out / "y_rows.npy")
+    assert y.dtype == rows.dtype == np.float64 and y.shape == rows.shape == (n,)
+    assert np.array_equal(rows, np.arange(n, dtype=np.float64))
+    ptr, idx, val = orc.poisson3d(64, 64, 64)
+    x = np.modf(np.arange(n, dtype=np.float64) * 0.6180339887498949)[0] - 0.5      # bench.py's x
+    assert np.array_equal(y, orc.spmv_csr(ptr, idx, val, x))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("scaling,launcher", [("weak", "torchrun"), ("strong", "torchrun"), ("weak", "self")])
 def test_bench_two_ranks_on_one_gpu(scaling, launcher):
     """the N > 1 job with two ranks sharing this box's GPU (RCCL refuses that: --comm callbacks, a bring-up run flagged degraded): partition, halo, the
@@ -141,7 +172,7 @@ def test_bench_two_ranks_on_one_gpu(scaling, launcher):
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--grid", "48", "--scaling", scaling, "--comm", "callbacks",
-            "--preroll", "5", "--solver-iters", "20", "--no-cpu-baseline"]
+            "--preroll", "5", "--solver-iters", "20", "--no-cpu-baseline", "--full"]
     head = ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
             if launcher == "torchrun" else [sys.executable])
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

@@ -608,3 +608,24 @@ def test_bench_reports_unphysical_fractions_instead_of_dying():
     bench.assert_fracs_physical({"roofline": line["roofline"]})
     with pytest.raises(AssertionError):
         bench.assert_fracs_physical({"roofline": {"frac": 1.2}})
+
+
+def test_bench_dump_rows_are_a_fixed_sample_within_64_mb():
+    """bench.py --dump-outputs: every row of a short y, a fixed seeded sample of a long one (512^3), ascending and in range; values and rows in float64 stay under 64 MB"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert np.array_equal(bench.dump_rows(1000), np.arange(1000))
+    n = 512 ** 3
+    rows = bench.dump_rows(n)
+    assert np.array_equal(rows, bench.dump_rows(n))
+    assert 0.99 * bench.DUMP_ROWS < len(rows) <= bench.DUMP_ROWS and rows[0] >= 0 and rows[-1] < n and np.all(np.diff(rows) > 0)
+    assert 2 * 8 * bench.DUMP_ROWS <= 64 << 20
+
+
+def test_bench_rejects_zero_steps():
+    """--steps sets the number of timed steps, so it must be at least 1 (refused before any GPU work)"""
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr and p.stdout == ""

@@ -5,7 +5,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 export PROF_PMC_ONLY="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum|TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum|TCC_HIT_sum TCC_MISS_sum"
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --preroll 100 --no-cpu-baseline --no-live-traffic --no-extras --solver-iters 40"
+CMD="python $PWD/bench.py --full --steps 20 --warmup 3 --preroll 100 --no-cpu-baseline --no-live-traffic --no-extras --solver-iters 40"
 tools/prof.sh r06_prof $CMD > gpurun_out/r06_prof_summary.txt 2>&1
 python tools/traffic_json.py gpurun_out/r06_prof "spmv_csr_rowgather_kernel<256, 2048, 7, 0>" gpurun_out/r06_spmv512_traffic_contract_form.json --coded 0 --command "$CMD" > /dev/null 2>&1
 python tools/traffic_json.py gpurun_out/r06_prof "spmv_csr_valuerec_march_kernel<2, 2, 0, false" gpurun_out/r06_spmv512_traffic.json --values 1 --box 1 --patterns 1 --command "$CMD" > /dev/null 2>&1

@@ -20,7 +20,7 @@ for MODE in weak strong; do
     [ "$N" -gt "$MAXN" ] && continue
     echo "== $MODE scaling, $N GPU(s)" >&2
     # the driver's own entry point: `python bench.py --gpus N` starts its N ranks itself (one per GPU, torch.distributed.run on 127.0.0.1)
-    timeout 1800 python bench.py --gpus "$N" --steps "$STEPS" --warmup 5 --scaling "$MODE" --solver-iters "$ITERS" --no-extras --no-live-traffic --no-cpu-baseline \
+    timeout 1800 python bench.py --full --gpus "$N" --steps "$STEPS" --warmup 5 --scaling "$MODE" --solver-iters "$ITERS" --no-extras --no-live-traffic --no-cpu-baseline \
       2> "$OUT/scale8_${MODE}_$N.err" | grep '^{' >> "$OUT/scale8_$MODE.jsonl"
     echo "   exit ${PIPESTATUS[0]}" >&2
   done

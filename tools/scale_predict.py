@@ -2,7 +2,7 @@
 
     python tools/scale_predict.py slabs.jsonl > profiles/r05_scale_prediction.json
 
-slabs.jsonl: bench.py lines of `--planes L` runs on one GPU for L = 512, 256, 128, 64 (512 x 512 x L rows: the slab one rank of the strong-scaling job owns at
+slabs.jsonl: bench.py --full lines of `--planes L` runs on one GPU for L = 512, 256, 128, 64 (512 x 512 x L rows: the slab one rank of the strong-scaling job owns at
 N = 1, 2, 4, 8; the weak-scaling job keeps the L = 512 slab on every rank).  From each line: the product's kernel time, CG + Jacobi and BiCGSTAB seconds per iteration.
 
 Model (every constant is here, none is fitted to a multi-GPU run -- there has not been one):

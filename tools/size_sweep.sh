@@ -1,7 +1,7 @@
 # bench.py over grid sizes: SpMV GFLOP/s (value records and values streamed) and Krylov it/s per size -> gpurun_out/size_sweep.txt
 cd $GRAFT_REPO_ROOT
 for g in 64 100 128 192 200 256 300 320 384 448 512; do
-  timeout 600 python bench.py --grid $g --steps 50 --warmup 5 --preroll 200 --solver-iters 300 --no-cpu-baseline --no-configs 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --grid $g --steps 50 --warmup 5 --preroll 200 --solver-iters 300 --no-cpu-baseline --no-configs 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['krylov']; f=j['structured_fast_path']; s=f.get('values_streamed') or {}; fk=f['krylov']
