@@ -38,6 +38,15 @@ constexpr int SLACK = 128;       // extra items a block may take to start on an 
 //   bit29 (0x20000000) value records: never the dominant-pattern kernels (the kernels of plans without a dominant pattern: tests);
 //   bit28 (0x10000000) the dominant-pattern product on contiguous chunks instead of tiles (the path of grids whose lines 128 does not divide: tests)
 int g_variant = 0;
+constexpr int VAR_SCALAR_LOADS   = 0x2;          // the products kernel with scalar loads (on aligned arrays too)
+constexpr int VAR_PRODUCTS       = 0x4;          // the products kernel with vector loads
+constexpr int VAR_GEOM           = 0xF0;         // geometry id (plan creation)
+constexpr int VAR_PATTERN_LDS    = 0x2000;       // row patterns through the general pattern kernel
+constexpr int VAR_GATHER         = 0x4000;       // a gather per entry: value records two rows per lane, pattern teams and wide rows without the x stage
+constexpr int VAR_NO_ROW_ALIGN   = 0x1000000;    // row blocks not aligned to ROW_ALIGN rows (plan creation)
+constexpr int VAR_DOM_CHUNKS     = 0x10000000;   // the dominant-pattern product on plain chunks
+constexpr int VAR_ROUND2_RECORDS = 0x20000000;   // value records without the dominant-pattern kernels
+inline bool variant_only(int bits) { return (g_variant & ~bits) == 0; }     // no variant bit outside `bits` is set
 int g_index_codes = 1;           // liship_spmv_csr_set_index_codes: 0 keeps every product on the 4 B indices
 int g_row_patterns = 1;          // liship_spmv_csr_set_row_patterns: 0 keeps coded matrices on one byte per non-zero
 int g_row_values = 1;            // liship_spmv_csr_set_row_values: 0 keeps streaming the values of matrices that have value records

@@ -340,7 +340,7 @@ static int build_split(liship_csr_plan_s *p, const int *ptr, hipStream_t st)
     hipError_t e = hipMalloc(&p->blk, bytes);
     if (e != hipSuccess) return (int)e;
     const int threads = 256, grid = (p->nblocks + 1 + threads - 1) / threads;
-    csr_plan_kernel<<<grid, threads, 0, st>>>(p->n, ptr, p->nblocks, WORK, (g_variant & 0x1000000) ? 0 : 1, p->blk);
+    csr_plan_kernel<<<grid, threads, 0, st>>>(p->n, ptr, p->nblocks, WORK, (g_variant & VAR_NO_ROW_ALIGN) ? 0 : 1, p->blk);
     e = hipGetLastError();
     p->blk_host = (v2i32 *)malloc(bytes);
     if (!p->blk_host) { (void)hipFree(p->blk); p->blk = nullptr; return LISHIP_ERR_ARG; }
@@ -415,7 +415,7 @@ extern "C" int liship_csr_plan_create(liship_csr_plan_t *out, int n, const int *
     liship_csr_plan_s *p = new liship_csr_plan_s();
     p->n = n;
     p->nnz = nnz;
-    p->geom = (g_variant >> 4) & 15;
+    p->geom = (g_variant & VAR_GEOM) >> 4;
     if (p->geom >= kNumGeom || p->geom == 2 || p->geom == 3 || p->geom == 4 || p->geom == 6) { delete p; return LISHIP_ERR_ARG; }
     const double mean_len = n > 0 ? (double)nnz / n : 0.0;
     p->unroll = mean_len <= 4.0 ? 4 : (mean_len <= 7.0 ? 7 : 8);

@@ -55,9 +55,52 @@ struct LaunchArgs {
     const v4i32 *vrec = nullptr;            // value records (with ptab8), when the plan has them and they are switched on
     const int *order = nullptr;             // launch order of the products kernel (whole-matrix launches of a plan that has one)
     const v4i32 *vrecw = nullptr;           // wide value records (rows of up to 32 entries), when the plan has them and they are switched on
-    const liship_csr_plan_s *plan = nullptr; // (set by the launchers) the dominant-pattern records live there
+    const liship_csr_plan_s *plan = nullptr; // the plan (plan_args): the dominant-pattern records live there
     const int *rowmap = nullptr;            // reordered plans: where row r of the (renumbered) matrix goes in y -- the block-local kernel only
 };
+
+// The plan's optional arrays as the switches in force let the kernels see them (null: the plan has none, or its switch is off): the one place that says which
+// switch gates which array (liship_spmv_csr_set_index_codes / _row_patterns / _row_values / _local_columns)
+struct PlanArrays { const unsigned char *codes, *rowpat; const unsigned short *lcol; const v4i32 *vrec, *vrecw; };
+PlanArrays plan_arrays(const liship_csr_plan_s *p)
+{
+    return PlanArrays{g_index_codes ? p->codes : nullptr, (g_row_patterns && g_index_codes) ? p->rowpat : nullptr, g_local_cols ? p->lcol : nullptr,
+                      g_row_values ? p->vrec : nullptr, g_row_values ? p->vrecw : nullptr};
+}
+
+// The launch arguments of a product of plan p over the whole matrix: every row block (empty ones included -- the fused forms fold a partial per row block),
+// the plan's launch order
+LaunchArgs plan_args(const liship_csr_plan_s *p, const int *ptr, const int *idx, const double *val, const double *x, double *y, hipStream_t st)
+{
+    const PlanArrays A = plan_arrays(p);
+    LaunchArgs a{};
+    a.plan = p; a.st = st;
+    a.ptr = ptr; a.idx = idx; a.val = val; a.x = x; a.y = y;
+    a.blk = p->blk; a.bfirst = 0; a.nb = p->nblocks; a.order = p->order;
+    a.rb = 0; a.re = p->n; a.nnz = (int)p->nnz; a.acc0 = p->first_term ? -0.0 : 0.0;
+    a.codes = A.codes; a.dict = p->dict;
+    a.lcol = A.lcol; a.dcol = p->dcol; a.doff = p->doff;
+    a.rowpat = A.rowpat; a.rowrel = p->rowrel; a.ptab = p->ptab; a.ptab_len = p->ptab_len; a.npat1 = p->npat + 1; a.ptab8 = p->ptab8;
+    a.vrec = A.vrec; a.vrecw = A.vrecw;
+    return a;
+}
+// ... and over the rows [rb, re) of a plan with row blocks: the blocks whose rows [blk[b].row, blk[b+1].row) meet the range, no launch order
+LaunchArgs plan_args(const liship_csr_plan_s *p, int rb, int re, const int *ptr, const int *idx, const double *val, const double *x, double *y, hipStream_t st)
+{
+    LaunchArgs a = plan_args(p, ptr, idx, val, x, y, st);
+    const v2i32 *blk = p->blk_host, *end = blk + p->nblocks;
+    const v2i32 *first = std::partition_point(blk + 1, end + 1, [&](const v2i32 &e) { return e.x <= rb; }) - 1;      // the first block that ends beyond rb
+    const v2i32 *last = std::partition_point(first, end, [&](const v2i32 &e) { return e.x < re; });                  // the first one after it that starts at re or later
+    a.rb = rb; a.re = re; a.bfirst = (int)(first - blk); a.nb = (int)(last - first); a.order = nullptr;
+    return a;
+}
+// what the shape probes of a plan read: its whole matrix, the value its row sums start from, a y taken for 16 B aligned; no arrays
+LaunchArgs probe_args(const liship_csr_plan_s *p)
+{
+    LaunchArgs a{};
+    a.plan = p; a.rb = 0; a.re = p->n; a.y = reinterpret_cast<double *>(16); a.acc0 = p->first_term ? -0.0 : 0.0;
+    return a;
+}
 
 
 // XCD strips of the 7-offset pattern kernel: whole-matrix launches of a plan that found a plane (xs_plane), unless switched off
@@ -164,7 +207,7 @@ static bool block2_shape(const LaunchArgs &a, Block2March &M)
 static bool launch_wide(const LaunchArgs &a, const double *guard, int dot = 0, const double *w = nullptr, double *partial = nullptr, int pstride = 0, int *wgs_out = nullptr)
 {
     const liship_csr_plan_s *P = a.plan;
-    if (block_rows_serve(P, a.rb, a.re) && !(g_variant & 0x4000)) {      // one lane per block row (the row form of a b x b blocked stencil)
+    if (block_rows_serve(P, a.rb, a.re) && !(g_variant & VAR_GATHER)) {      // one lane per block row (the row form of a b x b blocked stencil)
         const int b = P->bd.b, rows = a.re - a.rb, wgs = (rows + 256 * b - 1) / (256 * b);
         {   // 2 x 2 blocks of a 7-point box grid: whole planes march (spmv_csr_block2_march_kernel)
             Block2March M;
@@ -193,7 +236,7 @@ static bool launch_wide(const LaunchArgs &a, const double *guard, int dot = 0, c
 #undef GOB
         return true;
     }
-    if (!P || !P->wdrec || !P->wstage || P->wd.len <= 0 || !g_team || (g_variant & 0x4000)) return false;
+    if (!P || !P->wdrec || !P->wstage || P->wd.len <= 0 || !g_team || (g_variant & VAR_GATHER)) return false;
     {   // the 27-point box stencil: whole planes march (spmv_csr_box27_march_kernel)
         Box27 M;
         int lpw = 0;
@@ -234,7 +277,7 @@ static void launch_team(const LaunchArgs &a, const double *guard)
     if (rows <= 0) return;
     // (measured and dropped, profiles/EXPERIMENTS.md: XCD strips for these kernels -- neutral, they stage x per wavefront and are not bound by the fabric --; one lane
     //  per row with values and x staged -- 3 % faster on a repeated product, 3 % slower inside the Krylov loops)
-    if (P->prec_slot && P->tr.nruns > 0 && !(g_variant & 0x4000)) {
+    if (P->prec_slot && P->tr.nruns > 0 && !(g_variant & VAR_GATHER)) {
         const int vcap = 16 * P->tr.maxlen + 48, xcap = (P->tr.slots + 1) & ~1;
 #define GOT(NL) spmv_csr_pattern_team_staged_kernel<256, NL><<<wgs, 256, sizeof(double) * 4 * (size_t)(vcap + xcap), a.st>>>( \
             a.ptr, a.val, a.rowpat, P->prec36, P->prec_slot, a.x, a.y, Rows{a.rb, a.re, a.acc0}, a.nnz, P->tr, vcap, xcap, guard)
@@ -291,7 +334,7 @@ static long long dom_gather_shape(const LaunchArgs &a, DomTile &TL, int &run)
     // the chunks' shared x lines: 0.58 -> 0.535 ms).  Variant bit28 forces the plain chunks round-robin (tests of that path at small sizes).
     // (Measured and dropped, profiles/EXPERIMENTS.md: tiles of 32 / 64 / 256 columns, XCD regions of the planes, four rows per lane, 512 / 1024 lanes per
     // workgroup, kernarg preload of the arguments.)
-    const bool plain = (g_variant & 0x10000000) != 0;
+    const bool plain = (g_variant & VAR_DOM_CHUNKS) != 0;
     TL = DomTile{0, 0, 0, 0};
     long long wgs = (rows + 511) / 512;
     if (!plain) {
@@ -311,11 +354,11 @@ static long long dom_gather_shape(const LaunchArgs &a, DomTile &TL, int &run)
 // which form the whole-matrix product of this plan takes: 0 the gathering kernels, 1 the z-marching kernel with the faces' masks, 2 its BOX form (x and y alone are streamed)
 extern "C" int liship_csr_plan_marching(liship_csr_plan_t p)
 {
-    if (!p || !p->rowpat || !p->ptab8 || !p->vrec || !p->drec || p->products || !g_row_values || !g_row_patterns || !g_index_codes) return 0;
-    LaunchArgs a{};
-    a.plan = p; a.rb = 0; a.re = p->n; a.y = reinterpret_cast<double *>(16);
+    if (!p) return 0;
+    const PlanArrays A = plan_arrays(p);
+    if (!A.rowpat || !A.vrec || !p->ptab8 || !p->drec || p->products) return 0;
     DomMarch M;
-    if (!dom_march_shape(a, M)) return 0;
+    if (!dom_march_shape(probe_args(p), M)) return 0;
     return ((M.order & 3) != 2 && g_dom_march != 3 && M.z0 >= p->box_z0 && M.z1 <= p->box_z1) ? 2 : 1;
 }
 
@@ -351,13 +394,12 @@ static int dom_parts(const LaunchArgs &a, DomPart (&parts)[3])
     parts[0] = gather(a.rb, a.re);
     return 1;
 }
-static long long dom_shape(const LaunchArgs &a, DomTile &TL, int &run)      // the number of workgroups with rows = partial sums of the fused forms (TL, run: the gathering kernel's, when it is the only part)
+static long long dom_shape(const LaunchArgs &a)      // the number of workgroups with rows = partial sums of the fused forms
 {
     DomPart parts[3];
     const int np = dom_parts(a, parts);
     long long total = 0;
     for (int i = 0; i < np; i++) total += parts[i].wgs;
-    TL = parts[0].TL; run = parts[0].run;
     return total;
 }
 
@@ -450,7 +492,7 @@ void launch_geom(const LaunchArgs &a, int unroll, bool plan_products, int batch)
 {
     const bool val16 = aligned16(a.val), idx16 = aligned16(a.idx);
     const bool idx8 = (reinterpret_cast<uintptr_t>(a.idx) & 7u) == 0;
-    const bool products = plan_products || (g_variant & 6) != 0 || !(val16 && idx16);
+    const bool products = plan_products || (g_variant & (VAR_SCALAR_LOADS | VAR_PRODUCTS)) != 0 || !(val16 && idx16);
     if (a.lcol && plan_products && is_local_geom(G) && g_variant == 0 && val16) {     // long rows, few distinct columns per row block
         launch_local<G, 0>(a, nullptr, nullptr, nullptr, 0);
         return;
@@ -463,21 +505,21 @@ void launch_geom(const LaunchArgs &a, int unroll, bool plan_products, int batch)
         return;
     } else {
     if (products) {
-        const bool vec = !(g_variant & 2) && val16 && idx8;        // (variant bit 1: the scalar-load form on aligned arrays too -- tests)
+        const bool vec = !(g_variant & VAR_SCALAR_LOADS) && val16 && idx8;        // (variant bit 1: the scalar-load form on aligned arrays too -- tests)
         if (!vec) launch_products<G, 0>(a);
         else if (batch == 2) launch_products<G, 2>(a);
         else           launch_products<G, 4>(a);
         return;
     }
     const int U = unroll;
-    if (a.rowpat && a.ptab8 && a.vrec && (g_variant & ~0x30004000) == 0) {            // the rows' values ride in the pattern records: one byte per row
+    if (a.rowpat && a.ptab8 && a.vrec && variant_only(VAR_DOM_CHUNKS | VAR_ROUND2_RECORDS | VAR_GATHER)) {            // the rows' values ride in the pattern records: one byte per row
         constexpr Geometry g = kGeom[G];
         const int chunks = (a.re - a.rb + g.block - 1) / g.block;       // rows [rb, re) in chunks of one workgroup's lanes, two per workgroup
         // beyond the Infinity Cache (256 MB of x) the two-rows-per-lane form wins (16 B requests: 320^3 +4 %, 448^3 +13 %, 512^3 +7 %);
         // below it x stays cache-resident from product to product and the one-row form is 15 % faster (tools/valuerec_probe.py)
-        const bool pairs = (g_variant & 0x4000) || (long long)(a.re - a.rb) * 8 > (256ll << 20);
+        const bool pairs = (g_variant & VAR_GATHER) || (long long)(a.re - a.rb) * 8 > (256ll << 20);
         // one pattern carries most rows: its gathers are issued together with the pattern bytes (one round trip, no LDS, no barrier)
-        if (chunks > 0 && a.plan && a.plan->drec && !(g_variant & 0x20000000)) { launch_dom(a); return; }
+        if (chunks > 0 && a.plan && a.plan->drec && !(g_variant & VAR_ROUND2_RECORDS)) { launch_dom(a); return; }
         if (chunks > 0 && pairs)
             spmv_csr_valuerec_pair_kernel<g.block, 1><<<(chunks + 1) / 2, g.block, 0, a.st>>>(a.rowpat, a.vrec, a.npat1 - 1, a.x, a.y, Rows{a.rb, a.re, a.acc0});
         else if (chunks > 0)
@@ -485,14 +527,14 @@ void launch_geom(const LaunchArgs &a, int unroll, bool plan_products, int batch)
                 a.rowpat, a.vrec, a.npat1 - 1, a.x, a.y, a.blk, a.bfirst, chunks, Rows{a.rb, a.re, a.acc0});
         return;
     }
-    if (a.rowpat && a.vrecw && (g_variant & ~0x4000) == 0 && launch_wide(a, nullptr)) return;      // wide records, x staged, the dominant pattern in scalar registers
-    if (a.rowpat && a.vrecw && (g_variant & ~0x4000) == 0) {      // the rows' values ride in WIDE records (rows of up to 32 entries): one byte per row
+    if (a.rowpat && a.vrecw && variant_only(VAR_GATHER) && launch_wide(a, nullptr)) return;      // wide records, x staged, the dominant pattern in scalar registers
+    if (a.rowpat && a.vrecw && variant_only(VAR_GATHER)) {      // the rows' values ride in WIDE records (rows of up to 32 entries): one byte per row
         constexpr Geometry g = kGeom[G];
         spmv_csr_valuerecw_kernel<g.block, 0><<<a.nb, g.block, (size_t)(a.npat1 - 1) * (sizeof(double) * PATW_LEN + sizeof(int) * PATW_OFF), a.st>>>(
             a.rowpat, a.vrecw, a.npat1 - 1, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0});
         return;
     }
-    if (a.rowpat && a.ptab8 && (g_variant & ~0x20000000) == 0) {      // patterns of at most 7 offsets: gathers ahead of the slice
+    if (a.rowpat && a.ptab8 && variant_only(VAR_ROUND2_RECORDS)) {      // patterns of at most 7 offsets: gathers ahead of the slice
         // (round 3, measured and dropped: a wavefront per 64-row line segment, four lines per workgroup, the dominant pattern's gathers issued
         //  with the pattern bytes -- the shape that paid for the value records -- is bit-identical and 1.2 % faster at 512^3, 1.842 -> 1.821 ms:
         //  this kernel is bound by its value stream, not by x: profiles/r03_valuerec_dom_experiments.txt)
@@ -501,12 +543,12 @@ void launch_geom(const LaunchArgs &a, int unroll, bool plan_products, int batch)
             a.ptr, a.val, a.rowpat, a.rowrel, a.ptab8, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0}, a.nnz, nullptr, nullptr, nullptr, 0, xcd_strips(a));
         return;
     }
-    if (a.rowpat && a.plan && a.plan->prec36 && g_team && (g_variant & ~0x4000) == 0) {    // patterns of 8..32 offsets, values streamed: four lanes per row (0x2000: the general kernel, A/B)
+    if (a.rowpat && a.plan && a.plan->prec36 && g_team && variant_only(VAR_GATHER)) {    // patterns of 8..32 offsets, values streamed: four lanes per row (0x2000: the general kernel, A/B)
         // (measured and dropped, profiles/r03_pattern_team_kernel.txt: XCD slabs / runs of 1024+ workgroups +-2 %; the pattern byte speculated 2 %)
         launch_team(a, nullptr);
         return;
     }
-    if (a.rowpat && a.ptab_len <= PAT_TABLE && (g_variant & ~0x2000) == 0) {    // one byte per ROW (the plan found <= 255 row patterns); 0x2000: experiment, table in LDS even for short patterns
+    if (a.rowpat && a.ptab_len <= PAT_TABLE && variant_only(VAR_PATTERN_LDS)) {    // one byte per ROW (the plan found <= 255 row patterns); 0x2000: experiment, table in LDS even for short patterns
         constexpr Geometry g = kGeom[G];
 #define GOP(UU) spmv_csr_pattern_kernel<g.block, g.work, UU, 0><<<a.nb, g.block, 0, a.st>>>( \
             a.ptr, a.idx, a.val, a.rowpat, a.rowrel, a.ptab, a.ptab_len, a.npat1, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0}, a.nnz)
@@ -514,7 +556,7 @@ void launch_geom(const LaunchArgs &a, int unroll, bool plan_products, int batch)
 #undef GOP
         return;
     }
-    if (a.codes && (g_variant & ~0xF0) == 0) {     // one-byte column codes (the plan found <= 255 diagonals)
+    if (a.codes && variant_only(VAR_GEOM)) {     // one-byte column codes (the plan found <= 255 diagonals)
         constexpr Geometry g = kGeom[G];
 #define GO(UU) spmv_csr_coded_kernel<g.block, g.work, UU, 0><<<a.nb, g.block, 0, a.st>>>( \
             a.ptr, a.idx, a.val, a.codes, a.dict, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0}, a.nnz, nullptr, nullptr, nullptr, 0, xcd_strips(a))
@@ -529,10 +571,10 @@ void launch_geom(const LaunchArgs &a, int unroll, bool plan_products, int batch)
 }
 
 template <int G, int DOT>
-void launch_rowgather_dot(const LaunchArgs &a, int unroll, const double *w, double *partial, int pstride = 0)
+void launch_rowgather_dot(const LaunchArgs &a, int unroll, const double *w, double *partial, int pstride)
 {
     constexpr Geometry g = kGeom[G];
-    if (a.rowpat && a.ptab8 && a.vrec && a.plan && a.plan->drec && !(g_variant & 0x20002000) && g.block == 256) {    // the dominant pattern speculated (see launch_geom)
+    if (a.rowpat && a.ptab8 && a.vrec && a.plan && a.plan->drec && !(g_variant & (VAR_ROUND2_RECORDS | VAR_PATTERN_LDS)) && g.block == 256) {    // the dominant pattern speculated (see launch_geom)
         const liship_csr_plan_s *P = a.plan;
         {                                                 // four rows per lane, a wavefront per row block
             int wslot = -1;
@@ -544,26 +586,26 @@ void launch_rowgather_dot(const LaunchArgs &a, int unroll, const double *w, doub
             return;
         }
     }
-    if (a.rowpat && a.ptab8 && a.vrec && !(g_variant & 0x2000) && g.block == 256 &&
-        ((g_variant & 0x4000) || (long long)(a.re - a.rb) * 8 > (256ll << 20))) {          // two rows per lane beyond the Infinity Cache (see launch_geom)
+    if (a.rowpat && a.ptab8 && a.vrec && !(g_variant & VAR_PATTERN_LDS) && g.block == 256 &&
+        ((g_variant & VAR_GATHER) || (long long)(a.re - a.rb) * 8 > (256ll << 20))) {          // two rows per lane beyond the Infinity Cache (see launch_geom)
         spmv_csr_valuerec_pair_dot_kernel<256, DOT><<<(a.nb + 1) / 2, 256, 0, a.st>>>(
             a.rowpat, a.vrec, a.npat1 - 1, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0},
             w, partial, liship_internal_guard(), pstride);
         return;
     }
-    if (a.rowpat && a.ptab8 && a.vrec && !(g_variant & 0x2000)) {
+    if (a.rowpat && a.ptab8 && a.vrec && !(g_variant & VAR_PATTERN_LDS)) {
         spmv_csr_valuerec_kernel<g.block, 2, DOT><<<(a.nb + 1) / 2, g.block, 0, a.st>>>(
             a.rowpat, a.vrec, a.npat1 - 1, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0},
             w, partial, liship_internal_guard(), pstride);
         return;
     }
-    if (a.rowpat && a.ptab8 && !(g_variant & 0x2000)) {
+    if (a.rowpat && a.ptab8 && !(g_variant & VAR_PATTERN_LDS)) {
         spmv_csr_pattern7_kernel<g.block, g.work, DOT><<<a.nb, g.block, 0, a.st>>>(
             a.ptr, a.val, a.rowpat, a.rowrel, a.ptab8, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0}, a.nnz,
             w, partial, liship_internal_guard(), pstride, xcd_strips(a));
         return;
     }
-    if (a.rowpat && a.vrecw && !(g_variant & 0x2000)) {
+    if (a.rowpat && a.vrecw && !(g_variant & VAR_PATTERN_LDS)) {
         spmv_csr_valuerecw_kernel<g.block, DOT><<<a.nb, g.block, (size_t)(a.npat1 - 1) * (sizeof(double) * PATW_LEN + sizeof(int) * PATW_OFF), a.st>>>(
             a.rowpat, a.vrecw, a.npat1 - 1, a.x, a.y, a.blk, a.bfirst, a.nb, Rows{a.rb, a.re, a.acc0},
             w, partial, liship_internal_guard(), pstride);
@@ -591,7 +633,7 @@ void launch_rowgather_dot(const LaunchArgs &a, int unroll, const double *w, doub
 }
 
 template <int G, int DOT>
-void launch_products_dot(const LaunchArgs &a, int batch, const double *w, double *partial, int pstride = 0)
+void launch_products_dot(const LaunchArgs &a, int batch, const double *w, double *partial, int pstride)
 {
     constexpr Geometry g = kGeom[G];
     if (a.lcol && is_local_geom(G)) {
@@ -616,11 +658,10 @@ static void tail_prepass(const liship_csr_plan_s *p, const LaunchArgs &a)
     spmv_csr_tail_fold_kernel<<<(p->nheavy + 63) / 64, 64, 0, a.st>>>(p->nheavy, a.ptr, a.blk, p->thead, RW, p->tpart, a.y, a.rowmap);
 }
 
-int launch_csr(liship_csr_plan_t p, const LaunchArgs &a0)
+int launch_csr(const LaunchArgs &a)
 {
-    if (a0.nb <= 0) return 0;
-    LaunchArgs a = a0;
-    a.plan = p;
+    if (a.nb <= 0) return 0;
+    const liship_csr_plan_s *p = a.plan;
     tail_prepass(p, a);
     switch (p->geom) {
         case 0: launch_geom<0>(a, p->unroll, p->products != 0, p->batch); break;
@@ -634,6 +675,23 @@ int launch_csr(liship_csr_plan_t p, const LaunchArgs &a0)
     return 0;
 }
 
+// the row blocks' fused product (DOT 1: w.y, 2: and y.y) in the plan's geometry: a partial per row block at partial[0, a.nb), the second sums `pstride`
+// behind (0: a.nb behind)
+template <int DOT>
+void launch_blocks_dot(const LaunchArgs &a, const double *w, double *partial, int pstride)
+{
+    const liship_csr_plan_s *p = a.plan;
+    if (p->products) {
+        switch (p->geom) {              // a plan with block-local columns (or one that has them switched off), else geometry 1
+            case LOCAL_GEOM:   launch_products_dot<LOCAL_GEOM, DOT>(a, p->batch, w, partial, pstride); break;
+            case LOCAL_GEOM4:  launch_products_dot<LOCAL_GEOM4, DOT>(a, p->batch, w, partial, pstride); break;
+            case LOCAL_GEOM_R: launch_products_dot<LOCAL_GEOM_R, DOT>(a, p->batch, w, partial, pstride); break;
+            default:           launch_products_dot<1, DOT>(a, p->batch, w, partial, pstride);
+        }
+    } else if (p->geom == 1) launch_rowgather_dot<1, DOT>(a, p->unroll, w, partial, pstride);
+    else                     launch_rowgather_dot<0, DOT>(a, p->unroll, w, partial, pstride);
+}
+
 } // namespace
 
 // Does the product of this plan run one of the kernels with a row split of their own (16 / 64 rows per wavefront: the team and staged kernels) under the
@@ -642,26 +700,28 @@ int launch_csr(liship_csr_plan_t p, const LaunchArgs &a0)
 // 2125 it/s, profiles/r03_pattern_team_kernel.txt).
 static bool plan_runs_wide(const liship_csr_plan_s *p, int rb, int re)      // the staged wide-record kernels: an epilogue of their own (one partial per workgroup of 256 rows / block rows)
 {
-    return p && p->rowpat && g_row_patterns && g_index_codes && g_team && !p->ptab8 && g_row_values && p->vrecw && g_variant == 0 &&
-           ((p->wdrec && p->wstage && p->wd.len > 0) || block_rows_serve(p, rb, re));
+    if (!p) return false;
+    const PlanArrays A = plan_arrays(p);
+    return A.rowpat && A.vrecw && !p->ptab8 && g_team && g_variant == 0 && ((p->wdrec && p->wstage && p->wd.len > 0) || block_rows_serve(p, rb, re));
 }
 static bool plan_runs_teams(const liship_csr_plan_s *p)     // the four-lanes-per-row kernels (values streamed): no epilogue
 {
-    if (!p || !p->rowpat || !g_row_patterns || !g_index_codes || !g_team || p->ptab8) return false;
-    if (g_row_values && p->vrecw) return false;
-    return p->prec36 != nullptr && (g_variant & ~0x4000) == 0;
+    if (!p) return false;
+    const PlanArrays A = plan_arrays(p);
+    return A.rowpat && !A.vrecw && !p->ptab8 && g_team && p->prec36 && variant_only(VAR_GATHER);
 }
 static bool plan_runs_dom(const liship_csr_plan_s *p)       // the dominant-pattern product of a plan with value records: its tiles have an epilogue of their own too
-{                                                           // (variant 0x4000: the fused dots stay with the row blocks' partial sums, spmv_csr_valuerec_dom_dot4_kernel -- A/B, tests)
-    return p && p->rowpat && g_row_patterns && g_index_codes && p->ptab8 && g_row_values && p->vrec && p->drec && !p->products &&
-           kGeom[p->geom].block == 256 && (g_variant & ~0x10000000) == 0 && !g_row_block_dots;
+{                                                           // (variant VAR_GATHER: the fused dots stay with the row blocks' partial sums, spmv_csr_valuerec_dom_dot4_kernel -- A/B, tests)
+    if (!p) return false;
+    const PlanArrays A = plan_arrays(p);
+    return A.rowpat && A.vrec && p->ptab8 && p->drec && !p->products && kGeom[p->geom].block == 256 && variant_only(VAR_DOM_CHUNKS) && !g_row_block_dots;
 }
 // the reordered form serves whole-matrix products of the plan in its shipped configuration; row ranges and the fused reductions (whose partial sums follow the
 // ORIGINAL row blocks) keep the original numbering
 static bool plan_has_reordered_form(const liship_csr_plan_s *p)      // ... for callers that iterate in the new numbering (liship_csr_plan_reordered_form)
 {
     if (!p || !p->inner || !g_reorder || g_variant != 0) return false;
-    return p->inner->products ? (p->inner->lcol && g_local_cols) : true;
+    return !p->inner->products || plan_arrays(p->inner).lcol;
 }
 // ... and for single products: long rows only.  A product in the caller's numbering pays a gather of x and a scattered store of y, one random access per node each:
 // with 3 unknowns per node and ~70 entries per row that is 8 % of the product (Queen class), with scalar unknowns and 7 entries per row it is four times the product
@@ -671,11 +731,10 @@ static bool plan_has_reordered_form(const liship_csr_plan_s *p)      // ... for 
 static bool plan_runs_reordered(const liship_csr_plan_s *p) { return g_reorder == 2 && plan_has_reordered_form(p) && p->products && p->inner->products && p->ncols <= p->n; }      // (a rank's local matrix: x carries ghost entries behind the rows -- its single products keep the caller's numbering)
 static int launch_reordered(liship_csr_plan_t p, const double *x, double *y, hipStream_t st)
 {
-    const liship_csr_plan_s *q = p->inner;
     csr_reorder_gather_kernel<<<(p->n / 3 + 256) / 256, 256, 0, st>>>(p->n, p->r_perm, x, p->r_x);
-    LaunchArgs a{p->r_ptr, p->r_idx, p->r_val, p->r_x, y, q->blk, 0, q->nblocks, 0, q->n, (int)q->nnz, st, nullptr, nullptr, q->lcol, q->dcol, q->doff, p->first_term ? -0.0 : 0.0};
+    LaunchArgs a = plan_args(p->inner, p->r_ptr, p->r_idx, p->r_val, p->r_x, y, st);
     a.rowmap = p->r_perm;
-    return launch_csr(p->inner, a);
+    return launch_csr(a);
 }
 extern "C" int liship_csr_plan_fused_dots(liship_csr_plan_t p) { return (plan_runs_teams(p) || plan_runs_reordered(p)) ? 0 : 1; }
 // The reordered form as a matrix of its own -- P A P^T: its plan (owned by `p`), its arrays, the permutation (new position -> original row) -- for a caller that keeps
@@ -738,19 +797,15 @@ extern "C" long long liship_csr_plan_fused_slots(liship_csr_plan_t p)
 extern "C" int liship_csr_plan_block2_march(liship_csr_plan_t p)
 {
     if (!p || p->b2.S <= 0 || !block_rows_serve(p, 0, p->n)) return 0;
-    LaunchArgs a{};
-    a.plan = p; a.rb = 0; a.re = p->n; a.y = reinterpret_cast<double *>(16); a.acc0 = p->first_term ? -0.0 : 0.0;
     Block2March M;
-    return block2_shape(a, M) ? 1 : 0;
+    return block2_shape(probe_args(p), M) ? 1 : 0;
 }
 extern "C" int liship_csr_plan_box27(liship_csr_plan_t p)
 {
     if (!p || p->b27.S <= 0 || !p->vrecw || !g_team || !g_row_patterns || !g_index_codes) return 0;
-    LaunchArgs a{};
-    a.plan = p; a.rb = 0; a.re = p->n; a.y = reinterpret_cast<double *>(16); a.acc0 = p->first_term ? -0.0 : 0.0;
     Box27 M;
     int lpw = 0;
-    return box27_shape(a, M, lpw) ? 1 : 0;
+    return box27_shape(probe_args(p), M, lpw) ? 1 : 0;
 }
 
 extern "C" int liship_spmv_csr_f64(liship_csr_plan_t p, const int *ptr, const int *idx,
@@ -758,8 +813,50 @@ extern "C" int liship_spmv_csr_f64(liship_csr_plan_t p, const int *ptr, const in
 {
     if (!p) return LISHIP_ERR_ARG;
     if (plan_runs_reordered(p) && x != y) return launch_reordered(p, x, y, as_stream(stream));
-    LaunchArgs a{ptr, idx, val, x, y, p->blk, 0, p->nblocks, 0, p->n, (int)p->nnz, as_stream(stream), g_index_codes ? p->codes : nullptr, p->dict, g_local_cols ? p->lcol : nullptr, p->dcol, p->doff, p->first_term ? -0.0 : 0.0, (g_row_patterns && g_index_codes) ? p->rowpat : nullptr, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, p->ptab8, g_row_values ? p->vrec : nullptr, p->order, g_row_values ? p->vrecw : nullptr};
-    return launch_csr(p, a);
+    return launch_csr(plan_args(p, ptr, idx, val, x, y, as_stream(stream)));
+}
+
+extern "C" int liship_spmv_csr_rows_f64(liship_csr_plan_t p, int row_begin, int row_end, const int *ptr,
+                                        const int *idx, const double *val, const double *x, double *y,
+                                        void *stream)
+{
+    if (!p || row_begin < 0 || row_end > p->n) return LISHIP_ERR_ARG;
+    if (row_begin >= row_end || p->nblocks == 0) return 0;
+    return launch_csr(plan_args(p, row_begin, row_end, ptr, idx, val, x, y, as_stream(stream)));
+}
+
+// the variants the fused entry points serve
+constexpr int VAR_FUSED = VAR_PATTERN_LDS | VAR_GATHER | VAR_DOM_CHUNKS | VAR_ROUND2_RECORDS;
+
+// The fused product (dot 1: w.y, 2: and y.y as well) over the rows of `a`, in the form the plan runs: the staged wide-record kernels (a partial per workgroup of
+// 256 rows / block rows), the dominant-pattern product (a partial per workgroup of the range's own tiles) or the row blocks' kernels (a partial per row block).
+// The partials go to partial[0, count), the second sums `pstride` behind (0: `count` behind); returns count.  A form that needs more than `room` partials
+// refuses (-1, nothing launched) when `strict`, else leaves the call to the next form.
+static int launch_fused(const LaunchArgs &a, int dot, const double *w, double *partial, int pstride, size_t room, bool strict)
+{
+    const liship_csr_plan_s *p = a.plan;
+    const double *guard = liship_internal_guard();
+    if (plan_runs_wide(p, a.rb, a.re) && a.rb < a.re) {
+        if ((size_t)((a.re - a.rb + 255) / 256) <= room) {
+            int wgs = 0;
+            launch_wide(a, guard, dot, w, partial, pstride, &wgs);
+            return wgs;
+        }
+        if (strict) return -1;
+    }
+    if (plan_runs_dom(p)) {
+        const long long wgs = dom_shape(a);
+        if ((size_t)wgs <= room) {
+            launch_dom(a, dot, w, partial, guard, pstride);
+            return (int)wgs;
+        }
+        if (strict) return -1;
+    }
+    if (a.nb <= 0) return 0;
+    if ((size_t)a.nb > room) return -1;
+    tail_prepass(p, a);
+    if (dot == 2) launch_blocks_dot<2>(a, w, partial, pstride); else launch_blocks_dot<1>(a, w, partial, pstride);
+    return a.nb;
 }
 
 // y = A x and, in the same pass, result[0] = sum_r w[r]*y[r] (w may be x), result[1] = sum_r y[r]^2 if want_sumsq.
@@ -773,61 +870,13 @@ extern "C" int liship_spmv_csr_dot_f64(liship_csr_plan_t p, const int *ptr, cons
     if (!p || !w || !result || !work) return LISHIP_ERR_ARG;
     if (plan_runs_teams(p) || plan_runs_reordered(p) || liship_internal_ref_chunks()) return LISHIP_ERR_ARG;      // (reference-order sums: the product, then one ordered pass)
     const size_t slots = liship_reduce_work_bytes() / sizeof(double) / 4;
-    if ((g_variant & ~0x30006000) != 0 || (size_t)p->nblocks > slots || !aligned16(val) || !aligned16(idx)) return LISHIP_ERR_ARG;
+    if (!variant_only(VAR_FUSED) || (size_t)p->nblocks > slots || !aligned16(val) || !aligned16(idx)) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    if (p->nblocks == 0) { HIP_TRY(hipMemsetAsync(result, 0, sizeof(double) * 2, st)); return 0; }
     double *partial = static_cast<double *>(work), *spare = partial + 2 * slots;
-    if (plan_runs_wide(p, 0, p->n) && p->n > 0 && (size_t)((p->n + 255) / 256) <= slots) {       // wide records, x staged: a partial per workgroup of 256 rows
-        LaunchArgs aw{ptr, idx, val, x, y, p->blk, 0, p->nblocks, 0, p->n, (int)p->nnz, as_stream(stream), p->codes, p->dict, nullptr, nullptr, nullptr, p->first_term ? -0.0 : 0.0, p->rowpat, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, nullptr, nullptr, nullptr, p->vrecw};
-        aw.plan = p;
-        int wgs = 0;
-        launch_wide(aw, liship_internal_guard(), want_sumsq ? 2 : 1, w, partial, 0, &wgs);
-        LAUNCH_CHECK();
-        return liship_internal_fold(wgs, want_sumsq ? 2 : 1, wgs, partial, spare, result, stream);
-    }
-    LaunchArgs a{ptr, idx, val, x, y, p->blk, 0, p->nblocks, 0, p->n, (int)p->nnz, as_stream(stream), g_index_codes ? p->codes : nullptr, p->dict, g_local_cols ? p->lcol : nullptr, p->dcol, p->doff, p->first_term ? -0.0 : 0.0, (g_row_patterns && g_index_codes) ? p->rowpat : nullptr, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, p->ptab8, g_row_values ? p->vrec : nullptr, p->order, g_row_values ? p->vrecw : nullptr};
-    a.plan = p;
-    tail_prepass(p, a);
-    if (p->nblocks == 0) { HIP_TRY(hipMemsetAsync(result, 0, sizeof(double) * 2, a.st)); return 0; }
-    if (plan_runs_dom(p)) {                            // value records, dominant pattern: a partial per workgroup (tile) of the plain product's shape
-        DomTile TL;
-        int run = 1;
-        const long long wgs = dom_shape(a, TL, run);
-        const long long np = wgs;                         // a partial per workgroup
-        if (wgs > 0 && (size_t)np <= slots) {
-            launch_dom(a, want_sumsq ? 2 : 1, w, partial, liship_internal_guard(), 0);
-            LAUNCH_CHECK();
-            return liship_internal_fold((int)np, want_sumsq ? 2 : 1, (int)np, partial, spare, result, stream);
-        }
-    }
-    if (p->products && p->geom == LOCAL_GEOM) {      // a plan with block-local columns (or one that has them switched off)
-        if (want_sumsq) launch_products_dot<LOCAL_GEOM, 2>(a, p->batch, w, partial); else launch_products_dot<LOCAL_GEOM, 1>(a, p->batch, w, partial);
-    } else if (p->products && p->geom == LOCAL_GEOM4) {
-        if (want_sumsq) launch_products_dot<LOCAL_GEOM4, 2>(a, p->batch, w, partial); else launch_products_dot<LOCAL_GEOM4, 1>(a, p->batch, w, partial);
-    } else if (p->products && p->geom == LOCAL_GEOM_R) {
-        if (want_sumsq) launch_products_dot<LOCAL_GEOM_R, 2>(a, p->batch, w, partial); else launch_products_dot<LOCAL_GEOM_R, 1>(a, p->batch, w, partial);
-    } else if (p->products) {       // geometry 1
-        if (want_sumsq) launch_products_dot<1, 2>(a, p->batch, w, partial); else launch_products_dot<1, 1>(a, p->batch, w, partial);
-    } else if (p->geom == 1) { if (want_sumsq) launch_rowgather_dot<1, 2>(a, p->unroll, w, partial); else launch_rowgather_dot<1, 1>(a, p->unroll, w, partial); }
-    else if (want_sumsq) launch_rowgather_dot<0, 2>(a, p->unroll, w, partial);
-    else                 launch_rowgather_dot<0, 1>(a, p->unroll, w, partial);
+    const int np = launch_fused(plan_args(p, ptr, idx, val, x, y, st), want_sumsq ? 2 : 1, w, partial, 0, slots, false);      // (the row blocks fit: never -1)
     LAUNCH_CHECK();
-    return liship_internal_fold(p->nblocks, want_sumsq ? 2 : 1, p->nblocks, partial, spare, result, stream);
-}
-
-extern "C" int liship_spmv_csr_rows_f64(liship_csr_plan_t p, int row_begin, int row_end, const int *ptr,
-                                        const int *idx, const double *val, const double *x, double *y,
-                                        void *stream)
-{
-    if (!p || row_begin < 0 || row_end > p->n) return LISHIP_ERR_ARG;
-    if (row_begin >= row_end || p->nblocks == 0) return 0;
-    // row blocks whose interval [blk[b].row, blk[b+1].row) intersects [row_begin,row_end)
-    const v2i32 *br = p->blk_host;
-    int lo = 0, hi = p->nblocks;                 // first b with br[b+1].row > row_begin
-    while (lo < hi) { int mid = (lo + hi) / 2; if (br[mid + 1].x > row_begin) hi = mid; else lo = mid + 1; }
-    const int bfirst = lo;
-    lo = bfirst; hi = p->nblocks;                // first b with br[b].row >= row_end
-    while (lo < hi) { int mid = (lo + hi) / 2; if (br[mid].x >= row_end) hi = mid; else lo = mid + 1; }
-    LaunchArgs a{ptr, idx, val, x, y, p->blk, bfirst, lo - bfirst, row_begin, row_end, (int)p->nnz, as_stream(stream), g_index_codes ? p->codes : nullptr, p->dict, g_local_cols ? p->lcol : nullptr, p->dcol, p->doff, p->first_term ? -0.0 : 0.0, (g_row_patterns && g_index_codes) ? p->rowpat : nullptr, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, p->ptab8, g_row_values ? p->vrec : nullptr, nullptr, g_row_values ? p->vrecw : nullptr};
-    return launch_csr(p, a);
+    return liship_internal_fold(np, want_sumsq ? 2 : 1, np, partial, spare, result, stream);
 }
 
 // The fused-reduction product in parts (a multi-rank job runs the rows that reference no ghost column while the
@@ -842,59 +891,15 @@ extern "C" int liship_spmv_csr_rows_dot_f64(liship_csr_plan_t p, int row_begin, 
     if (!p || !w || !work || !slots_used || row_begin < 0 || row_end > p->n || slot_base < 0) return LISHIP_ERR_ARG;
     if (plan_runs_teams(p) || liship_internal_ref_chunks()) return LISHIP_ERR_ARG;
     const size_t slots = liship_reduce_work_bytes() / sizeof(double) / 4;
-    if ((g_variant & ~0x30006000) != 0 || !aligned16(val) || !aligned16(idx)) return LISHIP_ERR_ARG;
+    if (!variant_only(VAR_FUSED) || !aligned16(val) || !aligned16(idx)) return LISHIP_ERR_ARG;
     *slots_used = 0;
     if (row_begin >= row_end || p->nblocks == 0) return 0;
-    if (plan_runs_wide(p, row_begin, row_end)) {       // wide records, x staged: a partial per workgroup of 256 rows (block rows) of the range
-        int wgs = (row_end - row_begin + 255) / 256;
-        if ((size_t)slot_base + (size_t)wgs > slots) return LISHIP_ERR_ARG;
-        LaunchArgs aw{ptr, idx, val, x, y, p->blk, 0, p->nblocks, row_begin, row_end, (int)p->nnz, as_stream(stream), p->codes, p->dict, nullptr, nullptr, nullptr, p->first_term ? -0.0 : 0.0, p->rowpat, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, nullptr, nullptr, nullptr, p->vrecw};
-        aw.plan = p;
-        launch_wide(aw, liship_internal_guard(), want_sumsq ? 2 : 1, w, static_cast<double *>(work) + slot_base, (int)slots, &wgs);
-        LAUNCH_CHECK();
-        *slots_used = wgs;
-        return 0;
-    }
-    if (plan_runs_dom(p)) {                            // value records, dominant pattern: a partial per workgroup of the range's own tiles
-        LaunchArgs ad{ptr, idx, val, x, y, p->blk, 0, p->nblocks, row_begin, row_end, (int)p->nnz, as_stream(stream), p->codes, p->dict, nullptr, nullptr, nullptr, p->first_term ? -0.0 : 0.0, p->rowpat, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, p->ptab8, p->vrec, nullptr, nullptr};
-        ad.plan = p;
-        DomTile TL;
-        int run = 1;
-        const long long wgs = dom_shape(ad, TL, run);
-        const long long np = wgs;
-        if ((size_t)slot_base + (size_t)np > slots) return LISHIP_ERR_ARG;
-        launch_dom(ad, want_sumsq ? 2 : 1, w, static_cast<double *>(work) + slot_base, liship_internal_guard(), (int)slots);
-        LAUNCH_CHECK();
-        *slots_used = (int)np;
-        return 0;
-    }
-    const v2i32 *br = p->blk_host;
-    int lo = 0, hi = p->nblocks;                 // first b with br[b+1].row > row_begin
-    while (lo < hi) { int mid = (lo + hi) / 2; if (br[mid + 1].x > row_begin) hi = mid; else lo = mid + 1; }
-    const int bfirst = lo;
-    lo = bfirst; hi = p->nblocks;                // first b with br[b].row >= row_end
-    while (lo < hi) { int mid = (lo + hi) / 2; if (br[mid].x >= row_end) hi = mid; else lo = mid + 1; }
-    const int nb = lo - bfirst;
-    if (nb <= 0) return 0;
-    if ((size_t)slot_base + (size_t)nb > slots) return LISHIP_ERR_ARG;
-    double *partial = static_cast<double *>(work) + slot_base;
-    LaunchArgs a{ptr, idx, val, x, y, p->blk, bfirst, nb, row_begin, row_end, (int)p->nnz, as_stream(stream), g_index_codes ? p->codes : nullptr, p->dict, g_local_cols ? p->lcol : nullptr, p->dcol, p->doff, p->first_term ? -0.0 : 0.0, (g_row_patterns && g_index_codes) ? p->rowpat : nullptr, p->rowrel, p->ptab, p->ptab_len, p->npat + 1, p->ptab8, g_row_values ? p->vrec : nullptr, nullptr, g_row_values ? p->vrecw : nullptr};
-    a.plan = p;
-    tail_prepass(p, a);
-    const int ps = (int)slots;
-    if (p->products && p->geom == LOCAL_GEOM) {
-        if (want_sumsq) launch_products_dot<LOCAL_GEOM, 2>(a, p->batch, w, partial, ps); else launch_products_dot<LOCAL_GEOM, 1>(a, p->batch, w, partial, ps);
-    } else if (p->products && p->geom == LOCAL_GEOM4) {
-        if (want_sumsq) launch_products_dot<LOCAL_GEOM4, 2>(a, p->batch, w, partial, ps); else launch_products_dot<LOCAL_GEOM4, 1>(a, p->batch, w, partial, ps);
-    } else if (p->products && p->geom == LOCAL_GEOM_R) {
-        if (want_sumsq) launch_products_dot<LOCAL_GEOM_R, 2>(a, p->batch, w, partial, ps); else launch_products_dot<LOCAL_GEOM_R, 1>(a, p->batch, w, partial, ps);
-    } else if (p->products) {
-        if (want_sumsq) launch_products_dot<1, 2>(a, p->batch, w, partial, ps); else launch_products_dot<1, 1>(a, p->batch, w, partial, ps);
-    } else if (p->geom == 1) { if (want_sumsq) launch_rowgather_dot<1, 2>(a, p->unroll, w, partial, ps); else launch_rowgather_dot<1, 1>(a, p->unroll, w, partial, ps); }
-    else if (want_sumsq) launch_rowgather_dot<0, 2>(a, p->unroll, w, partial, ps);
-    else                 launch_rowgather_dot<0, 1>(a, p->unroll, w, partial, ps);
+    const size_t room = (size_t)slot_base < slots ? slots - (size_t)slot_base : 0;
+    const int np = launch_fused(plan_args(p, row_begin, row_end, ptr, idx, val, x, y, as_stream(stream)), want_sumsq ? 2 : 1, w,
+                                static_cast<double *>(work) + slot_base, (int)slots, room, true);
+    if (np < 0) return LISHIP_ERR_ARG;
     LAUNCH_CHECK();
-    *slots_used = nb;
+    *slots_used = np;
     return 0;
 }
 

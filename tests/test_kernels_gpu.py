@@ -71,7 +71,7 @@ def _chain_mode_for_the_long_row_cases(request, lib):
         check(lib.liship_spmv_csr_set_long_row_tree(1))
 
 
-# liship_spmv_csr_set_variant bits (lis_amd/csrc/kernels/spmv_csr.hip): 0 = shipped row-gather kernel with LDS-DMA;
+# liship_spmv_csr_set_variant bits (named VAR_* in lis_amd/csrc/kernels/csr_kernels.hpp): 0 = shipped row-gather kernel with LDS-DMA;
 # 0x2 / 0x4 products kernel (scalar / vector loads); 0x10 / 0x50 the 256 / 2048 and 512 / 4096 geometries; 0x1000000 unaligned row blocks.  Every value selects kernels that give the reference's bits.
 VARIANTS = [0x0, 0x2, 0x4, 0x10, 0x12, 0x14, 0x50, 0x54, 0x1000000, 0x1000004]
 
@@ -456,7 +456,7 @@ CODED_CASES = {
 TEAM_FORM = {"s19_varcoef_9x10x21": 2, "star9_varcoef_60x70": 2, "star13_varcoef_20x18x30": 2, "box27_varcoef_ghost_plane": 2, "box27_varcoef_foreign": 2, "box27_18x15x13": 2, "box9_70x50": 2, "box27_varcoef_21x10x9": 2, "box27_varcoef_7x6x70": 1, "box9_varcoef_130x77": 2}
 
 
-# liship_spmv_csr_set_variant bits that select the value-record kernels by hand: 3 the general pattern kernel, 4 the round-2 kernels by
+# liship_spmv_csr_set_variant bits (VAR_* in lis_amd/csrc/kernels/csr_kernels.hpp) that select the value-record kernels by hand: 3 the general pattern kernel, 4 the round-2 kernels by
 # size, 5 their two-rows-per-lane form, 6 the dominant-pattern kernels in plain form (contiguous chunks; fused dots two rows per lane),
 # 7 the default (tiles where the pattern has a stride that 128 divides; fused dots four rows per lane)
 VARIANT_OF_FORM = {3: 0x2000, 4: 0x20000000, 5: 0x20004000, 6: 0x10000000, 7: 0, 8: 0x4000}     # 8: the dominant-pattern product with the row blocks' partial sums (dot4)
