@@ -210,6 +210,10 @@ typedef LIS_INT      LIS_Comm;         /* ref:485 */
 #define LIS_MATRIX_RCO 255
 #define LIS_MATRIX_DECIDING_SIZE (-(LIS_MATRIX_RCO+1))
 #define LIS_MATRIX_NULL          (-(LIS_MATRIX_RCO+2))
+#define LIS_MATRIX_LOWER 0
+#define LIS_MATRIX_UPPER 1
+#define LIS_MATRIX_SSOR 2
+
 #define LIS_MATRIX_DEFAULT LIS_MATRIX_CSR
 #define LIS_MATRIX_POINT   LIS_MATRIX_CSR
 #define LIS_MATRIX_BLOCK   LIS_MATRIX_BSR
@@ -504,6 +508,10 @@ LIS_INT lis_matrix_convert(LIS_MATRIX Ain, LIS_MATRIX Aout);
  * reference keeps these two in its internal header (src/matrix lis_matrix.h; lis_matrix_ops.c:860, :1052) */
 LIS_INT lis_matrix_split(LIS_MATRIX A);
 LIS_INT lis_matrix_merge(LIS_MATRIX A);
+/* triangular solves on a split CSR matrix with A->WD (internal header of the reference: lis_matrix.h:82-83; flags below) --
+ * what -p ssor's psolve / psolveh run (lis_precon_ssor.c) */
+LIS_INT lis_matrix_solve(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT flag);
+LIS_INT lis_matrix_solveh(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT flag);
 LIS_INT lis_matrix_copy(LIS_MATRIX Ain, LIS_MATRIX Aout);
 LIS_INT lis_matrix_set_blocksize(LIS_MATRIX A, LIS_INT bnr, LIS_INT bnc, LIS_INT row[], LIS_INT col[]);
 LIS_INT lis_matrix_unset(LIS_MATRIX A);

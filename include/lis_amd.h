@@ -88,6 +88,14 @@ LIS_INT lis_amd_last_solve_uniform_jacobi(void);
 LIS_INT lis_amd_set_graphs(LIS_INT on);
 LIS_INT lis_amd_last_solve_graph_replays(void);        /* batches of the last lis_solve that ran as a graph replay */
 LIS_INT lis_amd_last_solve_renumbered(void);           /* 1: the last lis_solve ran in the numbering of a reordered plan (b, x0 gathered once, x scattered back; lis_amd_matrix_reordered) */
+/* 1 when the last lis_solve ran -p ssor (else 0, and 0 in every field): its row blocks (1, or T of lis_amd_set_reference_reductions(T)),
+ * the levels of its forward and backward sweeps, and the kernel launches of one psolve (runs of small levels share one launch) */
+LIS_INT lis_amd_last_solve_ssor(LIS_INT *blocks, LIS_INT *levels_fwd, LIS_INT *levels_bwd, LIS_INT *launches_per_psolve);
+/* SSOR schedule of a split CSR matrix with WD at the current block count: info = {host seconds spent building schedules for A,
+ * bytes one psolve streams (level-ordered layout), launches per psolve, forward levels} (tools/ssor_probe.py) */
+LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4]);
+/* reps psolves X = M^-1 B, each timed by device events into ms[k] (tools/ssor_probe.py) */
+LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms);
 
 /* vectors */
 LIS_INT lis_amd_vector_sync_host(LIS_VECTOR v);        /* make v->value[] current (D2H if needed)        */

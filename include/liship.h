@@ -541,6 +541,25 @@ int  liship_poisson3d_csr(int l, int m, int n, int is, int ie, int sorted,
 /* b = A*1 for those rows without forming A (test/test3.c:150): 6 minus the number of neighbours */
 int  liship_poisson3d_rhs(int l, int m, int n, int is, int ie, double *b, void *stream);
 
+/* ------------------------------------------------------------------ level-scheduled triangular sweeps (kernels/sptrsv.hip, SSOR)
+ * One sweep: nlev levels, the rows of level l are rows[lptr[l] .. lptr[l+1]) (short rows first, those of LISHIP_SWEEP_LONG_ROW or more
+ * terms from llong[l] on), row r's terms col/val[rptr[r] .. rptr[r+1]) in the order they are added.  groups[3g .. 3g+2] = {l0, l1, run}:
+ * run = 1: levels [l0, l1) in one single-workgroup launch (each at most LISHIP_SWEEP_SMALL_LEVEL rows), run = 0: level l0 on its own.
+ * lptr .. val live in HBM; groups, h_nrows, h_nshort (per level: rows, rows shorter than LISHIP_SWEEP_LONG_ROW) on the host. */
+#define LISHIP_SWEEP_MUL  0     /* x[i] = (b[i] - sum v x[j]) * wd[i] */
+#define LISHIP_SWEEP_SUB  1     /* x[i] -= (0.0 + sum v x[j]) * wd[i] */
+#define LISHIP_SWEEP_SCAT 2     /* x[i] = b[i] - sum v (x[j] * wd[j]) */
+#define LISHIP_SWEEP_SMALL_LEVEL 1024
+#define LISHIP_SWEEP_LONG_ROW 64
+typedef struct {
+	int nlev, nrows, nnz, ngroups;
+	const int *lptr, *llong, *rows, *rptr, *col;
+	const double *val;
+	const int *groups, *h_nrows, *h_nshort;
+} liship_sweep_t;
+/* every row of the sweep, level after level, on `stream`; b may equal x (unused by SUB) */
+int  liship_sweep_f64(const liship_sweep_t *sweep, int mode, const double *b, double *x, const double *wd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

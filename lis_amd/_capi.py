@@ -20,6 +20,7 @@ LIS_INS_VALUE, LIS_ADD_VALUE = 0, 1
 LIS_SUCCESS, LIS_ERR_ILL_ARG, LIS_BREAKDOWN, LIS_ERR_OUT_OF_MEMORY = 0, 1, 2, 3
 LIS_MAXITER, LIS_ERR_NOT_IMPLEMENTED = 4, 5
 LIS_COMM_WORLD = 1
+LIS_MATRIX_LOWER, LIS_MATRIX_UPPER, LIS_MATRIX_SSOR = 0, 1, 2
 FORMAT_ID = {"csr": 1, "csc": 2, "dia": 4, "ell": 5, "jad": 6, "bsr": 7}
 
 
@@ -161,6 +162,8 @@ _PROTOS = {
     "lis_matrix_convert": (LIS_INT, [PM, PM]),
     "lis_matrix_split": (LIS_INT, [PM]),
     "lis_matrix_merge": (LIS_INT, [PM]),
+    "lis_matrix_solve": (LIS_INT, [PM, PV, PV, LIS_INT]),
+    "lis_matrix_solveh": (LIS_INT, [PM, PV, PV, LIS_INT]),
     "lis_matrix_copy": (LIS_INT, [PM, PM]),
     "lis_matrix_set_blocksize": (LIS_INT, [PM, LIS_INT, LIS_INT, P_INT, P_INT]),
     "lis_matrix_malloc_csr": (LIS_INT, [LIS_INT, LIS_INT, C.POINTER(P_INT), C.POINTER(P_INT), C.POINTER(P_DBL)]),

@@ -96,6 +96,7 @@ typedef struct {
 	int *u_ptr, *u_index;
 	double *u_value, *dsplit, *jw;
 	liship_csr_plan_t u_plan;
+	void *ssor;                /* SSOR schedules of the split parts + WD in HBM (lis_ssor.c), dropped with the copy */
 } lisd_mat;
 
 typedef struct {
@@ -151,6 +152,7 @@ typedef struct {
 	int matrix_check;          /* LIS_AMD_MATRIX_CHECK=1 / lis_amd_set_matrix_check(1): every use of a matrix re-hashes its host arrays and rebuilds a stale HBM copy (debugging aid for caller-malloc'ed arrays) */
 	int no_direct_halo;        /* LIS_AMD_NO_DIRECT_HALO=1: boundary rows that form a run are packed like any other list instead of being sent straight from x (A/B) */
 	lis_amd_comm_callbacks cb;
+	int last_ssor, last_ssor_blocks, last_ssor_levels_fwd, last_ssor_levels_bwd, last_ssor_launches;   /* lis_amd_last_solve_ssor */
 } lisi_globals;
 extern lisi_globals lisg;
 
@@ -240,6 +242,13 @@ void    lisi_matrix_dlu_destroy(LIS_MATRIX A);
 LIS_INT lisi_split_rows(LIS_MATRIX A, LIS_INT *rows, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val, int *from_zero);
 LIS_INT lisi_matrix_bscale_bsr(LIS_MATRIX A, LIS_VECTOR B);                  /* -scale jacobi -storage bsr (lis_scale.c) */
 LIS_INT lisi_split_jad_part(LIS_MATRIX A, int upper, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val);
+/* ---- SSOR (lis_ssor.c) */
+LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon);             /* -storage csr, split, WD = 1 / (omega D) unless already built */
+void    lisi_ssor_wd_free(LIS_MATRIX A);
+void    lisd_ssor_free(void *ssor);                                          /* (lisd_mat_free) */
+LIS_INT lisd_ssor_begin(LIS_MATRIX A, int *T);                              /* schedules + WD in HBM for a solve; *T = its block count */
+LIS_INT lisd_ssor_psolve(LIS_MATRIX A, int T, const double *b, double *x);  /* x = M^-1 b  (b may be x) */
+LIS_INT lisd_ssor_psolveh(LIS_MATRIX A, int T, const double *b, double *x); /* x = M^-H b  (b may be x) */
 #define LISI_CHECK_NULL 0
 #define LISI_CHECK_SIZE 1
 #define LISI_CHECK_ASSEMBLED 2

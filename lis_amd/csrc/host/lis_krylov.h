@@ -17,6 +17,7 @@ typedef struct {
 	double *b, *x;           /* HBM */
 	double *dinv;            /* Jacobi 1/diag in HBM, NULL for none */
 	int duniform; double dconst;   /* every dinv[i] is the double dconst (a constant diagonal): the fused CG passes take the scalar */
+	int ssor, ssor_T;        /* SSOR preconditioner (lis_ssor.c) with ssor_T row blocks: only the loops that call d_psolve / d_psolveh */
 	double **work; int nwork;
 	double bnrm, tol;
 	int output, maxiter;
@@ -41,9 +42,15 @@ static inline void work_free(ctx_t *c)
 #define K(call) HIPCHK(call)
 static inline LIS_INT d_copy(ctx_t *c, const double *src, double *dst) { K(liship_memcpy_d2d(dst, src, sizeof(double) * (size_t)c->n, lisg.stream)); return LIS_SUCCESS; }
 static inline LIS_INT d_psolve(ctx_t *c, const double *r, double *z)
-{	/* none: copy (lis_precon.c:365-384); Jacobi: z = r .* dinv (lis_precon_jacobi.c:121-124) */
+{	/* none: copy (lis_precon.c:365-384); Jacobi: z = r .* dinv (lis_precon_jacobi.c:121-124); SSOR: the two sweeps (lis_precon_ssor.c:99-116) */
+	if (c->ssor) return lisd_ssor_psolve(c->A, c->ssor_T, r, z);
 	if (c->dinv) { K(liship_pmul_f64(c->n, r, c->dinv, z, lisg.stream)); return LIS_SUCCESS; }
 	return d_copy(c, r, z);
+}
+static inline LIS_INT d_psolveh(ctx_t *c, const double *r, double *z)
+{	/* M^-H (lis_psolveh): M^-1 itself for none / Jacobi; SSOR: the transposed sweeps (lis_precon_ssor.c:119-136) */
+	if (c->ssor) return lisd_ssor_psolveh(c->A, c->ssor_T, r, z);
+	return d_psolve(c, r, z);
 }
 static inline LIS_INT d_matvec(ctx_t *c, double *x, double *y) { return lisd_spmv(c->A, x, y); }
 static inline LIS_INT d_resid(ctx_t *c, const double *r, double *nrm)

@@ -220,13 +220,13 @@ LIS_INT lis_solver_set_optionC(LIS_SOLVER solver)
 	return set_from_tokens(lisi_cmd_argv, lisi_cmd_argc, solver);
 }
 
-/* ------------------------------------------------------------------ preconditioner (none, Jacobi) */
+/* ------------------------------------------------------------------ preconditioner (none, Jacobi, SSOR) */
 LIS_INT lis_precon_create(LIS_SOLVER solver, LIS_PRECON *precon)
 {
 	const LIS_INT type = solver->options[LIS_OPTIONS_PRECON];
 	*precon = NULL;
-	if (type != LIS_PRECON_TYPE_NONE && type != LIS_PRECON_TYPE_JACOBI)
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi)\n", type);
+	if (type != LIS_PRECON_TYPE_NONE && type != LIS_PRECON_TYPE_JACOBI && type != LIS_PRECON_TYPE_SSOR)
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ssor)\n", type);
 	LIS_PRECON p = (LIS_PRECON)calloc(1, sizeof(struct LIS_PRECON_STRUCT));
 	if (!p) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(struct LIS_PRECON_STRUCT));
 	p->precon_type = type;
@@ -235,6 +235,10 @@ LIS_INT lis_precon_create(LIS_SOLVER solver, LIS_PRECON *precon)
 		LIS_INT err = lis_vector_duplicate(solver->A, &p->D);
 		if (!err) err = lis_matrix_get_diagonal(solver->A, p->D);
 		if (!err) err = lis_vector_reciprocal(p->D);
+		if (err) { lis_precon_destroy(p); return err; }
+	}
+	if (type == LIS_PRECON_TYPE_SSOR) {        /* split A, WD: lis_ssor.c (A stays split: lis_solve never merges it) */
+		LIS_INT err = lisi_ssor_create(solver, p);
 		if (err) { lis_precon_destroy(p); return err; }
 	}
 	*precon = p;
@@ -529,7 +533,7 @@ static LIS_INT run_cg_unfused(ctx_t *c);
 static LIS_INT run_cg_device(ctx_t *c);
 static LIS_INT run_cg(ctx_t *c)
 {
-	if (lisg.no_fusion) return run_cg_unfused(c);
+	if (lisg.no_fusion || c->ssor) return run_cg_unfused(c);
 	if (device_scalars_ok(c)) return run_cg_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -614,7 +618,7 @@ static LIS_INT run_bicgstab_unfused(ctx_t *c);
 static LIS_INT run_bicgstab_device(ctx_t *c);
 static LIS_INT run_bicgstab(ctx_t *c)
 {
-	if (lisg.no_fusion) return run_bicgstab_unfused(c);
+	if (lisg.no_fusion || c->ssor) return run_bicgstab_unfused(c);
 	if (device_scalars_ok(c)) return run_bicgstab_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -728,8 +732,10 @@ done:
  *   x += alpha p ; r -= alpha q ; ||r||                    one pass
  *   r~ -= alpha q~ ; rho' = <r~, M^-1 r>                   one pass (rho' is :187 of the next iteration) */
 static LIS_INT run_bicg_device(ctx_t *c);
+static LIS_INT run_bicg_unfused(ctx_t *c);
 static LIS_INT run_bicg(ctx_t *c)
 {
+	if (c->ssor) return run_bicg_unfused(c);
 	if (!lisg.no_fusion && device_scalars_ok(c)) return run_bicg_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -768,6 +774,48 @@ static LIS_INT run_bicg(ctx_t *c)
 		TRY(lisd_fetch(2, sums));
 		rho_old = rho;
 		rho = sums[1];
+	}
+	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
+done:
+	work_free(c);
+	return err;
+}
+
+/* BiCG one call per reference statement (lis_solver_bicg.c:186-271): the form a preconditioner that is no diagonal needs, M^-H r~ by d_psolveh */
+static LIS_INT run_bicg_unfused(ctx_t *c)
+{
+	LIS_SOLVER s = c->s;
+	LIS_INT err = 0, iter;
+	const int n = c->n;
+	TRY(work_alloc(c, 6));
+	double *r = c->work[0], *rtld = c->work[1], *z = c->work[2], *ztld = c->work[3], *p = c->work[4], *ptld = c->work[5];
+	double *q = z, *qtld = ztld;                       /* aliases as in the reference (:167-168) */
+	double alpha, beta, rho, rho_old = 1.0, d1, nrm2 = 0.0;
+	int st = initial_residual(c, r);
+	if (st) { err = st < 0 ? -st : 0; goto done; }
+	TRY(d_copy(c, r, rtld));                           /* shadow residual = r0 (lis_solver.c:1862) */
+	KTRY(liship_set_all_f64(n, 0.0, p, lisg.stream));
+	KTRY(liship_set_all_f64(n, 0.0, ptld, lisg.stream));
+	for (iter = 1; iter <= c->maxiter; iter++) {
+		TRY(d_psolve(c, r, z));
+		TRY(d_psolveh(c, rtld, ztld));
+		TRY(lisd_dot(n, rtld, z, &rho));
+		if (rho == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		beta = rho / rho_old;
+		KTRY(liship_xpay_f64(n, z, beta, p, lisg.stream));
+		TRY(d_matvec(c, p, q));
+		KTRY(liship_xpay_f64(n, ztld, beta, ptld, lisg.stream));
+		TRY(lisd_spmv_t(c->A, ptld, qtld));
+		TRY(lisd_dot(n, ptld, q, &d1));
+		if (d1 == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		alpha = rho / d1;
+		KTRY(liship_axpy_f64(n, alpha, p, c->x, lisg.stream));
+		KTRY(liship_axpy_f64(n, -alpha, q, r, lisg.stream));
+		TRY(d_resid(c, r, &nrm2));
+		note(c, iter, nrm2);
+		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
+		KTRY(liship_axpy_f64(n, -alpha, qtld, rtld, lisg.stream));
+		rho_old = rho;
 	}
 	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
 done:
@@ -874,7 +922,7 @@ static LIS_INT run_gmres(ctx_t *c)
 			double *hc = h + (size_t)ii * ld;
 			/* M^-1 v: without a preconditioner the reference copies (lis_precon.c:365-384); the product reads v itself */
 			double *zin = z;
-			if (c->dinv || lisg.no_fusion) TRY(d_psolve(c, v[ii], z)); else zin = v[ii];
+			if (c->dinv || c->ssor || lisg.no_fusion) TRY(d_psolve(c, v[ii], z)); else zin = v[ii];
 			if (!chained) TRY(d_matvec(c, zin, v[i1]));
 			if (chained) {
 				/* modified Gram-Schmidt with the coefficients kept in HBM: step k reads h[k-1] from the previous
@@ -943,7 +991,7 @@ static LIS_INT run_gmres(ctx_t *c)
 			KTRY(liship_scale_to_f64(n, g[0], v[0], z, lisg.stream));     /* z = y0 v0  (:290-296) */
 			for (int j = 1; j <= ii; j++) KTRY(liship_axpy_f64(n, g[j], v[j], z, lisg.stream));
 		}
-		if (c->dinv || lisg.no_fusion) {
+		if (c->dinv || c->ssor || lisg.no_fusion) {
 			TRY(d_psolve(c, z, r));
 			KTRY(liship_axpy_f64(n, 1.0, r, c->x, lisg.stream));
 		} else KTRY(liship_axpy_f64(n, 1.0, z, c->x, lisg.stream));      /* the copy of psolve_none left out: same addend */
@@ -1007,6 +1055,8 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	LIS_INT err = 0;
 	ctx_t c;
 	memset(&c, 0, sizeof(c));
+	/* SSOR depends on the numbering (its sweeps follow the rows' order): such a solve never runs renumbered, nor builds the renumbered form */
+	const int ssor = precon && precon->precon_type == LIS_PRECON_TYPE_SSOR;
 	int renumbered = 0;                        /* the solve runs in the numbering of a reordered plan (below) */
 	const int *renum = NULL;
 	double *renum_b = NULL, *renum_d = NULL;
@@ -1122,8 +1172,8 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 		const int t_ok = !needs_t || (Awork->matrix_type == LIS_MATRIX_CSR && !Awork->is_splited);
 		const int multi = lisg.nprocs > 1 && Awork->commtable;
 		/* the renumbered form is built LAZILY: by the first solve that finds the plan has served lisg.reorder_after products (lis_device.c) */
-		if (!scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok) { if ((err = lisd_mat_lazy_reorder(Awork))) goto out; }
-		if (!scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok && dm->type == LIS_MATRIX_CSR && !dm->split_jad &&
+		if (!ssor && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok) { if ((err = lisd_mat_lazy_reorder(Awork))) goto out; }
+		if (!ssor && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok && dm->type == LIS_MATRIX_CSR && !dm->split_jad &&
 		    dm->plan && (Awork->np == Awork->n || (multi && Awork->matrix_type == LIS_MATRIX_CSR)) && dm->n == Awork->n && liship_csr_plan_reordered_form(dm->plan, &in, &rp, &ri, &rv, &renum) == 0) {
 			if (multi && (err = lisc_halo_renumbered(Awork, renum, liship_csr_plan_reordered_inner_rows(dm->plan)))) goto out;
 			held_plan = dm->plan; held_ptr = dm->ptr; held_index = dm->index; held_value = dm->value;
@@ -1155,6 +1205,11 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	lisg.last_uniform_jacobi = 0;
 	lisg.last_graph_replays = 0;
 	lisg.last_renumbered = renumbered;
+	lisg.last_ssor = 0;
+	if (ssor) {
+		c.ssor = 1;
+		if ((err = lisd_ssor_begin(Awork, &c.ssor_T))) goto out;
+	}
 	if (precon && precon->precon_type == LIS_PRECON_TYPE_JACOBI) {
 		if ((err = lisd_vec_in(precon->D, &c.dinv))) goto out;
 		if (renumbered) {

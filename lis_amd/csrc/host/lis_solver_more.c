@@ -26,6 +26,7 @@
 #define DOT(x, y, out)     TRY(lisd_dot(n, (x), (y), (out)))
 #define MATVEC(x, y)       TRY(d_matvec(c, (x), (y)))
 #define PSOLVE(r, z)       TRY(d_psolve(c, (r), (z)))
+#define PSOLVEH(r, z)      TRY(d_psolveh(c, (r), (z)))
 #define RESID(r, out)      TRY(d_resid(c, (r), (out)))
 #define FINISH(code) do { s->retcode = (code); s->iter = iter; s->resid = nrm2; err = ((code) == LIS_SUCCESS) ? 0 : (code); goto done; } while (0)
 
@@ -366,7 +367,7 @@ LIS_INT lisk_bicr(ctx_t *c)
 	if (st) { err = st < 0 ? -st : 0; goto done; }
 	COPY(r, rtld);
 	PSOLVE(r, z);
-	PSOLVE(rtld, ztld);                           /* M^-H = M^-1 for none / Jacobi */
+	PSOLVEH(rtld, ztld);                          /* M^-H: M^-1 for none / Jacobi, the transposed sweeps for SSOR */
 	COPY(z, p);
 	COPY(ztld, ptld);
 	MATVEC(z, ap);
@@ -384,7 +385,7 @@ LIS_INT lisk_bicr(ctx_t *c)
 		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
 		AXPY(-alpha, aptld, rtld);
 		AXPY(-alpha, map, z);
-		PSOLVE(rtld, ztld);
+		PSOLVEH(rtld, ztld);
 		MATVEC(z, az);
 		DOT(ztld, az, &rho);
 		if (rho == 0.0) FINISH(LIS_BREAKDOWN);
@@ -997,7 +998,7 @@ LIS_INT lisk_jacobi(ctx_t *c)
 	const double tol = s->params[LIS_PARAMS_RESID - LIS_OPTIONS_LEN];
 	double nrm2 = 0.0, bnrm2;
 	lisd_mat *dm = MDEV(c->A);
-	if (c->dinv) { err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver with a preconditioner (system rescaling) is not served by liblis_amd\n"); goto done; }
+	if (c->dinv || c->ssor) { err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver with a preconditioner (system rescaling) is not served by liblis_amd\n"); goto done; }
 	if (dm->type != LIS_MATRIX_CSR) { err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver is served for CSR / CSC storage only\n"); goto done; }
 	TRY(work_alloc(c, 4));
 	double *r = c->work[0], *t = c->work[1], *sx = c->work[2], *d = c->work[3];
