@@ -94,6 +94,10 @@ LIS_INT lis_amd_last_solve_ssor(LIS_INT *blocks, LIS_INT *levels_fwd, LIS_INT *l
 /* SSOR schedule of a split CSR matrix with WD at the current block count: info = {host seconds spent building schedules for A,
  * bytes one psolve streams (level-ordered layout), launches per psolve, forward levels} (tools/ssor_probe.py) */
 LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4]);
+/* One sweep of that schedule, read-only: sweep = 0 forward on L, 1 backward on U, 2 forward on U^T, 3 backward on L^T (the two of
+ * lis_matrix_solveh); info = {levels, launches, levels on a launch of their own (more than LISHIP_SWEEP_SMALL_LEVEL rows), long rows
+ * (LISHIP_SWEEP_LONG_ROW terms or more) in those levels, long rows in runs of small levels, terms} (tests/test_ssor_schedule_gpu.py) */
+LIS_INT lis_amd_ssor_sweep_info(LIS_MATRIX A, LIS_INT sweep, LIS_INT info[6]);
 /* reps psolves X = M^-1 B, each timed by device events into ms[k] (tools/ssor_probe.py) */
 LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms);
 

@@ -377,6 +377,25 @@ LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4])
 	return LIS_SUCCESS;
 }
 
+LIS_INT lis_amd_ssor_sweep_info(LIS_MATRIX A, LIS_INT sweep, LIS_INT info[6])
+{	/* one of the four sweeps (0 forward on L, 1 backward on U, 2 forward on U^T, 3 backward on L^T) at the solves' T, read-only:
+	 * {levels, launches, levels on a launch of their own, long rows in those levels, long rows in runs, terms} */
+	LISCHK(check_split(A));
+	if (sweep < 0 || sweep >= SW_COUNT || !info) return LISI_ERR(LIS_ERR_ILL_ARG, "sweep %D is not 0 .. 3, or info is NULL\n", sweep);
+	LISCHK(lisd_mat_ready(A));
+	const liship_sweep_t *s;
+	LISCHK(get_sweep(A, blocks(), (int)sweep, &s));
+	LIS_INT own = 0, long_own = 0, long_run = 0;
+	for (int g = 0; g < s->ngroups; g++)
+		for (int l = s->groups[3 * g]; l < s->groups[3 * g + 1]; l++) {
+			const int nlong = s->h_nrows[l] - s->h_nshort[l];
+			if (s->groups[3 * g + 2]) long_run += nlong;
+			else { own++; long_own += nlong; }
+		}
+	info[0] = s->nlev; info[1] = s->ngroups; info[2] = own; info[3] = long_own; info[4] = long_run; info[5] = s->nnz;
+	return LIS_SUCCESS;
+}
+
 LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms)
 {	/* reps psolves X = M^-1 B on the library's stream, each timed by device events (ms[k]) */
 	LISCHK(check_split(A));
