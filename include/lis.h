@@ -6,9 +6,9 @@
  * include/lis.h; the line each item mirrors is cited as "ref:NNN").  A program written against the
  * reference header compiles against this one and links against liblis_amd.so instead of liblis.
  * Only the slice on the hot path and the rows next to it are provided (six storage
- * formats, A x and A^T x, the Krylov solvers, none/Jacobi preconditioning, scaling, Matrix Market / Harwell-Boeing
+ * formats, A x and A^T x, the Krylov solvers, none / Jacobi / SSOR / ILU(k) preconditioning, scaling, Matrix Market / Harwell-Boeing
  * files); anything else is absent, and what exists in the enumerations but is not served (MSR/BSC/VBR/COO/DNS
- * storage, Gauss-Seidel / SOR, the ILU-family preconditioners) returns LIS_ERR_NOT_IMPLEMENTED at run time
+ * storage, Gauss-Seidel / SOR, the preconditioners after ILU(k) and SSOR: iluc, ilut, ...) returns LIS_ERR_NOT_IMPLEMENTED at run time
  * exactly where the reference would dispatch to it.
  *
  * Default build of the reference is assumed: LIS_INT = int (ref:461), LIS_SCALAR = LIS_REAL = double

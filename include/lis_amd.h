@@ -100,6 +100,29 @@ LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4]);
 LIS_INT lis_amd_ssor_sweep_info(LIS_MATRIX A, LIS_INT sweep, LIS_INT info[6]);
 /* reps psolves X = M^-1 B, each timed by device events into ms[k] (tools/ssor_probe.py) */
 LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms);
+/* ---- ILU(k) (-p ilu -ilu_fill k; A in CSR storage, not split, one rank).  All of these work at the current block count: 1, or T of
+ * lis_amd_set_reference_reductions(T) (the reference at T threads factorises T row blocks on their own). */
+/* 1 when the last lis_solve ran -p ilu (else 0, and 0 in every field; lis_amd_last_solve_ssor answers 0 then, and the other way
+ * round): its fill level, row blocks, forward levels (= the levels of the factorisation) and the kernel launches of one psolve */
+LIS_INT lis_amd_last_solve_ilu(LIS_INT *fill, LIS_INT *blocks, LIS_INT *levels, LIS_INT *launches_per_psolve);
+/* factorise A at fill level `fill` in HBM (pattern and schedule are cached on A's HBM copy, the numbers are made anew);
+ * sizes = {n, nnz(L), nnz(U)}, the room lis_amd_ilu_copy needs */
+LIS_INT lis_amd_ilu_factor(LIS_MATRIX A, LIS_INT fill, LIS_INT sizes[3]);
+/* the factor as it stands (factorised now if it never was): L and U as CSR arrays in the pattern's term order (lptr / uptr: n + 1
+ * entries; row i of L ascending, of U in A's stored order followed by fill-in as found), d[i] = 1 / pivot.  Any pointer may be NULL. */
+LIS_INT lis_amd_ilu_copy(LIS_MATRIX A, LIS_INT fill, LIS_INT *lptr, LIS_INT *lindex, LIS_SCALAR *lvalue,
+                         LIS_INT *uptr, LIS_INT *uindex, LIS_SCALAR *uvalue, LIS_SCALAR *d);
+/* X = M^-1 B (transposed = 0) or M^-H B (transposed != 0) with that factor; X may be B */
+LIS_INT lis_amd_ilu_psolve(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR X, LIS_INT transposed);
+/* reps factorisations, then reps psolves X = M^-1 B, each timed by device events into factor_ms[k] / psolve_ms[k] (tools/ilu_probe.py) */
+LIS_INT lis_amd_ilu_times(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *factor_ms, double *psolve_ms);
+/* info = {host seconds of the symbolic step and the layouts, nnz(L) + nnz(U), forward levels, launches of one factorisation (one per
+ * large level or run of small levels, plus the gathers into the L and U layouts; BiCG-type solvers, which also call M^-H, pay two more), launches per psolve, bytes one psolve streams} */
+LIS_INT lis_amd_ilu_info(LIS_MATRIX A, LIS_INT fill, double info[6]);
+/* the factorisation's schedule, read-only: info = {levels, level launches, levels on a launch of their own (more than
+ * LISHIP_SWEEP_SMALL_LEVEL rows), rows factorised by a workgroup (L + U terms >= LISHIP_SWEEP_LONG_ROW) in those levels, such rows in
+ * runs of small levels, 1 when a row of A stores a column twice and such rows are factorised by one thread} (tests/test_ilu_gpu.py) */
+LIS_INT lis_amd_ilu_factor_info(LIS_MATRIX A, LIS_INT fill, LIS_INT info[6]);
 
 /* vectors */
 LIS_INT lis_amd_vector_sync_host(LIS_VECTOR v);        /* make v->value[] current (D2H if needed)        */

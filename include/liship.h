@@ -541,7 +541,7 @@ int  liship_poisson3d_csr(int l, int m, int n, int is, int ie, int sorted,
 /* b = A*1 for those rows without forming A (test/test3.c:150): 6 minus the number of neighbours */
 int  liship_poisson3d_rhs(int l, int m, int n, int is, int ie, double *b, void *stream);
 
-/* ------------------------------------------------------------------ level-scheduled triangular sweeps (kernels/sptrsv.hip, SSOR)
+/* ------------------------------------------------------------------ level-scheduled triangular sweeps (kernels/sptrsv.hip, SSOR and ILU)
  * One sweep: nlev levels, the rows of level l are rows[lptr[l] .. lptr[l+1]) (short rows first, those of LISHIP_SWEEP_LONG_ROW or more
  * terms from llong[l] on), row r's terms col/val[rptr[r] .. rptr[r+1]) in the order they are added.  groups[3g .. 3g+2] = {l0, l1, run}:
  * run = 1: levels [l0, l1) in one single-workgroup launch (each at most LISHIP_SWEEP_SMALL_LEVEL rows), run = 0: level l0 on its own.
@@ -549,6 +549,7 @@ int  liship_poisson3d_rhs(int l, int m, int n, int is, int ie, double *b, void *
 #define LISHIP_SWEEP_MUL  0     /* x[i] = (b[i] - sum v x[j]) * wd[i] */
 #define LISHIP_SWEEP_SUB  1     /* x[i] -= (0.0 + sum v x[j]) * wd[i] */
 #define LISHIP_SWEEP_SCAT 2     /* x[i] = b[i] - sum v (x[j] * wd[j]) */
+#define LISHIP_SWEEP_PLAIN 3    /* x[i] = b[i] - sum v x[j]: liship_sweep_plain_f64 only (liship_sweep_f64 takes 0 .. 2) */
 #define LISHIP_SWEEP_SMALL_LEVEL 1024
 #define LISHIP_SWEEP_LONG_ROW 64
 typedef struct {
@@ -559,6 +560,27 @@ typedef struct {
 } liship_sweep_t;
 /* every row of the sweep, level after level, on `stream`; b may equal x (unused by SUB) */
 int  liship_sweep_f64(const liship_sweep_t *sweep, int mode, const double *b, double *x, const double *wd, void *stream);
+/* the same rows without a diagonal: x[i] = b[i] - sum v x[j]; b may equal x (ILU: forward on L, backward on L^T) */
+int  liship_sweep_plain_f64(const liship_sweep_t *sweep, const double *b, double *x, void *stream);
+
+/* ------------------------------------------------------------------ ILU(k) numerical factorisation (kernels/ilu.hip)
+ * A = (aptr, aindex, avalue) as it lies in HBM.  The symbolic pattern: row i of L = lcol[lptr[i] .. lptr[i+1]) ascending (a column
+ * held twice: twice, side by side), of U = ucol[uptr[i] .. uptr[i+1]) in term order.  To find the place of a column in row i of U:
+ * uskey = the row's columns ascending (ties by position), uspos = where each of them lies in ucol / uval; uspos NULL: the rows of
+ * U are ascending as they are and uskey is ucol.  Of a column held twice the later place takes A's value and the updates.
+ * Output in the pattern's order: lval, uval, d[i] = 1 / pivot (no pivot check: 1 / 0 = inf goes on).
+ * `schedule`: the rows by forward level (lptr, llong, rows, groups, h_nrows, h_nshort; its col / val are not read) -- the rows from
+ * llong[l] on are factorised by a workgroup each, the updates of ONE pivot spread over its threads, pivots in order; the others by
+ * a thread each.  serial != 0 (some row of A holds a column twice, so one pivot may update a target twice): such rows are
+ * factorised by one thread of their workgroup.  Every update is one rounded product and one rounded subtraction, in pivot order. */
+typedef struct {
+	int n, serial;
+	const int *aptr, *aindex;
+	const double *avalue;
+	const int *lptr, *lcol, *uptr, *ucol, *uskey, *uspos;
+	double *lval, *uval, *d;
+} liship_ilu_t;
+int  liship_ilu_factor_f64(const liship_ilu_t *ilu, const liship_sweep_t *schedule, void *stream);
 
 #ifdef __cplusplus
 }

@@ -215,6 +215,18 @@ _PROTOS = {
 }
 
 
+# the ILU(k) extensions of include/lis_amd.h: set where the library has them (liblis_amd.so), absent from the reference build
+_AMD_PROTOS = {
+    "lis_amd_last_solve_ilu": (LIS_INT, [P_INT, P_INT, P_INT, P_INT]),
+    "lis_amd_ilu_factor": (LIS_INT, [PM, LIS_INT, P_INT]),
+    "lis_amd_ilu_copy": (LIS_INT, [PM, LIS_INT, P_INT, P_INT, P_DBL, P_INT, P_INT, P_DBL, P_DBL]),
+    "lis_amd_ilu_psolve": (LIS_INT, [PM, LIS_INT, PV, PV, LIS_INT]),
+    "lis_amd_ilu_times": (LIS_INT, [PM, LIS_INT, PV, PV, LIS_INT, P_DBL, P_DBL]),
+    "lis_amd_ilu_info": (LIS_INT, [PM, LIS_INT, P_DBL]),
+    "lis_amd_ilu_factor_info": (LIS_INT, [PM, LIS_INT, P_INT]),
+}
+
+
 class LisLib:
     """A loaded library exporting the Lis C API."""
 
@@ -233,6 +245,10 @@ class LisLib:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+        for name, (res, args) in _AMD_PROTOS.items():
+            fn = getattr(self.dll, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
 
     def initialize(self, args=()):
         argv_list = [b"lis"] + [a.encode() if isinstance(a, str) else a for a in args]

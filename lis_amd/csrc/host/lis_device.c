@@ -1035,6 +1035,7 @@ void lisd_mat_free(LIS_MATRIX A)
 	(void)liship_free(d->export_index); (void)liship_free(d->ws); free(d->export_run);
 	(void)liship_free(d->sx); (void)liship_free(d->sy);
 	lisd_ssor_free(d->ssor);
+	lisd_ilu_free(d->ilu);
 	memset(d, 0, sizeof(*d));
 	lisp_matrix_release(A, 0);         /* no copy left that a host write could leave stale: the watched arrays are plain memory again */
 }

@@ -97,6 +97,7 @@ typedef struct {
 	double *u_value, *dsplit, *jw;
 	liship_csr_plan_t u_plan;
 	void *ssor;                /* SSOR schedules of the split parts + WD in HBM (lis_ssor.c), dropped with the copy */
+	void *ilu;                 /* ILU(k): symbolic pattern, schedule, sweep layouts and factor in HBM (lis_ilu.c), dropped with the copy */
 } lisd_mat;
 
 typedef struct {
@@ -152,6 +153,7 @@ typedef struct {
 	int matrix_check;          /* LIS_AMD_MATRIX_CHECK=1 / lis_amd_set_matrix_check(1): every use of a matrix re-hashes its host arrays and rebuilds a stale HBM copy (debugging aid for caller-malloc'ed arrays) */
 	int no_direct_halo;        /* LIS_AMD_NO_DIRECT_HALO=1: boundary rows that form a run are packed like any other list instead of being sent straight from x (A/B) */
 	lis_amd_comm_callbacks cb;
+	int last_ilu, last_ilu_fill, last_ilu_blocks, last_ilu_levels, last_ilu_launches;                  /* lis_amd_last_solve_ilu */
 	int last_ssor, last_ssor_blocks, last_ssor_levels_fwd, last_ssor_levels_bwd, last_ssor_launches;   /* lis_amd_last_solve_ssor */
 } lisi_globals;
 extern lisi_globals lisg;
@@ -242,6 +244,25 @@ void    lisi_matrix_dlu_destroy(LIS_MATRIX A);
 LIS_INT lisi_split_rows(LIS_MATRIX A, LIS_INT *rows, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val, int *from_zero);
 LIS_INT lisi_matrix_bscale_bsr(LIS_MATRIX A, LIS_VECTOR B);                  /* -scale jacobi -storage bsr (lis_scale.c) */
 LIS_INT lisi_split_jad_part(LIS_MATRIX A, int upper, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val);
+/* ---- level-ordered sweep layouts (lis_ssor.c), shared by SSOR and ILU */
+typedef struct {
+	int built;
+	liship_sweep_t k;                          /* what the launcher reads */
+	int *lptr, *llong, *rows, *rptr, *col;     /* HBM */
+	double *val;
+	int *groups, *nrows, *nshort;              /* host */
+	double bytes;                              /* one application: level-ordered streams + b / x / wd per row */
+} lisi_sweep_t;
+enum { SW_L, SW_U, SW_UT, SW_LT, SW_COUNT };   /* the four sweeps of a preconditioner: forward on L, backward on U, forward on U^T, backward on L^T */
+void    lisi_sweep_free(lisi_sweep_t *s);
+int    *lisi_block_of(int n, int T);                                         /* block of every row among T blocks of LIS_GET_ISIE (caller frees) */
+LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out);
+/* ---- ILU(k) (lis_ilu.c) */
+LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon);              /* refusals, symbolic step (cached), factorisation on the device */
+void    lisd_ilu_free(void *ilu);                                            /* (lisd_mat_free) */
+LIS_INT lisd_ilu_begin(LIS_MATRIX A, int fill, int *T);                     /* the factor of A for a solve (made now if the HBM copy was rebuilt since create) */
+LIS_INT lisd_ilu_psolve(LIS_MATRIX A, int fill, int T, const double *b, double *x);   /* x = M^-1 b  (b may be x) */
+LIS_INT lisd_ilu_psolveh(LIS_MATRIX A, int fill, int T, const double *b, double *x);  /* x = M^-H b  (b may be x) */
 /* ---- SSOR (lis_ssor.c) */
 LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon);             /* -storage csr, split, WD = 1 / (omega D) unless already built */
 void    lisi_ssor_wd_free(LIS_MATRIX A);

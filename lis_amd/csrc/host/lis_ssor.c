@@ -19,16 +19,8 @@
 #include <stdio.h>
 #include "lis_krylov.h"
 
-enum { SW_L, SW_U, SW_UT, SW_LT, SW_COUNT };   /* forward on L, backward on U, forward on U^T, backward on L^T */
 
-typedef struct {
-	int built;
-	liship_sweep_t k;                          /* what the launcher reads */
-	int *lptr, *llong, *rows, *rptr, *col;     /* HBM */
-	double *val;
-	int *groups, *nrows, *nshort;              /* host */
-	double bytes;                              /* one application: level-ordered streams + b / x / wd per row */
-} sweep_t;
+typedef lisi_sweep_t sweep_t;              /* lis_internal.h: shared with lis_ilu.c */
 
 typedef struct {
 	int T;                                     /* 0: slot unused */
@@ -43,7 +35,7 @@ typedef struct {
 	double build_s;                            /* host seconds spent building schedules */
 } lisd_ssor;
 
-static void sweep_free(sweep_t *s)
+void lisi_sweep_free(lisi_sweep_t *s)
 {
 	(void)liship_free(s->lptr); (void)liship_free(s->llong); (void)liship_free(s->rows); (void)liship_free(s->rptr);
 	(void)liship_free(s->col); (void)liship_free(s->val);
@@ -55,13 +47,13 @@ void lisd_ssor_free(void *p)
 {
 	lisd_ssor *ss = (lisd_ssor *)p;
 	if (!ss) return;
-	for (int t = 0; t < 2; t++) for (int w = 0; w < SW_COUNT; w++) sweep_free(&ss->s[t].sw[w]);
+	for (int t = 0; t < 2; t++) for (int w = 0; w < SW_COUNT; w++) lisi_sweep_free(&ss->s[t].sw[w]);
 	(void)liship_free(ss->wd);
 	free(ss);
 }
 
 /* block of row i among T blocks of LIS_GET_ISIE (ref include/lis.h:1067): the first n % T blocks hold n / T + 1 rows */
-static int *block_of(int n, int T)
+int *lisi_block_of(int n, int T)
 {
 	int *b = (int *)malloc(sizeof(int) * (size_t)(n > 0 ? n : 1));
 	if (!b) return NULL;
@@ -79,21 +71,25 @@ static LIS_INT up_i(int **dst, const int *src, size_t count)
 static LIS_INT up_d(double **dst, const double *src, size_t count)
 {
 	HIPCHK(lisd_malloc((void **)dst, (count + 2) * sizeof(double)));
-	if (count) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(double), lisg.stream));
+	if (count && src) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(double), lisg.stream));
 	return LIS_SUCCESS;
 }
 
-/* levels + level-ordered layout of n rows whose terms (tp, tc, tv) read only rows before them (desc = 0) or after them (desc = 1) */
-static LIS_INT sweep_build(sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc)
+/* levels + level-ordered layout of n rows whose terms (tp, tc, tv) read only rows before them (desc = 0) or after them (desc = 1).
+ * tv NULL: no values (a schedule only, or values that arrive later on the device); weight: what decides whether row i is a long
+ * row instead of its term count; src_out: for every place of the layout the term (index into tc) that lies there (caller frees) */
+LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out)
 {
 	LIS_INT err = LIS_SUCCESS;
 	const int nnz = tp[n];
 	int *lev = (int *)malloc(sizeof(int) * (size_t)(n + 1));
 	int *rows = (int *)malloc(sizeof(int) * (size_t)(n + 1)), *rptr = (int *)malloc(sizeof(int) * (size_t)(n + 1));
 	int *col = (int *)malloc(sizeof(int) * (size_t)(nnz + 1));
-	double *val = (double *)malloc(sizeof(double) * (size_t)(nnz + 1));
+	double *val = tv ? (double *)malloc(sizeof(double) * (size_t)(nnz + 1)) : NULL;
+	int *src = src_out ? (int *)malloc(sizeof(int) * (size_t)(nnz + 1)) : NULL;
 	int *lptr = NULL, *llong = NULL, *fill_s = NULL, *fill_l = NULL;
-	if (!lev || !rows || !rptr || !col || !val) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)nnz); goto out; }
+#define ROW_WEIGHT(i) (weight ? weight[(i)] : tp[(i) + 1] - tp[(i)])
+	if (!lev || !rows || !rptr || !col || (tv && !val) || (src_out && !src)) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)nnz); goto out; }
 	int nlev = 0;
 	for (int q = 0; q < n; q++) {
 		const int i = desc ? n - 1 - q : q;
@@ -107,17 +103,17 @@ static LIS_INT sweep_build(sweep_t *s, int n, const int *tp, const int *tc, cons
 	fill_s = (int *)calloc((size_t)nlev + 1, sizeof(int)); fill_l = (int *)calloc((size_t)nlev + 1, sizeof(int));
 	s->groups = (int *)malloc(sizeof(int) * 3 * ((size_t)nlev + 1));
 	if (!s->nrows || !s->nshort || !lptr || !llong || !fill_s || !fill_l || !s->groups) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)nlev); goto out; }
-	for (int i = 0; i < n; i++) { s->nrows[lev[i]]++; if (tp[i + 1] - tp[i] < LISHIP_SWEEP_LONG_ROW) s->nshort[lev[i]]++; }
+	for (int i = 0; i < n; i++) { s->nrows[lev[i]]++; if (ROW_WEIGHT(i) < LISHIP_SWEEP_LONG_ROW) s->nshort[lev[i]]++; }
 	for (int l = 0; l < nlev; l++) { lptr[l + 1] = lptr[l] + s->nrows[l]; llong[l] = lptr[l] + s->nshort[l]; fill_s[l] = lptr[l]; fill_l[l] = llong[l]; }
 	for (int i = 0; i < n; i++) {             /* rows by level; inside a level short rows first, each part by ascending row */
 		const int l = lev[i];
-		if (tp[i + 1] - tp[i] < LISHIP_SWEEP_LONG_ROW) rows[fill_s[l]++] = i; else rows[fill_l[l]++] = i;
+		if (ROW_WEIGHT(i) < LISHIP_SWEEP_LONG_ROW) rows[fill_s[l]++] = i; else rows[fill_l[l]++] = i;
 	}
 	rptr[0] = 0;
 	for (int r = 0; r < n; r++) {
 		const int i = rows[r];
 		int at = rptr[r];
-		for (int k = tp[i]; k < tp[i + 1]; k++, at++) { col[at] = tc[k]; val[at] = tv[k]; }
+		for (int k = tp[i]; k < tp[i + 1]; k++, at++) { col[at] = tc[k]; if (val) val[at] = tv[k]; if (src) src[at] = k; }
 		rptr[r + 1] = at;
 	}
 	/* launches: runs of small levels in one workgroup, every large level on its own */
@@ -134,7 +130,7 @@ static LIS_INT sweep_build(sweep_t *s, int n, const int *tp, const int *tc, cons
 		}
 	}
 	if ((err = up_i(&s->lptr, lptr, (size_t)nlev + 1)) || (err = up_i(&s->llong, llong, (size_t)nlev + 1)) || (err = up_i(&s->rows, rows, (size_t)n)) ||
-	    (err = up_i(&s->rptr, rptr, (size_t)n + 1)) || (err = up_i(&s->col, col, (size_t)nnz)) || (err = up_d(&s->val, val, (size_t)nnz))) goto out;
+	    (err = up_i(&s->rptr, rptr, (size_t)n + 1)) || (err = up_i(&s->col, col, (size_t)nnz)) || ((tv || src_out) && (err = up_d(&s->val, val, (size_t)nnz)))) goto out;      /* (values that arrive later: room only) */
 	{	int rc = liship_stream_synchronize(lisg.stream);          /* (the host arrays go below) */
 		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; } }
 	s->k.nlev = nlev; s->k.nrows = n; s->k.nnz = nnz; s->k.ngroups = ng;
@@ -142,9 +138,11 @@ static LIS_INT sweep_build(sweep_t *s, int n, const int *tp, const int *tc, cons
 	s->k.groups = s->groups; s->k.h_nrows = s->nrows; s->k.h_nshort = s->nshort;
 	s->bytes = 4.0 * n + 4.0 * (n + 1) + 12.0 * nnz + 24.0 * n;
 	s->built = 1;
+	if (src_out) { *src_out = src; src = NULL; }
 out:
-	free(lev); free(rows); free(rptr); free(col); free(val); free(lptr); free(llong); free(fill_s); free(fill_l);
-	if (err) sweep_free(s);
+#undef ROW_WEIGHT
+	free(lev); free(rows); free(rptr); free(col); free(val); free(src); free(lptr); free(llong); free(fill_s); free(fill_l);
+	if (err) lisi_sweep_free(s);
 	return err;
 }
 
@@ -153,7 +151,7 @@ static LIS_INT sweep_make(LIS_MATRIX A, int which, int T, sweep_t *s)
 {
 	const int n = A->n;
 	LIS_MATRIX_CORE P = (which == SW_L || which == SW_LT) ? A->L : A->U;
-	int *blk = block_of(n, T);
+	int *blk = lisi_block_of(n, T);
 	int *tp = (int *)calloc((size_t)n + 2, sizeof(int));
 	const int pn = P->ptr[n];
 	int *tc = (int *)malloc(sizeof(int) * (size_t)(pn + 1));
@@ -184,7 +182,7 @@ static LIS_INT sweep_make(LIS_MATRIX A, int which, int T, sweep_t *s)
 		free(fill);
 	}
 #undef KEEP
-	err = sweep_build(s, n, tp, tc, tv, which == SW_U || which == SW_LT);
+	err = lisi_sweep_build(s, n, tp, tc, tv, which == SW_U || which == SW_LT, NULL, NULL);
 out:
 	free(blk); free(tp); free(tc); free(tv);
 	return err;
@@ -211,7 +209,7 @@ static LIS_INT get_sweep(LIS_MATRIX A, int T, int which, const liship_sweep_t **
 	if (!sc) {
 		sc = &ss->s[ss->next];
 		ss->next ^= 1;
-		for (int w = 0; w < SW_COUNT; w++) sweep_free(&sc->sw[w]);
+		for (int w = 0; w < SW_COUNT; w++) lisi_sweep_free(&sc->sw[w]);
 		sc->T = T;
 	}
 	sweep_t *s = &sc->sw[which];

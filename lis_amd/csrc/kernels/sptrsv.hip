@@ -1,4 +1,4 @@
-// sptrsv.hip -- level-scheduled sparse triangular sweeps for the SSOR preconditioner (lis_ssor.c).
+// sptrsv.hip -- level-scheduled sparse triangular sweeps for the SSOR and ILU(k) preconditioners (lis_ssor.c, lis_ilu.c).
 //
 // A sweep is a list of levels; the rows of one level do not depend on each other, every row depends only on rows of earlier
 // levels.  The schedule (lis_ssor.c) stores the rows of each level and their terms contiguously in level order: rows[] the
@@ -10,6 +10,7 @@
 //   MUL   acc = b[i];  acc -= v * x[j] ...;           x[i] = acc * wd[i]     forward SSOR, LOWER / UPPER, the second psolveh sweep
 //   SUB   acc = 0.0;   acc += v * x[j] ...;           x[i] -= acc * wd[i]    backward SSOR
 //   SCAT  acc = b[i];  acc -= v * (x[j] * wd[j]) ...; x[i] = acc             first psolveh sweep (the transposed scatter of t = x[j] * wd[j])
+//   PLAIN acc = b[i];  acc -= v * x[j] ...;           x[i] = acc             ILU: forward on L, backward on L^T (no diagonal, wd unread)
 // A row reads its own b[i] before it writes x[i], and no other row's b: b and x may be the same vector.
 //
 // Dependencies between levels are kernel boundaries on the stream, or __syncthreads() inside the single-workgroup kernel
@@ -139,6 +140,12 @@ int run_sweep(const liship_sweep_t *sw, const double *b, double *x, const double
 }
 
 }  // namespace
+
+extern "C" int liship_sweep_plain_f64(const liship_sweep_t *sw, const double *b, double *x, void *stream)
+{
+    if (!sw || !x || !b) return LISHIP_ERR_ARG;
+    return run_sweep<LISHIP_SWEEP_PLAIN>(sw, b, x, nullptr, as_stream(stream));
+}
 
 extern "C" int liship_sweep_f64(const liship_sweep_t *sw, int mode, const double *b, double *x, const double *wd, void *stream)
 {
