@@ -541,7 +541,7 @@ int  liship_poisson3d_csr(int l, int m, int n, int is, int ie, int sorted,
 /* b = A*1 for those rows without forming A (test/test3.c:150): 6 minus the number of neighbours */
 int  liship_poisson3d_rhs(int l, int m, int n, int is, int ie, double *b, void *stream);
 
-/* ------------------------------------------------------------------ level-scheduled triangular sweeps (kernels/sptrsv.hip, SSOR and ILU)
+/* ------------------------------------------------------------------ level-scheduled triangular sweeps (kernels/sptrsv.hip on kernels/level_schedule.hpp, SSOR and ILU)
  * One sweep: nlev levels, the rows of level l are rows[lptr[l] .. lptr[l+1]) (short rows first, those of LISHIP_SWEEP_LONG_ROW or more
  * terms from llong[l] on), row r's terms col/val[rptr[r] .. rptr[r+1]) in the order they are added.  groups[3g .. 3g+2] = {l0, l1, run}:
  * run = 1: levels [l0, l1) in one single-workgroup launch (each at most LISHIP_SWEEP_SMALL_LEVEL rows), run = 0: level l0 on its own.
@@ -563,7 +563,7 @@ int  liship_sweep_f64(const liship_sweep_t *sweep, int mode, const double *b, do
 /* the same rows without a diagonal: x[i] = b[i] - sum v x[j]; b may equal x (ILU: forward on L, backward on L^T) */
 int  liship_sweep_plain_f64(const liship_sweep_t *sweep, const double *b, double *x, void *stream);
 
-/* ------------------------------------------------------------------ ILU(k) numerical factorisation (kernels/ilu.hip)
+/* ------------------------------------------------------------------ ILU(k) numerical factorisation (kernels/ilu.hip on kernels/level_schedule.hpp)
  * A = (aptr, aindex, avalue) as it lies in HBM.  The symbolic pattern: row i of L = lcol[lptr[i] .. lptr[i+1]) ascending (a column
  * held twice: twice, side by side), of U = ucol[uptr[i] .. uptr[i+1]) in term order.  To find the place of a column in row i of U:
  * uskey = the row's columns ascending (ties by position), uspos = where each of them lies in ucol / uval; uspos NULL: the rows of

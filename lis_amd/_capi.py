@@ -215,8 +215,12 @@ _PROTOS = {
 }
 
 
-# the ILU(k) extensions of include/lis_amd.h: set where the library has them (liblis_amd.so), absent from the reference build
+# the SSOR and ILU(k) extensions of include/lis_amd.h: set where the library has them (liblis_amd.so), absent from the reference build
 _AMD_PROTOS = {
+    "lis_amd_last_solve_ssor": (LIS_INT, [P_INT, P_INT, P_INT, P_INT]),
+    "lis_amd_ssor_schedule_info": (LIS_INT, [PM, P_DBL]),
+    "lis_amd_ssor_sweep_info": (LIS_INT, [PM, LIS_INT, P_INT]),
+    "lis_amd_ssor_psolve_times": (LIS_INT, [PM, PV, PV, LIS_INT, P_DBL]),
     "lis_amd_last_solve_ilu": (LIS_INT, [P_INT, P_INT, P_INT, P_INT]),
     "lis_amd_ilu_factor": (LIS_INT, [PM, LIS_INT, P_INT]),
     "lis_amd_ilu_copy": (LIS_INT, [PM, LIS_INT, P_INT, P_INT, P_DBL, P_INT, P_INT, P_DBL, P_DBL]),

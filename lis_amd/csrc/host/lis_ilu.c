@@ -14,9 +14,9 @@
  * for T (lis_amd_set_reference_reductions(T)), which reproduces the reference at T threads.
  *
  * From the pattern: the forward levels (level of row i = 1 + the largest level of the rows its L pattern names), which the
- * factorisation (kernels/ilu.hip) and the forward sweep share, and four level-ordered sweep layouts (lisi_sweep_build, the SSOR
- * engine): L, U, and for M^-H the transposed U^T (terms by source row ascending) and L^T (by source row descending, ties by place
- * in the source row) -- as row-wise sums these are the reference's scatters bit for bit.  The layouts hold copies of the values:
+ * factorisation (kernels/ilu.hip) and the forward sweep share, and four level-ordered sweep layouts (lis_sweep.c, the engine
+ * SSOR runs on too): L, U, and for M^-H the transposed U^T (terms by source row ascending) and L^T (by source row descending,
+ * ties by place in the source row) -- as row-wise sums these are the reference's scatters bit for bit.  The layouts hold copies of the values:
  * after every factorisation a gather kernel per layout fills them in HBM from the factor (the permutation kept from the build).
  *   psolve : x = b; forward on L (no diagonal); backward on U, then x[i] = d[i] x[i]           (ref :880-934)
  *   psolveh: x = b; forward on U^T with x[i] = d[i] x[i] first; backward on L^T (no diagonal)    (ref :1086-1140)
@@ -64,15 +64,6 @@ void lisd_ilu_free(void *p)
 	entry_free(&il->e[0]); entry_free(&il->e[1]);
 	free(il);
 }
-
-static LIS_INT up_i(int **dst, const int *src, size_t count)
-{
-	HIPCHK(lisd_malloc((void **)dst, (count + 4) * sizeof(int)));
-	if (count) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(int), lisg.stream));
-	return LIS_SUCCESS;
-}
-
-static int blocks(void) { return lisg.ref_reductions > 0 ? lisg.ref_reductions : 1; }
 
 /* ------------------------------------------------------------------ symbolic step */
 typedef struct { int *v; size_t len, cap; } ivec;
@@ -181,7 +172,7 @@ static LIS_INT upload_search_keys(ilu_entry *e)
 		qsort(tmp, (size_t)len, sizeof(long long), cmp_ll);
 		for (int k = 0; k < len; k++) { key[u0 + k] = (int)(tmp[k] >> 32); pos[u0 + k] = (int)(tmp[k] & 0x7fffffff); }
 	}
-	if ((err = up_i(&e->d_uskey, key, (size_t)e->unnz)) || (err = up_i(&e->d_uspos, pos, (size_t)e->unnz))) goto out;
+	if ((err = lisd_upload_i(&e->d_uskey, key, (size_t)e->unnz)) || (err = lisd_upload_i(&e->d_uspos, pos, (size_t)e->unnz))) goto out;
 	{	int rc = liship_stream_synchronize(lisg.stream);
 		if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
 out:
@@ -189,36 +180,21 @@ out:
 	return err;
 }
 
-/* one of the four layouts, with the permutation that brings the factor's values into it */
+/* one of the four layouts, with the permutation that brings the factor's values into it (the pattern is block-filtered already) */
 static LIS_INT sweep_make(ilu_entry *e, int which)
 {
-	const int n = e->n;
-	const int *sp = (which == SW_L || which == SW_LT) ? e->lp : e->up, *sc = (which == SW_L || which == SW_LT) ? e->lc : e->uc;
-	const int nnz = sp[n];
-	int *src = NULL, *tp = NULL, *tc = NULL, *tid = NULL, *fill = NULL;
-	LIS_INT err = LIS_SUCCESS;
-	if (which == SW_L || which == SW_U) {
-		if ((err = lisi_sweep_build(&e->sw[which], n, sp, sc, NULL, which == SW_U, NULL, &src))) goto out;
-	} else {
-		tp = (int *)calloc((size_t)n + 2, sizeof(int)); tc = (int *)malloc(sizeof(int) * (size_t)(nnz + 1));
-		tid = (int *)malloc(sizeof(int) * (size_t)(nnz + 1)); fill = (int *)malloc(sizeof(int) * (size_t)(n + 1));
-		if (!tp || !tc || !tid || !fill) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)nnz); goto out; }
-		for (int k = 0; k < nnz; k++) tp[sc[k] + 1]++;
-		for (int i = 0; i < n; i++) tp[i + 1] += tp[i];
-		memcpy(fill, tp, sizeof(int) * (size_t)n);
-		for (int q = 0; q < n; q++) {          /* U^T by source row ascending, L^T by source row descending */
-			const int i = which == SW_UT ? q : n - 1 - q;
-			for (int k = sp[i]; k < sp[i + 1]; k++) { const int at = fill[sc[k]]++; tc[at] = i; tid[at] = k; }
-		}
-		if ((err = lisi_sweep_build(&e->sw[which], n, tp, tc, NULL, which == SW_LT, NULL, &src))) goto out;
-		for (int k = 0; k < nnz; k++) src[k] = tid[src[k]];
-	}
-	if ((err = up_i(&e->d_src[which], src, (size_t)nnz))) goto out;
+	const int n = e->n, lower = which == SW_L || which == SW_LT, nnz = lower ? e->lnnz : e->unnz;
+	int *src = NULL, *tp = NULL, *tc = NULL, *tid = NULL;
+	LIS_INT err;
+	if ((err = lisi_sweep_terms(n, lower ? e->lp : e->up, lower ? e->lc : e->uc, NULL, SW_TERMS(which), &tp, &tc, &tid))) goto out;
+	if ((err = lisi_sweep_build(&e->sw[which], n, tp, tc, NULL, SW_DESC(which), NULL, &src))) goto out;
+	for (int k = 0; k < nnz; k++) src[k] = tid[src[k]];
+	if ((err = lisd_upload_i(&e->d_src[which], src, (size_t)nnz))) goto out;
 	{	int rc = liship_stream_synchronize(lisg.stream);
 		if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
-	e->sw[which].bytes = 4.0 * n + 4.0 * (n + 1) + 12.0 * nnz + ((which == SW_U || which == SW_UT) ? 24.0 : 16.0) * n;
+	e->sw[which].bytes = lisi_sweep_bytes(n, nnz, lower ? 16.0 : 24.0);
 out:
-	free(src); free(tp); free(tc); free(tid); free(fill);
+	free(src); free(tp); free(tc); free(tid);
 	if (err) { lisi_sweep_free(&e->sw[which]); (void)liship_free(e->d_src[which]); e->d_src[which] = NULL; }
 	return err;
 }
@@ -278,8 +254,8 @@ static LIS_INT entry_build(LIS_MATRIX A, ilu_entry *e, int fill, int T)
 	if (!weight) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)n); goto out; }
 	for (int i = 0; i < n; i++) weight[i] = (e->lp[i + 1] - e->lp[i]) + (e->up[i + 1] - e->up[i]);
 	if ((err = lisi_sweep_build(&e->sched, n, e->lp, e->lc, NULL, 0, weight, NULL))) goto out;
-	if ((err = up_i(&e->d_lp, e->lp, (size_t)n + 1)) || (err = up_i(&e->d_lc, e->lc, (size_t)e->lnnz)) ||
-	    (err = up_i(&e->d_up, e->up, (size_t)n + 1)) || (err = up_i(&e->d_uc, e->uc, (size_t)e->unnz))) goto out;
+	if ((err = lisd_upload_i(&e->d_lp, e->lp, (size_t)n + 1)) || (err = lisd_upload_i(&e->d_lc, e->lc, (size_t)e->lnnz)) ||
+	    (err = lisd_upload_i(&e->d_up, e->up, (size_t)n + 1)) || (err = lisd_upload_i(&e->d_uc, e->uc, (size_t)e->unnz))) goto out;
 	{	int rc = lisd_malloc((void **)&e->d_lval, ((size_t)e->lnnz + 2) * sizeof(double));
 		if (!rc) rc = lisd_malloc((void **)&e->d_uval, ((size_t)e->unnz + 2) * sizeof(double));
 		if (!rc) rc = lisd_malloc((void **)&e->d_d, ((size_t)n + 2) * sizeof(double));
@@ -354,7 +330,7 @@ LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon)
 	if (solver->options[LIS_OPTIONS_ADDS]) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu with -adds true is not served (A is untouched)\n");
 	LISCHK(check_served(A, fill));
 	ilu_entry *e;
-	LISCHK(get_entry(A, (int)fill, blocks(), &e));
+	LISCHK(get_entry(A, (int)fill, lisi_sweep_blocks(), &e));
 	const liship_sweep_t *s;
 	LISCHK(get_sweep(e, SW_L, &s));
 	LISCHK(get_sweep(e, SW_U, &s));
@@ -368,7 +344,7 @@ LIS_INT lisd_ilu_begin(LIS_MATRIX A, int fill, int *T)
 {
 	ilu_entry *e;
 	const liship_sweep_t *f, *b;
-	*T = blocks();
+	*T = lisi_sweep_blocks();
 	LISCHK(check_served(A, fill));
 	LISCHK(get_entry(A, fill, *T, &e));
 	LISCHK(get_sweep(e, SW_L, &f));
@@ -430,7 +406,7 @@ static LIS_INT tool_entry(LIS_MATRIX A, LIS_INT fill, ilu_entry **e)
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisd_init());
 	LISCHK(check_served(A, fill));
-	return get_entry(A, (int)fill, blocks(), e);
+	return get_entry(A, (int)fill, lisi_sweep_blocks(), e);
 }
 
 LIS_INT lis_amd_ilu_factor(LIS_MATRIX A, LIS_INT fill, LIS_INT sizes[3])
@@ -475,6 +451,10 @@ LIS_INT lis_amd_ilu_psolve(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR 
 	return lisd_vec_done(X);
 }
 
+typedef struct { LIS_MATRIX A; ilu_entry *e; const double *b; double *x; } timed_args;
+static LIS_INT factorise_once(void *ctx) { const timed_args *t = (const timed_args *)ctx; return factorise(t->A, t->e); }
+static LIS_INT psolve_once(void *ctx) { const timed_args *t = (const timed_args *)ctx; return psolve_on(t->e, t->b, t->x); }
+
 LIS_INT lis_amd_ilu_times(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *factor_ms, double *psolve_ms)
 {	/* reps factorisations and reps psolves X = M^-1 B on the library's stream, each timed by device events */
 	ilu_entry *e;
@@ -486,22 +466,9 @@ LIS_INT lis_amd_ilu_times(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR X
 	double *db, *dx;
 	LISCHK(lisd_vec_in(B, &db));
 	LISCHK(lisd_vec_out(X, &dx));
-	void *timer = NULL;
-	HIPCHK(liship_timer_create(&timer));
-	LIS_INT err = LIS_SUCCESS;
-	for (int pass = 0; pass < 2 && !err; pass++)
-		for (LIS_INT k = 0; k < reps && !err; k++) {
-			float ms = 0.0f;
-			int rc = liship_timer_start(timer, lisg.stream);
-			if (!rc) err = pass == 0 ? factorise(A, e) : psolve_on(e, db, dx);
-			if (!rc && !err) rc = liship_timer_stop(timer, lisg.stream);
-			if (!rc && !err) rc = liship_stream_synchronize(lisg.stream);
-			if (!rc && !err) rc = liship_timer_elapsed_ms(timer, &ms);
-			if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
-			if (pass == 0) { if (factor_ms) factor_ms[k] = ms; } else if (psolve_ms) psolve_ms[k] = ms;
-		}
-	(void)liship_timer_destroy(timer);
-	if (err) return err;
+	timed_args args = {A, e, db, dx};
+	LISCHK(lisi_sweep_times(reps, factorise_once, &args, factor_ms));
+	LISCHK(lisi_sweep_times(reps, psolve_once, &args, psolve_ms));
 	return lisd_vec_done(X);
 }
 
@@ -528,14 +495,7 @@ LIS_INT lis_amd_ilu_factor_info(LIS_MATRIX A, LIS_INT fill, LIS_INT info[6])
 	 * those levels, rows given to a workgroup inside runs of small levels, 1 when such rows are factorised by one thread} */
 	ilu_entry *e;
 	LISCHK(tool_entry(A, fill, &e));
-	const liship_sweep_t *s = &e->sched.k;
-	LIS_INT own = 0, long_own = 0, long_run = 0;
-	for (int g = 0; g < s->ngroups; g++)
-		for (int l = s->groups[3 * g]; l < s->groups[3 * g + 1]; l++) {
-			const int nlong = s->h_nrows[l] - s->h_nshort[l];
-			if (s->groups[3 * g + 2]) long_run += nlong;
-			else { own++; long_own += nlong; }
-		}
-	info[0] = s->nlev; info[1] = s->ngroups; info[2] = own; info[3] = long_own; info[4] = long_run; info[5] = e->serial;
+	lisi_sweep_census(&e->sched.k, info);
+	info[5] = e->serial;
 	return LIS_SUCCESS;
 }

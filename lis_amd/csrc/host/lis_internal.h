@@ -244,19 +244,29 @@ void    lisi_matrix_dlu_destroy(LIS_MATRIX A);
 LIS_INT lisi_split_rows(LIS_MATRIX A, LIS_INT *rows, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val, int *from_zero);
 LIS_INT lisi_matrix_bscale_bsr(LIS_MATRIX A, LIS_VECTOR B);                  /* -scale jacobi -storage bsr (lis_scale.c) */
 LIS_INT lisi_split_jad_part(LIS_MATRIX A, int upper, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val);
-/* ---- level-ordered sweep layouts (lis_ssor.c), shared by SSOR and ILU */
+/* ---- level-ordered sweep layouts (lis_sweep.c), shared by SSOR and ILU */
 typedef struct {
 	int built;
 	liship_sweep_t k;                          /* what the launcher reads */
 	int *lptr, *llong, *rows, *rptr, *col;     /* HBM */
 	double *val;
 	int *groups, *nrows, *nshort;              /* host */
-	double bytes;                              /* one application: level-ordered streams + b / x / wd per row */
+	double bytes;                              /* one application (lisi_sweep_bytes), set by the owner once the sweep is built */
 } lisi_sweep_t;
 enum { SW_L, SW_U, SW_UT, SW_LT, SW_COUNT };   /* the four sweeps of a preconditioner: forward on L, backward on U, forward on U^T, backward on L^T */
-void    lisi_sweep_free(lisi_sweep_t *s);
+enum { LISI_TERMS_ROWS, LISI_TERMS_T_ASC, LISI_TERMS_T_DESC };               /* lisi_sweep_terms: the rows as stored; transposed, by source row ascending / descending */
+#define SW_TERMS(w) ((w) == SW_UT ? LISI_TERMS_T_ASC : (w) == SW_LT ? LISI_TERMS_T_DESC : LISI_TERMS_ROWS)
+#define SW_DESC(w)  ((w) == SW_U || (w) == SW_LT)                            /* the sweep runs from the last row to the first */
+LIS_INT lisd_upload_i(int **dst, const int *src, size_t count);               /* a fresh HBM array holding src[0 .. count), queued on the library's stream */
+LIS_INT lisd_upload_d(double **dst, const double *src, size_t count);         /* (src NULL: room only) */
+int     lisi_sweep_blocks(void);                                             /* row blocks of the solves: 1, or the reference-order mode's T */
 int    *lisi_block_of(int n, int T);                                         /* block of every row among T blocks of LIS_GET_ISIE (caller frees) */
+LIS_INT lisi_sweep_terms(int n, const int *ptr, const int *idx, const int *blk, int order, int **tp, int **tc, int **tid);   /* the terms of a sweep, row by row; tid: their places in idx */
 LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out);
+void    lisi_sweep_free(lisi_sweep_t *s);
+double  lisi_sweep_bytes(int n, int nnz, double vec_bytes_per_row);          /* one application: 24 B per row of vectors with a diagonal, 16 B plain */
+void    lisi_sweep_census(const liship_sweep_t *s, LIS_INT census[5]);       /* {levels, launches, own-launch levels, long rows in those, long rows in runs} */
+LIS_INT lisi_sweep_times(LIS_INT reps, LIS_INT (*apply)(void *ctx), void *ctx, double *ms);   /* reps event-timed calls of apply: ms[k] */
 /* ---- ILU(k) (lis_ilu.c) */
 LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon);              /* refusals, symbolic step (cached), factorisation on the device */
 void    lisd_ilu_free(void *ilu);                                            /* (lisd_mat_free) */

@@ -10,11 +10,10 @@
  * of it: block-Jacobi SSOR with T blocks.  Here T = 1 (true SSOR, independent of any core count) unless the reference-order mode
  * asks for T (lis_amd_set_reference_reductions(T)), which reproduces the reference at T threads.
  *
- * Schedule: per sweep, the level of a row is 1 + the largest level of the rows its kept terms read; rows of a level and their terms
- * are stored contiguously in level order (the reference's in-row order kept).  The transposed sweeps of psolveh hold, for row jj of
- * U^T, its terms by source row ascending, of L^T by source row descending (ties by position in the source row): a row-wise sum in
- * that order is the reference's scatter sum bit for bit.  Built on the host (O(nnz), from the split parts), cached on the HBM copy
- * of A (lisd_mat.ssor) and dropped with it (lisd_mat_free: host edits, page-watch writes, conversions).
+ * Schedule: the four sweeps (L, U, and for psolveh U^T and L^T) keep the terms whose row and column lie in the same block, are
+ * listed and laid out by level by lis_sweep.c in the reference's order of additions, built on the host (O(nnz), from the split
+ * parts) on first use, cached on the HBM copy of A (lisd_mat.ssor) and dropped with it (lisd_mat_free: host edits, page-watch
+ * writes, conversions).
  */
 #include <stdio.h>
 #include "lis_krylov.h"
@@ -35,14 +34,6 @@ typedef struct {
 	double build_s;                            /* host seconds spent building schedules */
 } lisd_ssor;
 
-void lisi_sweep_free(lisi_sweep_t *s)
-{
-	(void)liship_free(s->lptr); (void)liship_free(s->llong); (void)liship_free(s->rows); (void)liship_free(s->rptr);
-	(void)liship_free(s->col); (void)liship_free(s->val);
-	free(s->groups); free(s->nrows); free(s->nshort);
-	memset(s, 0, sizeof(*s));
-}
-
 void lisd_ssor_free(void *p)
 {
 	lisd_ssor *ss = (lisd_ssor *)p;
@@ -52,139 +43,23 @@ void lisd_ssor_free(void *p)
 	free(ss);
 }
 
-/* block of row i among T blocks of LIS_GET_ISIE (ref include/lis.h:1067): the first n % T blocks hold n / T + 1 rows */
-int *lisi_block_of(int n, int T)
-{
-	int *b = (int *)malloc(sizeof(int) * (size_t)(n > 0 ? n : 1));
-	if (!b) return NULL;
-	const int q = n / T, rem = n % T;
-	for (int i = 0; i < n; i++) b[i] = (i < rem * (q + 1)) ? i / (q + 1) : rem + (i - rem * (q + 1)) / q;
-	return b;
-}
-
-static LIS_INT up_i(int **dst, const int *src, size_t count)
-{
-	HIPCHK(lisd_malloc((void **)dst, (count + 4) * sizeof(int)));
-	if (count) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(int), lisg.stream));
-	return LIS_SUCCESS;
-}
-static LIS_INT up_d(double **dst, const double *src, size_t count)
-{
-	HIPCHK(lisd_malloc((void **)dst, (count + 2) * sizeof(double)));
-	if (count && src) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(double), lisg.stream));
-	return LIS_SUCCESS;
-}
-
-/* levels + level-ordered layout of n rows whose terms (tp, tc, tv) read only rows before them (desc = 0) or after them (desc = 1).
- * tv NULL: no values (a schedule only, or values that arrive later on the device); weight: what decides whether row i is a long
- * row instead of its term count; src_out: for every place of the layout the term (index into tc) that lies there (caller frees) */
-LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out)
-{
-	LIS_INT err = LIS_SUCCESS;
-	const int nnz = tp[n];
-	int *lev = (int *)malloc(sizeof(int) * (size_t)(n + 1));
-	int *rows = (int *)malloc(sizeof(int) * (size_t)(n + 1)), *rptr = (int *)malloc(sizeof(int) * (size_t)(n + 1));
-	int *col = (int *)malloc(sizeof(int) * (size_t)(nnz + 1));
-	double *val = tv ? (double *)malloc(sizeof(double) * (size_t)(nnz + 1)) : NULL;
-	int *src = src_out ? (int *)malloc(sizeof(int) * (size_t)(nnz + 1)) : NULL;
-	int *lptr = NULL, *llong = NULL, *fill_s = NULL, *fill_l = NULL;
-#define ROW_WEIGHT(i) (weight ? weight[(i)] : tp[(i) + 1] - tp[(i)])
-	if (!lev || !rows || !rptr || !col || (tv && !val) || (src_out && !src)) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)nnz); goto out; }
-	int nlev = 0;
-	for (int q = 0; q < n; q++) {
-		const int i = desc ? n - 1 - q : q;
-		int l = 0;
-		for (int k = tp[i]; k < tp[i + 1]; k++) { const int lj = lev[tc[k]] + 1; if (lj > l) l = lj; }
-		lev[i] = l;
-		if (l + 1 > nlev) nlev = l + 1;
-	}
-	s->nrows = (int *)calloc((size_t)nlev + 1, sizeof(int)); s->nshort = (int *)calloc((size_t)nlev + 1, sizeof(int));
-	lptr = (int *)calloc((size_t)nlev + 1, sizeof(int)); llong = (int *)calloc((size_t)nlev + 1, sizeof(int));
-	fill_s = (int *)calloc((size_t)nlev + 1, sizeof(int)); fill_l = (int *)calloc((size_t)nlev + 1, sizeof(int));
-	s->groups = (int *)malloc(sizeof(int) * 3 * ((size_t)nlev + 1));
-	if (!s->nrows || !s->nshort || !lptr || !llong || !fill_s || !fill_l || !s->groups) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)nlev); goto out; }
-	for (int i = 0; i < n; i++) { s->nrows[lev[i]]++; if (ROW_WEIGHT(i) < LISHIP_SWEEP_LONG_ROW) s->nshort[lev[i]]++; }
-	for (int l = 0; l < nlev; l++) { lptr[l + 1] = lptr[l] + s->nrows[l]; llong[l] = lptr[l] + s->nshort[l]; fill_s[l] = lptr[l]; fill_l[l] = llong[l]; }
-	for (int i = 0; i < n; i++) {             /* rows by level; inside a level short rows first, each part by ascending row */
-		const int l = lev[i];
-		if (ROW_WEIGHT(i) < LISHIP_SWEEP_LONG_ROW) rows[fill_s[l]++] = i; else rows[fill_l[l]++] = i;
-	}
-	rptr[0] = 0;
-	for (int r = 0; r < n; r++) {
-		const int i = rows[r];
-		int at = rptr[r];
-		for (int k = tp[i]; k < tp[i + 1]; k++, at++) { col[at] = tc[k]; if (val) val[at] = tv[k]; if (src) src[at] = k; }
-		rptr[r + 1] = at;
-	}
-	/* launches: runs of small levels in one workgroup, every large level on its own */
-	int ng = 0;
-	for (int l = 0; l < nlev; ) {
-		if (s->nrows[l] <= LISHIP_SWEEP_SMALL_LEVEL) {
-			int e = l;
-			while (e < nlev && s->nrows[e] <= LISHIP_SWEEP_SMALL_LEVEL) e++;
-			s->groups[3 * ng] = l; s->groups[3 * ng + 1] = e; s->groups[3 * ng + 2] = 1; ng++;
-			l = e;
-		} else {
-			s->groups[3 * ng] = l; s->groups[3 * ng + 1] = l + 1; s->groups[3 * ng + 2] = 0; ng++;
-			l++;
-		}
-	}
-	if ((err = up_i(&s->lptr, lptr, (size_t)nlev + 1)) || (err = up_i(&s->llong, llong, (size_t)nlev + 1)) || (err = up_i(&s->rows, rows, (size_t)n)) ||
-	    (err = up_i(&s->rptr, rptr, (size_t)n + 1)) || (err = up_i(&s->col, col, (size_t)nnz)) || ((tv || src_out) && (err = up_d(&s->val, val, (size_t)nnz)))) goto out;      /* (values that arrive later: room only) */
-	{	int rc = liship_stream_synchronize(lisg.stream);          /* (the host arrays go below) */
-		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; } }
-	s->k.nlev = nlev; s->k.nrows = n; s->k.nnz = nnz; s->k.ngroups = ng;
-	s->k.lptr = s->lptr; s->k.llong = s->llong; s->k.rows = s->rows; s->k.rptr = s->rptr; s->k.col = s->col; s->k.val = s->val;
-	s->k.groups = s->groups; s->k.h_nrows = s->nrows; s->k.h_nshort = s->nshort;
-	s->bytes = 4.0 * n + 4.0 * (n + 1) + 12.0 * nnz + 24.0 * n;
-	s->built = 1;
-	if (src_out) { *src_out = src; src = NULL; }
-out:
-#undef ROW_WEIGHT
-	free(lev); free(rows); free(rptr); free(col); free(val); free(src); free(lptr); free(llong); free(fill_s); free(fill_l);
-	if (err) lisi_sweep_free(s);
-	return err;
-}
-
-/* the terms of one sweep under T blocks: those whose row and column lie in the same block (T = 1: all of them) */
+/* one sweep under T blocks: the terms whose row and column lie in the same block (T = 1: all of them), with their values */
 static LIS_INT sweep_make(LIS_MATRIX A, int which, int T, sweep_t *s)
 {
 	const int n = A->n;
 	LIS_MATRIX_CORE P = (which == SW_L || which == SW_LT) ? A->L : A->U;
-	int *blk = lisi_block_of(n, T);
-	int *tp = (int *)calloc((size_t)n + 2, sizeof(int));
-	const int pn = P->ptr[n];
-	int *tc = (int *)malloc(sizeof(int) * (size_t)(pn + 1));
-	double *tv = (double *)malloc(sizeof(double) * (size_t)(pn + 1));
+	int *blk = lisi_block_of(n, T), *tp = NULL, *tc = NULL, *tid = NULL;
+	double *tv = NULL;
 	LIS_INT err = LIS_SUCCESS;
-	if (!blk || !tp || !tc || !tv) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)pn); goto out; }
-#define KEEP(i, c) ((c) >= 0 && (c) < n && blk[(i)] == blk[(c)])
-	if (which == SW_L || which == SW_U) {          /* the rows themselves, stored order */
-		int at = 0;
-		for (int i = 0; i < n; i++) {
-			for (int k = P->ptr[i]; k < P->ptr[i + 1]; k++) if (KEEP(i, P->index[k])) { tc[at] = P->index[k]; tv[at] = P->value[k]; at++; }
-			tp[i + 1] = at;
-		}
-	} else {                                      /* transposed: U^T by source row ascending, L^T by source row descending */
-		for (int i = 0; i < n; i++)
-			for (int k = P->ptr[i]; k < P->ptr[i + 1]; k++) if (KEEP(i, P->index[k])) tp[P->index[k] + 1]++;
-		for (int i = 0; i < n; i++) tp[i + 1] += tp[i];
-		int *fill = (int *)malloc(sizeof(int) * (size_t)(n + 1));
-		if (!fill) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)n); goto out; }
-		memcpy(fill, tp, sizeof(int) * (size_t)n);
-		for (int q = 0; q < n; q++) {
-			const int i = which == SW_UT ? q : n - 1 - q;
-			for (int k = P->ptr[i]; k < P->ptr[i + 1]; k++) {
-				const int c = P->index[k];
-				if (KEEP(i, c)) { const int at = fill[c]++; tc[at] = i; tv[at] = P->value[k]; }
-			}
-		}
-		free(fill);
-	}
-#undef KEEP
-	err = lisi_sweep_build(s, n, tp, tc, tv, which == SW_U || which == SW_LT, NULL, NULL);
+	if (!blk) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)n); goto out; }
+	if ((err = lisi_sweep_terms(n, P->ptr, P->index, blk, SW_TERMS(which), &tp, &tc, &tid))) goto out;
+	tv = (double *)malloc(sizeof(double) * (size_t)(tp[n] + 1));
+	if (!tv) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)tp[n]); goto out; }
+	for (int k = 0; k < tp[n]; k++) tv[k] = P->value[tid[k]];
+	if ((err = lisi_sweep_build(s, n, tp, tc, tv, SW_DESC(which), NULL, NULL))) goto out;
+	s->bytes = lisi_sweep_bytes(n, s->k.nnz, 24.0);
 out:
-	free(blk); free(tp); free(tc); free(tv);
+	free(blk); free(tp); free(tc); free(tid); free(tv);
 	return err;
 }
 
@@ -232,8 +107,6 @@ static LIS_INT upload_wd(LIS_MATRIX A, const double **out)
 	return LIS_SUCCESS;
 }
 
-static int blocks(void) { return lisg.ref_reductions > 0 ? lisg.ref_reductions : 1; }
-
 /* ------------------------------------------------------------------ create */
 LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon)
 {
@@ -276,7 +149,7 @@ LIS_INT lisd_ssor_begin(LIS_MATRIX A, int *T)
 {
 	const liship_sweep_t *f, *b;
 	const double *wd;
-	*T = blocks();
+	*T = lisi_sweep_blocks();
 	LISCHK(get_sweep(A, *T, SW_L, &f));
 	LISCHK(get_sweep(A, *T, SW_U, &b));
 	LISCHK(upload_wd(A, &wd));
@@ -317,7 +190,7 @@ static LIS_INT solve_common(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT fl
 	if (flag != LIS_MATRIX_LOWER && flag != LIS_MATRIX_UPPER && flag != LIS_MATRIX_SSOR) return LISI_ERR(LIS_ERR_ILL_ARG, "flag %D is not LOWER, UPPER or SSOR\n", flag);
 	if (B->n != A->n || X->n != A->n) return LISI_ERR(LIS_ERR_ILL_ARG, "sizes of A, B and X do not match\n");
 	LISCHK(lisd_mat_ready(A));
-	const int T = flag == LIS_MATRIX_SSOR ? blocks() : 1;
+	const int T = flag == LIS_MATRIX_SSOR ? lisi_sweep_blocks() : 1;
 	const liship_sweep_t *s1, *s2 = NULL;
 	const double *wd;
 	if (!herm) {
@@ -363,7 +236,7 @@ LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4])
 	LISCHK(check_split(A));
 	LISCHK(lisd_mat_ready(A));
 	const liship_sweep_t *f, *b;
-	const int T = blocks();
+	const int T = lisi_sweep_blocks();
 	LISCHK(get_sweep(A, T, SW_L, &f));
 	LISCHK(get_sweep(A, T, SW_U, &b));
 	lisd_ssor *ss = (lisd_ssor *)MDEV(A)->ssor;
@@ -382,43 +255,27 @@ LIS_INT lis_amd_ssor_sweep_info(LIS_MATRIX A, LIS_INT sweep, LIS_INT info[6])
 	if (sweep < 0 || sweep >= SW_COUNT || !info) return LISI_ERR(LIS_ERR_ILL_ARG, "sweep %D is not 0 .. 3, or info is NULL\n", sweep);
 	LISCHK(lisd_mat_ready(A));
 	const liship_sweep_t *s;
-	LISCHK(get_sweep(A, blocks(), (int)sweep, &s));
-	LIS_INT own = 0, long_own = 0, long_run = 0;
-	for (int g = 0; g < s->ngroups; g++)
-		for (int l = s->groups[3 * g]; l < s->groups[3 * g + 1]; l++) {
-			const int nlong = s->h_nrows[l] - s->h_nshort[l];
-			if (s->groups[3 * g + 2]) long_run += nlong;
-			else { own++; long_own += nlong; }
-		}
-	info[0] = s->nlev; info[1] = s->ngroups; info[2] = own; info[3] = long_own; info[4] = long_run; info[5] = s->nnz;
+	LISCHK(get_sweep(A, lisi_sweep_blocks(), (int)sweep, &s));
+	lisi_sweep_census(s, info);
+	info[5] = s->nnz;
 	return LIS_SUCCESS;
 }
+
+typedef struct { LIS_MATRIX A; int T; const double *b; double *x; } psolve_args;
+static LIS_INT psolve_once(void *ctx) { const psolve_args *p = (const psolve_args *)ctx; return lisd_ssor_psolve(p->A, p->T, p->b, p->x); }
 
 LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms)
 {	/* reps psolves X = M^-1 B on the library's stream, each timed by device events (ms[k]) */
 	LISCHK(check_split(A));
 	LISCHK(lisd_mat_ready(A));
 	const double *wd;
-	int T = blocks();
+	int T = lisi_sweep_blocks();
 	LISCHK(lisd_ssor_begin(A, &T));
 	LISCHK(upload_wd(A, &wd));
 	double *db, *dx;
 	LISCHK(lisd_vec_in(B, &db));
 	LISCHK(lisd_vec_out(X, &dx));
-	void *timer = NULL;
-	HIPCHK(liship_timer_create(&timer));
-	LIS_INT err = LIS_SUCCESS;
-	for (LIS_INT k = 0; k < reps && !err; k++) {
-		float e = 0.0f;
-		int rc = liship_timer_start(timer, lisg.stream);
-		if (!rc) err = lisd_ssor_psolve(A, T, db, dx);
-		if (!rc && !err) rc = liship_timer_stop(timer, lisg.stream);
-		if (!rc && !err) rc = liship_stream_synchronize(lisg.stream);
-		if (!rc && !err) rc = liship_timer_elapsed_ms(timer, &e);
-		if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
-		ms[k] = e;
-	}
-	(void)liship_timer_destroy(timer);
-	if (err) return err;
+	psolve_args args = {A, T, db, dx};
+	LISCHK(lisi_sweep_times(reps, psolve_once, &args, ms));
 	return lisd_vec_done(X);
 }

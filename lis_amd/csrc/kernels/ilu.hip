@@ -1,8 +1,8 @@
-// ilu.hip -- the numerical factorisation of ILU(k) along the forward levels (lis_ilu.c builds pattern and schedule).
+// ilu.hip -- the numerical factorisation of ILU(k) along the forward levels (lis_ilu.c builds the pattern, lis_sweep.c the schedule).
 //
 // Row i of the factor depends on the rows its L pattern names, all of earlier levels: the rows of one level are independent.
-// Like the sweeps (sptrsv.hip): a level of more than LISHIP_SWEEP_SMALL_LEVEL rows is one launch, a run of smaller levels one
-// single-workgroup launch with __syncthreads() between levels; no workgroup ever waits on a flag another workgroup writes.
+// The levels are walked like those of the sweeps (level_schedule.hpp): a level of more than LISHIP_SWEEP_SMALL_LEVEL rows is one
+// launch, a run of smaller levels one single-workgroup launch.
 //
 // One row: L, D, U of the row start at 0 and take A's kept entries; then for every pivot j of L(i), ascending,
 //   l = L[i][j] * d[j] (d holds 1 / pivot), stored; for every term (c, u) of U(j) with c in row i's pattern: target = target - l * u
@@ -15,13 +15,9 @@
 // (uskey / uspos); a binary search in the row's own keys, which stay in the CU's L1 / L2 while the row is worked on.  Of equal keys
 // the last one answers (the reference's jw[] keeps the later place of a column stored twice).  When a row of A stores a column
 // twice a pivot may hit one target twice: `serial` hands such matrices' long rows to one thread.
-#include "common.hpp"
-#include "liship.h"
+#include "level_schedule.hpp"
 
 namespace {
-
-constexpr int LEVEL_BLOCK = 256;        // one level per launch: a thread per short row, a workgroup per long row
-constexpr int RUN_BLOCK = 1024;         // a run of small levels: one workgroup
 
 struct Fac {
     int n, serial;
@@ -127,28 +123,15 @@ __device__ void row_by_workgroup(const Fac &f, int i)
     if (t == 0) f.d[i] = 1.0 / f.d[i];
 }
 
-// one level: blocks [0, nshort_blocks) take a short row per thread, each further block one long row
-__global__ __launch_bounds__(LEVEL_BLOCK) void factor_level(Fac f, int level, int nshort_blocks)
-{
-    const int r0 = f.slptr[level], rl = f.sllong[level];
-    if ((int)blockIdx.x < nshort_blocks) {
-        const int r = r0 + (int)blockIdx.x * LEVEL_BLOCK + (int)threadIdx.x;
-        if (r < rl) row_by_thread(f, f.srows[r]);
-    } else {
-        row_by_workgroup<LEVEL_BLOCK>(f, f.srows[rl + (int)blockIdx.x - nshort_blocks]);
-    }
-}
-
-// levels [l0, l1) in one workgroup, a barrier between consecutive levels
-__global__ __launch_bounds__(RUN_BLOCK) void factor_run(Fac f, int l0, int l1)
-{
-    for (int l = l0; l < l1; l++) {
-        const int r0 = f.slptr[l], rl = f.sllong[l], r1 = f.slptr[l + 1];
-        for (int r = r0 + (int)threadIdx.x; r < rl; r += RUN_BLOCK) row_by_thread(f, f.srows[r]);
-        for (int r = rl; r < r1; r++) { row_by_workgroup<RUN_BLOCK>(f, f.srows[r]); __syncthreads(); }
-        __syncthreads();
-    }
-}
+// the rows of the factorisation (level_schedule.hpp); no LDS.  In a run every long row ends on a barrier of its own.
+struct FacRows {
+    Fac f;
+    __device__ __forceinline__ const int *level_ptr() const { return f.slptr; }
+    __device__ __forceinline__ const int *level_long() const { return f.sllong; }
+    __device__ __forceinline__ void short_row(int r) const { row_by_thread(f, f.srows[r]); }
+    template <int BS, bool IN_RUN>
+    __device__ __forceinline__ void long_row(int r) const { row_by_workgroup<BS>(f, f.srows[r]); if (IN_RUN) __syncthreads(); }
+};
 
 }  // namespace
 
@@ -157,20 +140,7 @@ extern "C" int liship_ilu_factor_f64(const liship_ilu_t *p, const liship_sweep_t
     if (!p || !sw || p->n < 0 || sw->nrows != p->n) return LISHIP_ERR_ARG;
     if (p->n == 0) return 0;
     if (!p->aptr || !p->lptr || !p->uptr || !p->d || !sw->lptr || !sw->llong || !sw->rows) return LISHIP_ERR_ARG;
-    hipStream_t st = as_stream(stream);
-    const Fac f{p->n, p->serial, p->aptr, p->aindex, p->avalue, p->lptr, p->lcol, p->uptr, p->ucol, p->uskey, p->uspos,
-                p->lval, p->uval, p->d, sw->lptr, sw->llong, sw->rows};
-    for (int g = 0; g < sw->ngroups; g++) {
-        const int l0 = sw->groups[3 * g], l1 = sw->groups[3 * g + 1], run = sw->groups[3 * g + 2];
-        if (run) {
-            factor_run<<<1, RUN_BLOCK, 0, st>>>(f, l0, l1);
-        } else {
-            const int nshort = sw->h_nshort[l0];
-            const int nsb = (nshort + LEVEL_BLOCK - 1) / LEVEL_BLOCK;
-            const int grid = nsb + (sw->h_nrows[l0] - nshort);
-            factor_level<<<grid, LEVEL_BLOCK, 0, st>>>(f, l0, nsb);
-        }
-        LAUNCH_CHECK();
-    }
-    return 0;
+    const FacRows rows{{p->n, p->serial, p->aptr, p->aindex, p->avalue, p->lptr, p->lcol, p->uptr, p->ucol, p->uskey, p->uspos,
+                        p->lval, p->uval, p->d, sw->lptr, sw->llong, sw->rows}};
+    return walk_levels(sw, rows, as_stream(stream));
 }

@@ -1,4 +1,4 @@
-"""-p ilu on the GPU (lis_ilu.c, kernels/ilu.hip, the sweeps of kernels/sptrsv.hip) against tests/ilu_oracle.py in every bit, against
+"""-p ilu on the GPU (lis_ilu.c on lis_sweep.c, kernels/ilu.hip, the sweeps of kernels/sptrsv.hip) against tests/ilu_oracle.py in every bit, against
 tests/golden/ilu_bits.{json,npz} (make_golden_ilu.py: the reference at T = 1 and T = 8) and against the reference library itself.
 
 The factor and the two psolves are the reference's bits at any block count: pattern, term order, every value.  Whole solves are the

@@ -1,4 +1,4 @@
-"""-p ssor on the GPU (lis_ssor.c, kernels/sptrsv.hip) against the reference library itself (oracle/_ref, one OpenMP thread) and
+"""-p ssor on the GPU (lis_ssor.c on lis_sweep.c, kernels/sptrsv.hip) against the reference library itself (oracle/_ref, one OpenMP thread) and
 against tests/golden/ssor_bits.{json,npz} (make_golden_ssor.py: the reference at T = 1 and T = 8).
 
 The preconditioner's bits are the reference's: the sweeps add every row's terms in the reference's order with its roundings.  Only the

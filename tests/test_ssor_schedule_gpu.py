@@ -1,4 +1,4 @@
-"""The sweep kernels of -p ssor (kernels/sptrsv.hip) and the schedule builder (lis_ssor.c) against tests/ssor_oracle.py, bit for bit,
+"""The sweep kernels of -p ssor (kernels/sptrsv.hip) and the schedule builder (lis_sweep.c) against tests/ssor_oracle.py, bit for bit,
 on matrices built to a prescribed level schedule (tests/ssor_cases.py): every level size and row length at which the per-level
 kernel, its tail block, its long-row workgroups and the run / own-launch switch change behaviour.
 

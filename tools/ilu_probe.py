@@ -27,7 +27,6 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import lis_amd  # noqa: E402
 import lisdrv  # noqa: E402
 import orc  # noqa: E402
-from lis_amd import _capi as capi  # noqa: E402
 
 REPS = 40
 
@@ -84,7 +83,6 @@ def probe(lib, N, fills):
         row[f"cg_{pc}"] = solve_row(lib, A, b, f"-i cg -p {pc}")
     ms = (C.c_double * REPS)()
     vb, vx = lisdrv.new_vector(lib, A, rhs), lisdrv.new_vector(lib, A)
-    dll.lis_amd_ssor_psolve_times.argtypes = [capi.PM, capi.PV, capi.PV, C.c_int, capi.P_DBL]
     assert dll.lis_amd_ssor_psolve_times(A, vb, vx, REPS, ms) == 0
     lib.lis_vector_destroy(vb)
     lib.lis_vector_destroy(vx)
