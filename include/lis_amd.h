@@ -123,6 +123,18 @@ LIS_INT lis_amd_ilu_info(LIS_MATRIX A, LIS_INT fill, double info[6]);
  * LISHIP_SWEEP_SMALL_LEVEL rows), rows factorised by a workgroup (L + U terms >= LISHIP_SWEEP_LONG_ROW) in those levels, such rows in
  * runs of small levels, 1 when a row of A stores a column twice and such rows are factorised by one thread} (tests/test_ilu_gpu.py) */
 LIS_INT lis_amd_ilu_factor_info(LIS_MATRIX A, LIS_INT fill, LIS_INT info[6]);
+/* ---- block Jacobi (-p bjacobi; A in BSR storage with square blocks -- as given, or through -storage bsr -storage_block k --, one rank).  lis_precon_create
+ * leaves A BSR and split and precon->WD = the inverted diagonal blocks (bn x bn, column-major, the last block padded with 1.0 on its diagonal).
+ * 1 when the last lis_solve applied block Jacobi: bn = its block size, nr = its blocks.  0 otherwise, with bn = nr = 0; *fell_back = 1 when that solve asked for
+ * -p bjacobi on a matrix without blocks and ran -p jacobi instead, as the reference does */
+LIS_INT lis_amd_last_solve_bjacobi(LIS_INT *bn, LIS_INT *nr, LIS_INT *fell_back);
+/* the inverted blocks of a split BSR matrix out of HBM (made there if need be): out takes A->nr * bn * bn doubles */
+LIS_INT lis_amd_bjacobi_copy(LIS_MATRIX A, LIS_SCALAR *out);
+/* X = M^-1 B (transposed != 0: M^-H B, every block transposed) on a split BSR matrix; X must not be B */
+LIS_INT lis_amd_bjacobi_psolve(LIS_MATRIX A, LIS_INT transposed, LIS_VECTOR B, LIS_VECTOR X);
+/* reps inversions of a copy of A's diagonal blocks, reps psolves X = M^-1 B and reps Jacobi psolves X = B .* d of the same length, each timed by device events
+ * into inverse_ms[k] / psolve_ms[k] / jacobi_ms[k] (tools/bjacobi_probe.py) */
+LIS_INT lis_amd_bjacobi_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *inverse_ms, double *psolve_ms, double *jacobi_ms);
 
 /* vectors */
 LIS_INT lis_amd_vector_sync_host(LIS_VECTOR v);        /* make v->value[] current (D2H if needed)        */

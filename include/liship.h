@@ -582,6 +582,15 @@ typedef struct {
 } liship_ilu_t;
 int  liship_ilu_factor_f64(const liship_ilu_t *ilu, const liship_sweep_t *schedule, void *stream);
 
+/* ------------------------------------------------------------------ block diagonal (kernels/bdiag.hip, -p bjacobi)
+ * d: nr = ceil(n / bn) blocks of bn x bn doubles, block b at d[b*bn*bn], entry (i, j) at i + j*bn (LIS_MATRIX_DIAG).
+ * inverse: every block replaced by its inverse, by the reference's lis_array_ge (LU without pivoting, no pivot check: 1 / 0 = inf goes on), after the
+ * last block got 1.0 on the diagonal of its padding when bn does not divide n.  bn <= 8: work is not read; larger: work holds nr*bn*bn doubles.
+ * matvec: y[0 .. n) = D x, or D^T x block by block (transposed != 0), each row summed left to right, from the first product for bn <= 4 (transposed:
+ * bn <= 3) and from +0.0 for larger blocks, as the reference's routines do; x is read as +0.0 from n on; y must not be x. */
+int  liship_bdiag_inverse_f64(int n, int nr, int bn, double *d, double *work, void *stream);
+int  liship_bdiag_matvec_f64(int n, int nr, int bn, int transposed, const double *d, const double *x, double *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,8 @@ _LISHIP = {
     "liship_poisson3d_nnz": (C.c_longlong, [_ci, _ci, _ci, _ci, _ci]),
     "liship_poisson3d_csr": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "liship_poisson3d_rhs": (_ci, [_ci, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "liship_bdiag_inverse_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp]),
+    "liship_bdiag_matvec_f64": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
 }
 
 

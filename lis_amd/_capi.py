@@ -215,7 +215,7 @@ _PROTOS = {
 }
 
 
-# the SSOR and ILU(k) extensions of include/lis_amd.h: set where the library has them (liblis_amd.so), absent from the reference build
+# the SSOR, ILU(k) and block Jacobi extensions of include/lis_amd.h: set where the library has them (liblis_amd.so), absent from the reference build
 _AMD_PROTOS = {
     "lis_amd_last_solve_ssor": (LIS_INT, [P_INT, P_INT, P_INT, P_INT]),
     "lis_amd_ssor_schedule_info": (LIS_INT, [PM, P_DBL]),
@@ -228,6 +228,10 @@ _AMD_PROTOS = {
     "lis_amd_ilu_times": (LIS_INT, [PM, LIS_INT, PV, PV, LIS_INT, P_DBL, P_DBL]),
     "lis_amd_ilu_info": (LIS_INT, [PM, LIS_INT, P_DBL]),
     "lis_amd_ilu_factor_info": (LIS_INT, [PM, LIS_INT, P_INT]),
+    "lis_amd_last_solve_bjacobi": (LIS_INT, [P_INT, P_INT, P_INT]),
+    "lis_amd_bjacobi_copy": (LIS_INT, [PM, P_DBL]),
+    "lis_amd_bjacobi_psolve": (LIS_INT, [PM, LIS_INT, PV, PV]),
+    "lis_amd_bjacobi_times": (LIS_INT, [PM, PV, PV, LIS_INT, P_DBL, P_DBL, P_DBL]),
 }
 
 

@@ -1036,6 +1036,7 @@ void lisd_mat_free(LIS_MATRIX A)
 	(void)liship_free(d->sx); (void)liship_free(d->sy);
 	lisd_ssor_free(d->ssor);
 	lisd_ilu_free(d->ilu);
+	lisd_bjacobi_free(d->bjacobi);
 	memset(d, 0, sizeof(*d));
 	lisp_matrix_release(A, 0);         /* no copy left that a host write could leave stale: the watched arrays are plain memory again */
 }
@@ -1540,8 +1541,9 @@ LIS_INT lisd_spmv_dot_launch_to(LIS_MATRIX A, double *dx, double *dy, const doub
 		if (rc != LISHIP_ERR_ARG) HIPCHK(rc);
 		HIPCHK(liship_spmv_bsr_nnz_f64(d->nr, A->bnnz, d->bnr, d->bnc, d->bptr, d->bindex, d->value, dx, dy, lisg.stream));
 	} else LISCHK(lisd_spmv(A, dx, dy));
-	if (want_sumsq) HIPCHK(liship_dot2_f64(d->n, dy, dw, result, lisg.reduce_work, lisg.stream));
-	else HIPCHK(liship_dot_f64(d->n, dw, dy, result, lisg.reduce_work, lisg.stream));
+	/* over A's n rows: the row form of a split BSR matrix (d->n) counts the padding rows of its last block row too, which would move the chunk borders of the reference-order sums */
+	if (want_sumsq) HIPCHK(liship_dot2_f64(A->n, dy, dw, result, lisg.reduce_work, lisg.stream));
+	else HIPCHK(liship_dot_f64(A->n, dw, dy, result, lisg.reduce_work, lisg.stream));
 	return LIS_SUCCESS;
 }
 

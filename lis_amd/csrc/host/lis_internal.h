@@ -98,6 +98,7 @@ typedef struct {
 	liship_csr_plan_t u_plan;
 	void *ssor;                /* SSOR schedules of the split parts + WD in HBM (lis_ssor.c), dropped with the copy */
 	void *ilu;                 /* ILU(k): symbolic pattern, schedule, sweep layouts and factor in HBM (lis_ilu.c), dropped with the copy */
+	void *bjacobi;             /* block Jacobi: the inverted diagonal blocks of a split BSR matrix in HBM (lis_bjacobi.c), dropped with the copy */
 } lisd_mat;
 
 typedef struct {
@@ -105,6 +106,13 @@ typedef struct {
 	lisd_mat dev;
 } lisi_matrix;
 #define MDEV(A) (&((lisi_matrix *)(A))->dev)
+
+/* ---- preconditioners ---------------------------------------------------------------------------- */
+typedef struct {
+	struct LIS_PRECON_STRUCT pub;
+	int from_bjacobi;          /* made for -p bjacobi: a Jacobi preconditioner with this set is the fallback for a matrix without blocks (lis_amd_last_solve_bjacobi) */
+} lisi_precon;
+#define PPRIV(p) ((lisi_precon *)(p))
 
 /* ---- global runtime state ------------------------------------------------------------------------ */
 typedef struct {
@@ -154,6 +162,7 @@ typedef struct {
 	int no_direct_halo;        /* LIS_AMD_NO_DIRECT_HALO=1: boundary rows that form a run are packed like any other list instead of being sent straight from x (A/B) */
 	lis_amd_comm_callbacks cb;
 	int last_ilu, last_ilu_fill, last_ilu_blocks, last_ilu_levels, last_ilu_launches;                  /* lis_amd_last_solve_ilu */
+	int last_bjacobi, last_bjacobi_bn, last_bjacobi_nr, last_bjacobi_fallback;                         /* lis_amd_last_solve_bjacobi */
 	int last_ssor, last_ssor_blocks, last_ssor_levels_fwd, last_ssor_levels_bwd, last_ssor_launches;   /* lis_amd_last_solve_ssor */
 } lisi_globals;
 extern lisi_globals lisg;
@@ -280,6 +289,12 @@ void    lisd_ssor_free(void *ssor);                                          /* 
 LIS_INT lisd_ssor_begin(LIS_MATRIX A, int *T);                              /* schedules + WD in HBM for a solve; *T = its block count */
 LIS_INT lisd_ssor_psolve(LIS_MATRIX A, int T, const double *b, double *x);  /* x = M^-1 b  (b may be x) */
 LIS_INT lisd_ssor_psolveh(LIS_MATRIX A, int T, const double *b, double *x); /* x = M^-H b  (b may be x) */
+/* ---- block Jacobi (lis_bjacobi.c) */
+LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon);          /* refusals, -storage, then Jacobi (precon_type changed) or split + WD inverted on the device */
+void    lisi_bjacobi_wd_free(LIS_PRECON precon);
+void    lisd_bjacobi_free(void *bjacobi);                                    /* (lisd_mat_free) */
+LIS_INT lisd_bjacobi_begin(LIS_MATRIX A);                                   /* the inverse of A's diagonal blocks for a solve (made now if the HBM copy was rebuilt since create) */
+LIS_INT lisd_bjacobi_psolve(LIS_MATRIX A, int transposed, const double *b, double *x);   /* x = M^-1 b, or M^-H b  (b must not be x) */
 #define LISI_CHECK_NULL 0
 #define LISI_CHECK_SIZE 1
 #define LISI_CHECK_ASSEMBLED 2

@@ -19,6 +19,7 @@ typedef struct {
 	int duniform; double dconst;   /* every dinv[i] is the double dconst (a constant diagonal): the fused CG passes take the scalar */
 	int sweeps, sweeps_T;    /* the preconditioner is a pair of triangular sweeps (SSOR: lis_ssor.c, ILU: lis_ilu.c) with sweeps_T row blocks: only the loops that call d_psolve / d_psolveh */
 	int ilu, ilu_fill;       /* ... and it is ILU(ilu_fill), else SSOR */
+	int bjacobi;             /* the preconditioner is the inverted block diagonal of a BSR matrix (lis_bjacobi.c): like the sweeps, only the loops that call d_psolve / d_psolveh */
 	double **work; int nwork;
 	double bnrm, tol;
 	int output, maxiter;
@@ -43,18 +44,23 @@ static inline void work_free(ctx_t *c)
 #define K(call) HIPCHK(call)
 static inline LIS_INT d_copy(ctx_t *c, const double *src, double *dst) { K(liship_memcpy_d2d(dst, src, sizeof(double) * (size_t)c->n, lisg.stream)); return LIS_SUCCESS; }
 static inline LIS_INT d_psolve(ctx_t *c, const double *r, double *z)
-{	/* none: copy (lis_precon.c:365-384); Jacobi: z = r .* dinv (lis_precon_jacobi.c:121-124); SSOR: the two sweeps (lis_precon_ssor.c:99-116); ILU: L, then U and D (lis_precon_iluk.c:880-934) */
+{	/* none: copy (lis_precon.c:365-384); Jacobi: z = r .* dinv (lis_precon_jacobi.c:121-124); SSOR: the two sweeps (lis_precon_ssor.c:99-116); ILU: L, then U and D (lis_precon_iluk.c:880-934);
+	 * block Jacobi: z = WD r (lis_precon_jacobi.c:255-272) */
+	if (c->bjacobi) return lisd_bjacobi_psolve(c->A, 0, r, z);
 	if (c->ilu) return lisd_ilu_psolve(c->A, c->ilu_fill, c->sweeps_T, r, z);
 	if (c->sweeps) return lisd_ssor_psolve(c->A, c->sweeps_T, r, z);
 	if (c->dinv) { K(liship_pmul_f64(c->n, r, c->dinv, z, lisg.stream)); return LIS_SUCCESS; }
 	return d_copy(c, r, z);
 }
 static inline LIS_INT d_psolveh(ctx_t *c, const double *r, double *z)
-{	/* M^-H (lis_psolveh): M^-1 itself for none / Jacobi; SSOR / ILU: the transposed sweeps (lis_precon_ssor.c:119-136, lis_precon_iluk.c:1086-1140) */
+{	/* M^-H (lis_psolveh): M^-1 itself for none / Jacobi; SSOR / ILU: the transposed sweeps (lis_precon_ssor.c:119-136, lis_precon_iluk.c:1086-1140); block Jacobi: the transposed blocks (:276-293) */
+	if (c->bjacobi) return lisd_bjacobi_psolve(c->A, 1, r, z);
 	if (c->ilu) return lisd_ilu_psolveh(c->A, c->ilu_fill, c->sweeps_T, r, z);
 	if (c->sweeps) return lisd_ssor_psolveh(c->A, c->sweeps_T, r, z);
 	return d_psolve(c, r, z);
 }
+/* the preconditioner is no point diagonal: the fused and device-driven loops (which fold z = r .* dinv into their passes) do not apply */
+static inline int precon_by_calls(const ctx_t *c) { return c->sweeps || c->bjacobi; }
 static inline LIS_INT d_matvec(ctx_t *c, double *x, double *y) { return lisd_spmv(c->A, x, y); }
 static inline LIS_INT d_resid(ctx_t *c, const double *r, double *nrm)
 {	/* lis_solver_get_residual_nrm2_r (lis_solver.c:1792) / _nrm1_b (:1804) */

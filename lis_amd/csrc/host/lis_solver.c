@@ -220,18 +220,23 @@ LIS_INT lis_solver_set_optionC(LIS_SOLVER solver)
 	return set_from_tokens(lisi_cmd_argv, lisi_cmd_argc, solver);
 }
 
-/* ------------------------------------------------------------------ preconditioner (none, Jacobi, ILU(k), SSOR) */
+/* ------------------------------------------------------------------ preconditioner (none, Jacobi, ILU(k), SSOR, block Jacobi) */
 LIS_INT lis_precon_create(LIS_SOLVER solver, LIS_PRECON *precon)
 {
 	const LIS_INT type = solver->options[LIS_OPTIONS_PRECON];
 	*precon = NULL;
-	if (type != LIS_PRECON_TYPE_NONE && type != LIS_PRECON_TYPE_JACOBI && type != LIS_PRECON_TYPE_SSOR && type != LIS_PRECON_TYPE_ILU)
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ilu, ssor)\n", type);
-	LIS_PRECON p = (LIS_PRECON)calloc(1, sizeof(struct LIS_PRECON_STRUCT));
-	if (!p) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(struct LIS_PRECON_STRUCT));
+	if (type != LIS_PRECON_TYPE_NONE && type != LIS_PRECON_TYPE_JACOBI && type != LIS_PRECON_TYPE_SSOR && type != LIS_PRECON_TYPE_ILU && type != LIS_PRECON_TYPE_BJACOBI)
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ilu, ssor, bjacobi)\n", type);
+	LIS_PRECON p = (LIS_PRECON)calloc(1, sizeof(lisi_precon));
+	if (!p) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(lisi_precon));
 	p->precon_type = type;
 	lisi_register(p, LISI_KIND_PRECON);
-	if (type == LIS_PRECON_TYPE_JACOBI) {      /* D = 1 / diag(A): ref lis_precon_jacobi.c:61-85 */
+	if (type == LIS_PRECON_TYPE_BJACOBI) {     /* -storage, then split A + WD = D^-1 block by block; a matrix without blocks turns p into a Jacobi preconditioner: lis_bjacobi.c */
+		PPRIV(p)->from_bjacobi = 1;
+		LIS_INT err = lisi_bjacobi_create(solver, p);
+		if (err) { lis_precon_destroy(p); return err; }
+	}
+	if (p->precon_type == LIS_PRECON_TYPE_JACOBI) {      /* D = 1 / diag(A): ref lis_precon_jacobi.c:61-85 */
 		LIS_INT err = lis_vector_duplicate(solver->A, &p->D);
 		if (!err) err = lis_matrix_get_diagonal(solver->A, p->D);
 		if (!err) err = lis_vector_reciprocal(p->D);
@@ -253,6 +258,7 @@ LIS_INT lis_precon_destroy(LIS_PRECON precon)
 {
 	if (precon && lisi_is_registered(precon)) {
 		if (precon->D) lis_vector_destroy(precon->D);
+		lisi_bjacobi_wd_free(precon);
 		lisi_unregister(precon);
 		free(precon);
 	}
@@ -537,7 +543,7 @@ static LIS_INT run_cg_unfused(ctx_t *c);
 static LIS_INT run_cg_device(ctx_t *c);
 static LIS_INT run_cg(ctx_t *c)
 {
-	if (lisg.no_fusion || c->sweeps) return run_cg_unfused(c);
+	if (lisg.no_fusion || precon_by_calls(c)) return run_cg_unfused(c);
 	if (device_scalars_ok(c)) return run_cg_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -622,7 +628,7 @@ static LIS_INT run_bicgstab_unfused(ctx_t *c);
 static LIS_INT run_bicgstab_device(ctx_t *c);
 static LIS_INT run_bicgstab(ctx_t *c)
 {
-	if (lisg.no_fusion || c->sweeps) return run_bicgstab_unfused(c);
+	if (lisg.no_fusion || precon_by_calls(c)) return run_bicgstab_unfused(c);
 	if (device_scalars_ok(c)) return run_bicgstab_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -739,7 +745,7 @@ static LIS_INT run_bicg_device(ctx_t *c);
 static LIS_INT run_bicg_unfused(ctx_t *c);
 static LIS_INT run_bicg(ctx_t *c)
 {
-	if (c->sweeps) return run_bicg_unfused(c);
+	if (precon_by_calls(c)) return run_bicg_unfused(c);
 	if (!lisg.no_fusion && device_scalars_ok(c)) return run_bicg_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -926,7 +932,7 @@ static LIS_INT run_gmres(ctx_t *c)
 			double *hc = h + (size_t)ii * ld;
 			/* M^-1 v: without a preconditioner the reference copies (lis_precon.c:365-384); the product reads v itself */
 			double *zin = z;
-			if (c->dinv || c->sweeps || lisg.no_fusion) TRY(d_psolve(c, v[ii], z)); else zin = v[ii];
+			if (c->dinv || precon_by_calls(c) || lisg.no_fusion) TRY(d_psolve(c, v[ii], z)); else zin = v[ii];
 			if (!chained) TRY(d_matvec(c, zin, v[i1]));
 			if (chained) {
 				/* modified Gram-Schmidt with the coefficients kept in HBM: step k reads h[k-1] from the previous
@@ -995,7 +1001,7 @@ static LIS_INT run_gmres(ctx_t *c)
 			KTRY(liship_scale_to_f64(n, g[0], v[0], z, lisg.stream));     /* z = y0 v0  (:290-296) */
 			for (int j = 1; j <= ii; j++) KTRY(liship_axpy_f64(n, g[j], v[j], z, lisg.stream));
 		}
-		if (c->dinv || c->sweeps || lisg.no_fusion) {
+		if (c->dinv || precon_by_calls(c) || lisg.no_fusion) {
 			TRY(d_psolve(c, z, r));
 			KTRY(liship_axpy_f64(n, 1.0, r, c->x, lisg.stream));
 		} else KTRY(liship_axpy_f64(n, 1.0, z, c->x, lisg.stream));      /* the copy of psolve_none left out: same addend */
@@ -1059,8 +1065,9 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	LIS_INT err = 0;
 	ctx_t c;
 	memset(&c, 0, sizeof(c));
-	/* SSOR and ILU depend on the numbering (their sweeps follow the rows' order): such a solve never runs renumbered, nor builds the renumbered form */
+	/* SSOR, ILU and block Jacobi depend on the numbering (the sweeps follow the rows' order, the blocks the caller's rows): such a solve never runs renumbered, nor builds the renumbered form */
 	const int ilu = precon && precon->precon_type == LIS_PRECON_TYPE_ILU;
+	const int bjacobi = precon && precon->precon_type == LIS_PRECON_TYPE_BJACOBI;
 	const int sweeps = precon && (precon->precon_type == LIS_PRECON_TYPE_SSOR || ilu);
 	int renumbered = 0;                        /* the solve runs in the numbering of a reordered plan (below) */
 	const int *renum = NULL;
@@ -1177,8 +1184,8 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 		const int t_ok = !needs_t || (Awork->matrix_type == LIS_MATRIX_CSR && !Awork->is_splited);
 		const int multi = lisg.nprocs > 1 && Awork->commtable;
 		/* the renumbered form is built LAZILY: by the first solve that finds the plan has served lisg.reorder_after products (lis_device.c) */
-		if (!sweeps && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok) { if ((err = lisd_mat_lazy_reorder(Awork))) goto out; }
-		if (!sweeps && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok && dm->type == LIS_MATRIX_CSR && !dm->split_jad &&
+		if (!sweeps && !bjacobi && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok) { if ((err = lisd_mat_lazy_reorder(Awork))) goto out; }
+		if (!sweeps && !bjacobi && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok && dm->type == LIS_MATRIX_CSR && !dm->split_jad &&
 		    dm->plan && (Awork->np == Awork->n || (multi && Awork->matrix_type == LIS_MATRIX_CSR)) && dm->n == Awork->n && liship_csr_plan_reordered_form(dm->plan, &in, &rp, &ri, &rv, &renum) == 0) {
 			if (multi && (err = lisc_halo_renumbered(Awork, renum, liship_csr_plan_reordered_inner_rows(dm->plan)))) goto out;
 			held_plan = dm->plan; held_ptr = dm->ptr; held_index = dm->index; held_value = dm->value;
@@ -1212,6 +1219,12 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	lisg.last_renumbered = renumbered;
 	lisg.last_ssor = 0;
 	lisg.last_ilu = 0;
+	lisg.last_bjacobi = 0;
+	lisg.last_bjacobi_fallback = precon && lisi_is_registered(precon) && PPRIV(precon)->from_bjacobi && precon->precon_type == LIS_PRECON_TYPE_JACOBI;
+	if (bjacobi) {
+		c.bjacobi = 1;
+		if ((err = lisd_bjacobi_begin(Awork))) goto out;
+	}
 	if (ilu) {
 		c.sweeps = 1; c.ilu = 1; c.ilu_fill = (int)solver->options[LIS_OPTIONS_FILL];
 		if ((err = lisd_ilu_begin(Awork, c.ilu_fill, &c.sweeps_T))) goto out;

@@ -998,7 +998,7 @@ LIS_INT lisk_jacobi(ctx_t *c)
 	const double tol = s->params[LIS_PARAMS_RESID - LIS_OPTIONS_LEN];
 	double nrm2 = 0.0, bnrm2;
 	lisd_mat *dm = MDEV(c->A);
-	if (c->dinv || c->sweeps) { err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver with a preconditioner (system rescaling) is not served by liblis_amd\n"); goto done; }
+	if (c->dinv || precon_by_calls(c)) { err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver with a preconditioner (system rescaling) is not served by liblis_amd\n"); goto done; }
 	if (dm->type != LIS_MATRIX_CSR) { err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver is served for CSR / CSC storage only\n"); goto done; }
 	TRY(work_alloc(c, 4));
 	double *r = c->work[0], *t = c->work[1], *sx = c->work[2], *d = c->work[3];
