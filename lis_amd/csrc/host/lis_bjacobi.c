@@ -3,7 +3,7 @@
  *
  * create (ref :221-251): -storage conversion of the caller's A (lis_matrix_convert_self, lis_matrix_ops.c:326-368: only when -storage
  * names another type than A has; a BSR matrix keeps its blocks whatever -storage_block says).  A that is no BSR matrix after that:
- * the solver's option and the preconditioner become Jacobi, and lis_precon_create goes on as for -p jacobi.  A BSR matrix:
+ * the solver's option and the preconditioner become Jacobi, and lis_precon_create goes on with the Jacobi row's create.  A BSR matrix:
  * lis_matrix_split(A) -- A STAYS split, every later lis_matvec adds D, L, U in that order --, WD = D with 1.0 on the diagonal of the
  * last block's padding when bn does not divide n (lis_matrix_diag.c:787-794), every block inverted by lis_array_ge's statement.
  *   psolve  = lis_matrix_diag_matvec(WD, B, X)    (lis_matrix_diag.c:810-895)
@@ -90,6 +90,7 @@ LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon)
 {
 	LIS_MATRIX A = solver->A;
 	const LIS_INT storage = solver->options[LIS_OPTIONS_STORAGE], block = solver->options[LIS_OPTIONS_STORAGE_BLOCK];
+	PPRIV(precon)->from_bjacobi = 1;             /* (stays set when the type below becomes Jacobi: the fallback's mark) */
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisd_init());                         /* no device: the no-device code, before anything that could succeed */
 	const LIS_INT result = storage ? storage : A->matrix_type;       /* what A is after lis_matrix_convert_self */
@@ -131,20 +132,22 @@ LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon)
 	return LIS_SUCCESS;
 }
 
-/* ------------------------------------------------------------------ the solve's side (lis_krylov.h d_psolve / d_psolveh) */
-LIS_INT lisd_bjacobi_begin(LIS_MATRIX A)
+/* ------------------------------------------------------------------ the solve's side (the block Jacobi row of lisi_precon_kinds) */
+LIS_INT lisd_bjacobi_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st)
 {	/* checked and resolved once per solve */
 	lisd_bjacobi *bj;
+	(void)solver;
+	st->A = A; st->n = A->n;
 	LISCHK(get_inverse(A, &bj));                 /* (made now if the HBM copy was rebuilt since lis_precon_create) */
 	lisg.last_bjacobi = 1; lisg.last_bjacobi_bn = bj->bn; lisg.last_bjacobi_nr = bj->nr;
 	return LIS_SUCCESS;
 }
 
-LIS_INT lisd_bjacobi_psolve(LIS_MATRIX A, int transposed, const double *b, double *x)
-{	/* per iteration: what lisd_bjacobi_begin resolved, read off the HBM copy with no checks between the loop's launches; only a copy that a
-	 * product rebuilt in mid-solve (a host write seen by the page watch) has lost it, and then it is made again instead of applied stale */
-	lisd_bjacobi *bj = (lisd_bjacobi *)MDEV(A)->bjacobi;
-	if (!bj) LISCHK(get_inverse(A, &bj));
+LIS_INT lisd_bjacobi_apply(const lisi_precon_state *st, int transposed, const double *b, double *x)
+{	/* x = M^-1 b, or M^-H b (b must NOT be x).  Per iteration: what begin resolved, read off the HBM copy with no checks between the loop's launches;
+	 * only a copy that a product rebuilt in mid-solve (a host write seen by the page watch) has lost it, and then it is made again instead of applied stale */
+	lisd_bjacobi *bj = (lisd_bjacobi *)MDEV(st->A)->bjacobi;
+	if (!bj) LISCHK(get_inverse(st->A, &bj));
 	return apply(bj, transposed, b, x);
 }
 

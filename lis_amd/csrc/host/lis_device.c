@@ -1034,9 +1034,7 @@ void lisd_mat_free(LIS_MATRIX A)
 	(void)liship_free(d->bptr); (void)liship_free(d->bindex); (void)liship_free(d->value);
 	(void)liship_free(d->export_index); (void)liship_free(d->ws); free(d->export_run);
 	(void)liship_free(d->sx); (void)liship_free(d->sy);
-	lisd_ssor_free(d->ssor);
-	lisd_ilu_free(d->ilu);
-	lisd_bjacobi_free(d->bjacobi);
+	lisi_precon_release(d, NULL, NULL);   /* what the preconditioners cached on this copy */
 	memset(d, 0, sizeof(*d));
 	lisp_matrix_release(A, 0);         /* no copy left that a host write could leave stale: the watched arrays are plain memory again */
 }

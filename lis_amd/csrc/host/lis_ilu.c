@@ -25,7 +25,6 @@
 #include <stdio.h>
 #include "lis_krylov.h"
 
-
 typedef struct {
 	int used, fill, T, n;
 	int lnnz, unnz;
@@ -339,56 +338,44 @@ LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon)
 	return LIS_SUCCESS;
 }
 
-/* ------------------------------------------------------------------ the solve's side (lis_krylov.h d_psolve / d_psolveh) */
-LIS_INT lisd_ilu_begin(LIS_MATRIX A, int fill, int *T)
+/* ------------------------------------------------------------------ the solve's side (the ILU row of lisi_precon_kinds) */
+LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st)
 {
 	ilu_entry *e;
 	const liship_sweep_t *f, *b;
-	*T = lisi_sweep_blocks();
-	LISCHK(check_served(A, fill));
-	LISCHK(get_entry(A, fill, *T, &e));
+	st->A = A; st->n = A->n; st->fill = (int)solver->options[LIS_OPTIONS_FILL]; st->T = lisi_sweep_blocks();
+	LISCHK(check_served(A, st->fill));
+	LISCHK(get_entry(A, st->fill, st->T, &e));
 	LISCHK(get_sweep(e, SW_L, &f));
 	LISCHK(get_sweep(e, SW_U, &b));
 	if (!e->factored) LISCHK(factorise(A, e));   /* (the HBM copy was rebuilt since lis_precon_create) */
-	lisg.last_ilu = 1; lisg.last_ilu_fill = fill; lisg.last_ilu_blocks = *T;
+	lisg.last_ilu = 1; lisg.last_ilu_fill = st->fill; lisg.last_ilu_blocks = st->T;
 	lisg.last_ilu_levels = f->nlev; lisg.last_ilu_launches = f->ngroups + b->ngroups;
 	return LIS_SUCCESS;
 }
 
-static LIS_INT psolve_on(ilu_entry *e, const double *b, double *x)
+/* x = M^-1 b: forward on L, backward on U and D; x = M^-H b: forward on U^T with D first, backward on L^T */
+static LIS_INT apply_on(ilu_entry *e, int transposed, const double *b, double *x)
 {
-	const liship_sweep_t *l, *u;
-	LISCHK(get_sweep(e, SW_L, &l));
-	LISCHK(get_sweep(e, SW_U, &u));
-	HIPCHK(liship_sweep_plain_f64(l, b, x, lisg.stream));
-	HIPCHK(liship_sweep_f64(u, LISHIP_SWEEP_MUL, x, x, e->d_d, lisg.stream));
+	const liship_sweep_t *first, *second;
+	LISCHK(get_sweep(e, transposed ? SW_UT : SW_L, &first));
+	LISCHK(get_sweep(e, transposed ? SW_LT : SW_U, &second));
+	if (!transposed) {
+		HIPCHK(liship_sweep_plain_f64(first, b, x, lisg.stream));
+		HIPCHK(liship_sweep_f64(second, LISHIP_SWEEP_MUL, x, x, e->d_d, lisg.stream));
+	} else {
+		HIPCHK(liship_sweep_f64(first, LISHIP_SWEEP_MUL, b, x, e->d_d, lisg.stream));
+		HIPCHK(liship_sweep_plain_f64(second, x, x, lisg.stream));
+	}
 	return LIS_SUCCESS;
 }
 
-static LIS_INT psolveh_on(ilu_entry *e, const double *b, double *x)
-{
-	const liship_sweep_t *ut, *lt;
-	LISCHK(get_sweep(e, SW_UT, &ut));
-	LISCHK(get_sweep(e, SW_LT, &lt));
-	HIPCHK(liship_sweep_f64(ut, LISHIP_SWEEP_MUL, b, x, e->d_d, lisg.stream));
-	HIPCHK(liship_sweep_plain_f64(lt, x, x, lisg.stream));
-	return LIS_SUCCESS;
-}
-
-LIS_INT lisd_ilu_psolve(LIS_MATRIX A, int fill, int T, const double *b, double *x)
-{
+LIS_INT lisd_ilu_apply(const lisi_precon_state *st, int transposed, const double *b, double *x)
+{	/* x = M^-1 b, or M^-H b (b may be x): get_entry finds the entry begin left, or makes it again on a copy that a product rebuilt in mid-solve */
 	ilu_entry *e;
-	LISCHK(get_entry(A, fill, T, &e));
-	if (!e->factored) LISCHK(factorise(A, e));
-	return psolve_on(e, b, x);
-}
-
-LIS_INT lisd_ilu_psolveh(LIS_MATRIX A, int fill, int T, const double *b, double *x)
-{
-	ilu_entry *e;
-	LISCHK(get_entry(A, fill, T, &e));
-	if (!e->factored) LISCHK(factorise(A, e));
-	return psolveh_on(e, b, x);
+	LISCHK(get_entry(st->A, st->fill, st->T, &e));
+	if (!e->factored) LISCHK(factorise(st->A, e));
+	return apply_on(e, transposed, b, x);
 }
 
 /* ------------------------------------------------------------------ introspection and tools (include/lis_amd.h) */
@@ -447,13 +434,13 @@ LIS_INT lis_amd_ilu_psolve(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR 
 	LISCHK(lisd_vec_in(B, &db));
 	if (X == B) dx = db;
 	else LISCHK(lisd_vec_out(X, &dx));
-	LISCHK(transposed ? psolveh_on(e, db, dx) : psolve_on(e, db, dx));
+	LISCHK(apply_on(e, transposed != 0, db, dx));
 	return lisd_vec_done(X);
 }
 
 typedef struct { LIS_MATRIX A; ilu_entry *e; const double *b; double *x; } timed_args;
 static LIS_INT factorise_once(void *ctx) { const timed_args *t = (const timed_args *)ctx; return factorise(t->A, t->e); }
-static LIS_INT psolve_once(void *ctx) { const timed_args *t = (const timed_args *)ctx; return psolve_on(t->e, t->b, t->x); }
+static LIS_INT psolve_once(void *ctx) { const timed_args *t = (const timed_args *)ctx; return apply_on(t->e, 0, t->b, t->x); }
 
 LIS_INT lis_amd_ilu_times(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *factor_ms, double *psolve_ms)
 {	/* reps factorisations and reps psolves X = M^-1 B on the library's stream, each timed by device events */

@@ -114,6 +114,38 @@ typedef struct {
 } lisi_precon;
 #define PPRIV(p) ((lisi_precon *)(p))
 
+/* what one solve's psolves read, resolved once by the kind's begin and held in the solve context (lis_krylov.h ctx_t) */
+typedef struct {
+	LIS_MATRIX A;
+	int n;
+	int fill, T;               /* ILU: the fill level; SSOR / ILU: the row blocks of the sweeps */
+	double *dinv;              /* Jacobi: 1/diag in HBM, in the numbering the solve runs in */
+} lisi_precon_state;
+
+/* One row per served LIS_PRECON_TYPE_*; a pointer that may be NULL is a step the kind does not have.
+ *   create   what lis_precon_create runs on the registered precon; it may change precon->precon_type (-p bjacobi on a matrix without
+ *            blocks becomes Jacobi), and lis_precon_create then runs the new type's create
+ *   begin    once per solve (lis_solve_kernel): fills the state, makes what a rebuilt HBM copy lost, records lisg.last_*
+ *   apply    z = M^-1 r, or M^-H r (transposed).  none: a copy; Jacobi: liship_pmul_f64; SSOR, ILU: the sweeps, r may be z;
+ *            block Jacobi: r must NOT be z.  Nothing is looked up or checked per call beyond what the kind's file says
+ *   by_calls no point diagonal: the fused and device-driven loops (which fold z = r .* dinv into their passes) do not apply, and
+ *            the solve never runs renumbered (the sweeps follow the rows' order, the blocks the caller's rows)
+ *   the frees: the cache on the HBM copy (the slot of lisd_mat at cache_slot), what the matrix and what the precon own on the host */
+typedef struct {
+	LIS_INT type;
+	int by_calls;
+	LIS_INT (*create)(LIS_SOLVER solver, LIS_PRECON precon);
+	LIS_INT (*begin)(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);
+	LIS_INT (*apply)(const lisi_precon_state *st, int transposed, const double *r, double *z);
+	size_t cache_slot; void (*cache_free)(void *cache);
+	void (*matrix_free)(LIS_MATRIX A);
+	void (*precon_free)(LIS_PRECON precon);
+} lisi_precon_kind;
+#define LISI_PRECON_KINDS 5                                                    /* none, jacobi, ilu, ssor, bjacobi */
+extern const lisi_precon_kind lisi_precon_kinds[LISI_PRECON_KINDS];           /* lis_solver.c */
+const lisi_precon_kind *lisi_precon_kind_of(LIS_INT type);                    /* NULL: not served */
+void lisi_precon_release(lisd_mat *d, LIS_MATRIX A, LIS_PRECON precon);       /* every kind's frees for the arguments that are not NULL */
+
 /* ---- global runtime state ------------------------------------------------------------------------ */
 typedef struct {
 	int initialized;
@@ -278,23 +310,21 @@ void    lisi_sweep_census(const liship_sweep_t *s, LIS_INT census[5]);       /* 
 LIS_INT lisi_sweep_times(LIS_INT reps, LIS_INT (*apply)(void *ctx), void *ctx, double *ms);   /* reps event-timed calls of apply: ms[k] */
 /* ---- ILU(k) (lis_ilu.c) */
 LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon);              /* refusals, symbolic step (cached), factorisation on the device */
-void    lisd_ilu_free(void *ilu);                                            /* (lisd_mat_free) */
-LIS_INT lisd_ilu_begin(LIS_MATRIX A, int fill, int *T);                     /* the factor of A for a solve (made now if the HBM copy was rebuilt since create) */
-LIS_INT lisd_ilu_psolve(LIS_MATRIX A, int fill, int T, const double *b, double *x);   /* x = M^-1 b  (b may be x) */
-LIS_INT lisd_ilu_psolveh(LIS_MATRIX A, int fill, int T, const double *b, double *x);  /* x = M^-H b  (b may be x) */
+void    lisd_ilu_free(void *ilu);
+LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);    /* the factor of A for a solve (made now if the HBM copy was rebuilt since create) */
+LIS_INT lisd_ilu_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
 /* ---- SSOR (lis_ssor.c) */
 LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon);             /* -storage csr, split, WD = 1 / (omega D) unless already built */
 void    lisi_ssor_wd_free(LIS_MATRIX A);
-void    lisd_ssor_free(void *ssor);                                          /* (lisd_mat_free) */
-LIS_INT lisd_ssor_begin(LIS_MATRIX A, int *T);                              /* schedules + WD in HBM for a solve; *T = its block count */
-LIS_INT lisd_ssor_psolve(LIS_MATRIX A, int T, const double *b, double *x);  /* x = M^-1 b  (b may be x) */
-LIS_INT lisd_ssor_psolveh(LIS_MATRIX A, int T, const double *b, double *x); /* x = M^-H b  (b may be x) */
+void    lisd_ssor_free(void *ssor);
+LIS_INT lisd_ssor_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);   /* schedules + WD in HBM for a solve */
+LIS_INT lisd_ssor_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
 /* ---- block Jacobi (lis_bjacobi.c) */
 LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon);          /* refusals, -storage, then Jacobi (precon_type changed) or split + WD inverted on the device */
 void    lisi_bjacobi_wd_free(LIS_PRECON precon);
-void    lisd_bjacobi_free(void *bjacobi);                                    /* (lisd_mat_free) */
-LIS_INT lisd_bjacobi_begin(LIS_MATRIX A);                                   /* the inverse of A's diagonal blocks for a solve (made now if the HBM copy was rebuilt since create) */
-LIS_INT lisd_bjacobi_psolve(LIS_MATRIX A, int transposed, const double *b, double *x);   /* x = M^-1 b, or M^-H b  (b must not be x) */
+void    lisd_bjacobi_free(void *bjacobi);
+LIS_INT lisd_bjacobi_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);   /* the inverse of A's diagonal blocks for a solve (made now if the HBM copy was rebuilt since create) */
+LIS_INT lisd_bjacobi_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
 #define LISI_CHECK_NULL 0
 #define LISI_CHECK_SIZE 1
 #define LISI_CHECK_ASSEMBLED 2

@@ -1,8 +1,9 @@
 /*
  * lis_krylov.h -- what every Krylov loop of liblis_amd shares: the device-side solve context (work vectors in
  * HBM, preconditioner diagonal, tolerances), the residual bookkeeping of lis_solver.c:957-1091 / :1792-1812,
- * and the error-unwinding macros.  Included by lis_solver.c (CG, BiCG, BiCGSTAB, GMRES with fused passes) and
- * lis_solver_more.c (the other short-recurrence solvers, one kernel per reference call).
+ * the error-unwinding macros and the vocabulary the loops are written in.  Included by lis_solver.c (CG, BiCG, BiCGSTAB with
+ * fused passes, host-driven and device-driven, and GMRES) and lis_solver_more.c (every loop that is one kernel per reference call:
+ * CG, BiCG and BiCGSTAB in that form -- what a preconditioner that is no point diagonal runs -- and the other solvers).
  */
 #ifndef LIS_AMD_KRYLOV_H
 #define LIS_AMD_KRYLOV_H
@@ -17,9 +18,8 @@ typedef struct {
 	double *b, *x;           /* HBM */
 	double *dinv;            /* Jacobi 1/diag in HBM, NULL for none */
 	int duniform; double dconst;   /* every dinv[i] is the double dconst (a constant diagonal): the fused CG passes take the scalar */
-	int sweeps, sweeps_T;    /* the preconditioner is a pair of triangular sweeps (SSOR: lis_ssor.c, ILU: lis_ilu.c) with sweeps_T row blocks: only the loops that call d_psolve / d_psolveh */
-	int ilu, ilu_fill;       /* ... and it is ILU(ilu_fill), else SSOR */
-	int bjacobi;             /* the preconditioner is the inverted block diagonal of a BSR matrix (lis_bjacobi.c): like the sweeps, only the loops that call d_psolve / d_psolveh */
+	const lisi_precon_kind *pk;    /* the preconditioner's row (lis_internal.h) ... */
+	lisi_precon_state ps;    /* ... and what its begin resolved for this solve (ps.dinv is dinv) */
 	double **work; int nwork;
 	double bnrm, tol;
 	int output, maxiter;
@@ -41,26 +41,11 @@ static inline void work_free(ctx_t *c)
 	free(c->work); c->work = NULL; c->nwork = 0;
 }
 
-#define K(call) HIPCHK(call)
-static inline LIS_INT d_copy(ctx_t *c, const double *src, double *dst) { K(liship_memcpy_d2d(dst, src, sizeof(double) * (size_t)c->n, lisg.stream)); return LIS_SUCCESS; }
-static inline LIS_INT d_psolve(ctx_t *c, const double *r, double *z)
-{	/* none: copy (lis_precon.c:365-384); Jacobi: z = r .* dinv (lis_precon_jacobi.c:121-124); SSOR: the two sweeps (lis_precon_ssor.c:99-116); ILU: L, then U and D (lis_precon_iluk.c:880-934);
-	 * block Jacobi: z = WD r (lis_precon_jacobi.c:255-272) */
-	if (c->bjacobi) return lisd_bjacobi_psolve(c->A, 0, r, z);
-	if (c->ilu) return lisd_ilu_psolve(c->A, c->ilu_fill, c->sweeps_T, r, z);
-	if (c->sweeps) return lisd_ssor_psolve(c->A, c->sweeps_T, r, z);
-	if (c->dinv) { K(liship_pmul_f64(c->n, r, c->dinv, z, lisg.stream)); return LIS_SUCCESS; }
-	return d_copy(c, r, z);
-}
-static inline LIS_INT d_psolveh(ctx_t *c, const double *r, double *z)
-{	/* M^-H (lis_psolveh): M^-1 itself for none / Jacobi; SSOR / ILU: the transposed sweeps (lis_precon_ssor.c:119-136, lis_precon_iluk.c:1086-1140); block Jacobi: the transposed blocks (:276-293) */
-	if (c->bjacobi) return lisd_bjacobi_psolve(c->A, 1, r, z);
-	if (c->ilu) return lisd_ilu_psolveh(c->A, c->ilu_fill, c->sweeps_T, r, z);
-	if (c->sweeps) return lisd_ssor_psolveh(c->A, c->sweeps_T, r, z);
-	return d_psolve(c, r, z);
-}
-/* the preconditioner is no point diagonal: the fused and device-driven loops (which fold z = r .* dinv into their passes) do not apply */
-static inline int precon_by_calls(const ctx_t *c) { return c->sweeps || c->bjacobi; }
+static inline LIS_INT d_copy(ctx_t *c, const double *src, double *dst) { HIPCHK(liship_memcpy_d2d(dst, src, sizeof(double) * (size_t)c->n, lisg.stream)); return LIS_SUCCESS; }
+/* z = M^-1 r and z = M^-H r (lis_psolve / lis_psolveh): the row's apply; which r may alias z is on the row */
+static inline LIS_INT d_psolve(ctx_t *c, const double *r, double *z) { return c->pk->apply(&c->ps, 0, r, z); }
+static inline LIS_INT d_psolveh(ctx_t *c, const double *r, double *z) { return c->pk->apply(&c->ps, 1, r, z); }
+static inline int precon_by_calls(const ctx_t *c) { return c->pk->by_calls; }
 static inline LIS_INT d_matvec(ctx_t *c, double *x, double *y) { return lisd_spmv(c->A, x, y); }
 static inline LIS_INT d_resid(ctx_t *c, const double *r, double *nrm)
 {	/* lis_solver_get_residual_nrm2_r (lis_solver.c:1792) / _nrm1_b (:1804) */
@@ -104,10 +89,63 @@ static inline int initial_residual(ctx_t *c, double *r)
 	return 0;
 }
 
+/* GMRES and FGMRES, host scalars (lis_solver_gmres.c:254-290).  The new Hessenberg column hc (entries 0 .. ii + 1) takes the earlier rotations, which lie
+ * behind h at CS (cosines) and SN (sines), then its own is made, kept and applied to hc and to g; returns |g[ii + 1]| */
+static inline double givens_column(double *h, double *hc, double *g, int ii, int CS, int SN)
+{
+	const int i1 = ii + 1;
+	for (int k = 1; k <= ii; k++) {
+		const int jj = k - 1;
+		const double tt = hc[jj];
+		double aa = h[jj + CS] * tt;  aa += h[jj + SN] * hc[k];
+		double bb = -h[jj + SN] * tt; bb += h[jj + CS] * hc[k];
+		hc[jj] = aa; hc[k] = bb;
+	}
+	double aa = hc[ii], bb = hc[i1];
+	double rr = sqrt(aa * aa + bb * bb);
+	if (rr == 0.0) rr = 1.0e-17;
+	h[ii + CS] = aa / rr;
+	h[ii + SN] = bb / rr;
+	g[i1] = -h[ii + SN] * g[ii];
+	g[ii] =  h[ii + CS] * g[ii];
+	aa  = h[ii + CS] * hc[ii];
+	aa += h[ii + SN] * hc[i1];
+	hc[ii] = aa;
+	return fabs(g[i1]);
+}
+/* ... and the back substitution: g[0 .. ii] becomes the coefficients of the update */
+static inline void hessenberg_solve(const double *h, double *g, int ii, int ld)
+{
+	g[ii] = g[ii] / h[ii + (size_t)ii * ld];
+	for (int k = 1; k <= ii; k++) {
+		const int jj = ii - k;
+		double tt = g[jj];
+		for (int j = jj + 1; j <= ii; j++) tt -= h[jj + (size_t)j * ld] * g[j];
+		g[jj] = tt / h[jj + (size_t)jj * ld];
+	}
+}
+
 #define TRY(expr) do { LIS_INT e__ = (expr); if (e__) { err = e__; goto done; } } while (0)
 #define KTRY(call) do { int rc__ = (call); if (rc__) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc__); goto done; } } while (0)
 
+/* the loops' vocabulary; each names c, n, s, iter, nrm2, err and the label done of the loop it stands in */
+#define AXPY(a, x, y)      KTRY(liship_axpy_f64(n, (a), (x), (y), lisg.stream))          /* y += a x     */
+#define XPAY(x, a, y)      KTRY(liship_xpay_f64(n, (x), (a), (y), lisg.stream))          /* y = x + a y  */
+#define AXPYZ(a, x, y, z)  KTRY(liship_axpyz_f64(n, (a), (x), (y), (z), lisg.stream))    /* z = a x + y  */
+#define SCALE(a, x)        KTRY(liship_scale_f64(n, (a), (x), lisg.stream))
+#define COPY(src, dst)     TRY(d_copy(c, (src), (dst)))
+#define DOT(x, y, out)     TRY(lisd_dot(n, (x), (y), (out)))
+#define MATVEC(x, y)       TRY(d_matvec(c, (x), (y)))
+#define PSOLVE(r, z)       TRY(d_psolve(c, (r), (z)))
+#define PSOLVEH(r, z)      TRY(d_psolveh(c, (r), (z)))
+#define RESID(r, out)      TRY(d_resid(c, (r), (out)))
+#define START(r) do { int st__ = initial_residual(c, (r)); if (st__) { err = st__ < 0 ? -st__ : 0; goto done; } } while (0)
+#define FINISH(code) do { s->retcode = (code); s->iter = iter; s->resid = nrm2; err = ((code) == LIS_SUCCESS) ? 0 : (code); goto done; } while (0)
+
 /* lis_solver_more.c */
+LIS_INT lisk_cg(ctx_t *c);
+LIS_INT lisk_bicg(ctx_t *c);
+LIS_INT lisk_bicgstab(ctx_t *c);
 LIS_INT lisk_cgs(ctx_t *c);
 LIS_INT lisk_cr(ctx_t *c);
 LIS_INT lisk_gpbicg(ctx_t *c);

@@ -457,7 +457,7 @@ LIS_INT lis_matrix_destroy(LIS_MATRIX A)
 {
 	if (A && lisi_is_registered(A)) {
 		lisi_matrix_storage_destroy(A);
-		lisi_ssor_wd_free(A);
+		lisi_precon_release(NULL, A, NULL);     /* what a preconditioner left on the matrix (SSOR's WD) */
 		free(A->w_nnz);
 		free(A->l2g_map);
 		if (A->commtable) lisc_commtable_destroy(A->commtable);

@@ -1,5 +1,7 @@
 /*
- * lis_solver.c -- lis_solve() and the three Krylov loops of the hot path, iterating entirely in HBM.
+ * lis_solver.c -- the solver object, the preconditioner table, lis_solve() in stages, and the Krylov loops of the hot path,
+ * iterating entirely in HBM: CG, BiCG and BiCGSTAB with fused passes (host scalars, and device-driven) and GMRES.  Their
+ * one-kernel-per-reference-call forms, which every preconditioner that is no point diagonal runs, are in lis_solver_more.c.
  *
  * Orchestration follows the reference (src/solver/lis_solver.c: lis_solve :367, lis_solve_kernel :441,
  * initial residual :957, defaults :242-284, option table :175-197); the recurrences are the reference's
@@ -220,36 +222,71 @@ LIS_INT lis_solver_set_optionC(LIS_SOLVER solver)
 	return set_from_tokens(lisi_cmd_argv, lisi_cmd_argc, solver);
 }
 
-/* ------------------------------------------------------------------ preconditioner (none, Jacobi, ILU(k), SSOR, block Jacobi) */
+/* ------------------------------------------------------------------ preconditioners: the rows of none and Jacobi, the table (lis_internal.h) */
+static LIS_INT none_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st) { (void)solver; st->A = A; st->n = A->n; return LIS_SUCCESS; }
+static LIS_INT none_apply(const lisi_precon_state *st, int transposed, const double *r, double *z)
+{	/* a copy (lis_precon.c:365-384), M^-H likewise */
+	(void)transposed;
+	HIPCHK(liship_memcpy_d2d(z, r, sizeof(double) * (size_t)st->n, lisg.stream));
+	return LIS_SUCCESS;
+}
+static LIS_INT jacobi_create(LIS_SOLVER solver, LIS_PRECON p)
+{	/* D = 1 / diag(A): ref lis_precon_jacobi.c:61-85 */
+	LISCHK(lis_vector_duplicate(solver->A, &p->D));
+	LISCHK(lis_matrix_get_diagonal(solver->A, p->D));
+	return lis_vector_reciprocal(p->D);
+}
+static LIS_INT jacobi_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st) { st->A = A; st->n = A->n; return lisd_vec_in(solver->precon->D, &st->dinv); }
+static LIS_INT jacobi_apply(const lisi_precon_state *st, int transposed, const double *r, double *z)
+{	/* z = r .* dinv (lis_precon_jacobi.c:121-124), M^-H likewise; r may be z */
+	(void)transposed;
+	HIPCHK(liship_pmul_f64(st->n, r, st->dinv, z, lisg.stream));
+	return LIS_SUCCESS;
+}
+static void jacobi_free(LIS_PRECON p) { if (p->D) lis_vector_destroy(p->D); }
+
+const lisi_precon_kind lisi_precon_kinds[LISI_PRECON_KINDS] = {
+	{ LIS_PRECON_TYPE_NONE,    0, NULL,                none_begin,         none_apply,         0, NULL, NULL, NULL },
+	{ LIS_PRECON_TYPE_JACOBI,  0, jacobi_create,       jacobi_begin,       jacobi_apply,       0, NULL, NULL, jacobi_free },
+	/* pattern, schedule and factor live on the HBM copy of A: lis_ilu.c (the precon owns nothing, L / U stay NULL) */
+	{ LIS_PRECON_TYPE_ILU,     1, lisi_ilu_create,     lisd_ilu_begin,     lisd_ilu_apply,     offsetof(lisd_mat, ilu), lisd_ilu_free, NULL, NULL },
+	/* split A, WD on the matrix: lis_ssor.c (A stays split: lis_solve never merges it) */
+	{ LIS_PRECON_TYPE_SSOR,    1, lisi_ssor_create,    lisd_ssor_begin,    lisd_ssor_apply,    offsetof(lisd_mat, ssor), lisd_ssor_free, lisi_ssor_wd_free, NULL },
+	/* -storage, then split A + WD = D^-1 block by block on the precon; a matrix without blocks turns p into a Jacobi preconditioner: lis_bjacobi.c */
+	{ LIS_PRECON_TYPE_BJACOBI, 1, lisi_bjacobi_create, lisd_bjacobi_begin, lisd_bjacobi_apply, offsetof(lisd_mat, bjacobi), lisd_bjacobi_free, NULL, lisi_bjacobi_wd_free },
+};
+
+const lisi_precon_kind *lisi_precon_kind_of(LIS_INT type)
+{
+	for (int k = 0; k < LISI_PRECON_KINDS; k++) if (lisi_precon_kinds[k].type == type) return &lisi_precon_kinds[k];
+	return NULL;
+}
+
+void lisi_precon_release(lisd_mat *d, LIS_MATRIX A, LIS_PRECON precon)
+{
+	for (const lisi_precon_kind *k = lisi_precon_kinds; k < lisi_precon_kinds + LISI_PRECON_KINDS; k++) {
+		if (d && k->cache_free) { void **slot = (void **)((char *)d + k->cache_slot); k->cache_free(*slot); *slot = NULL; }
+		if (A && k->matrix_free) k->matrix_free(A);
+		if (precon && k->precon_free) k->precon_free(precon);
+	}
+}
+
 LIS_INT lis_precon_create(LIS_SOLVER solver, LIS_PRECON *precon)
 {
 	const LIS_INT type = solver->options[LIS_OPTIONS_PRECON];
+	const lisi_precon_kind *k = lisi_precon_kind_of(type);
 	*precon = NULL;
-	if (type != LIS_PRECON_TYPE_NONE && type != LIS_PRECON_TYPE_JACOBI && type != LIS_PRECON_TYPE_SSOR && type != LIS_PRECON_TYPE_ILU && type != LIS_PRECON_TYPE_BJACOBI)
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ilu, ssor, bjacobi)\n", type);
+	if (!k) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ilu, ssor, bjacobi)\n", type);
 	LIS_PRECON p = (LIS_PRECON)calloc(1, sizeof(lisi_precon));
 	if (!p) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(lisi_precon));
 	p->precon_type = type;
 	lisi_register(p, LISI_KIND_PRECON);
-	if (type == LIS_PRECON_TYPE_BJACOBI) {     /* -storage, then split A + WD = D^-1 block by block; a matrix without blocks turns p into a Jacobi preconditioner: lis_bjacobi.c */
-		PPRIV(p)->from_bjacobi = 1;
-		LIS_INT err = lisi_bjacobi_create(solver, p);
-		if (err) { lis_precon_destroy(p); return err; }
+	LIS_INT err = k->create ? k->create(solver, p) : LIS_SUCCESS;
+	if (!err && p->precon_type != type) {      /* the create turned p into another kind (-p bjacobi without blocks: Jacobi), whose create goes on */
+		k = lisi_precon_kind_of(p->precon_type);
+		err = k->create ? k->create(solver, p) : LIS_SUCCESS;
 	}
-	if (p->precon_type == LIS_PRECON_TYPE_JACOBI) {      /* D = 1 / diag(A): ref lis_precon_jacobi.c:61-85 */
-		LIS_INT err = lis_vector_duplicate(solver->A, &p->D);
-		if (!err) err = lis_matrix_get_diagonal(solver->A, p->D);
-		if (!err) err = lis_vector_reciprocal(p->D);
-		if (err) { lis_precon_destroy(p); return err; }
-	}
-	if (type == LIS_PRECON_TYPE_SSOR) {        /* split A, WD: lis_ssor.c (A stays split: lis_solve never merges it) */
-		LIS_INT err = lisi_ssor_create(solver, p);
-		if (err) { lis_precon_destroy(p); return err; }
-	}
-	if (type == LIS_PRECON_TYPE_ILU) {         /* pattern, schedule and factor live on the HBM copy of A: lis_ilu.c (the precon owns nothing, L / U stay NULL) */
-		LIS_INT err = lisi_ilu_create(solver, p);
-		if (err) { lis_precon_destroy(p); return err; }
-	}
+	if (err) { lis_precon_destroy(p); return err; }
 	*precon = p;
 	return LIS_SUCCESS;
 }
@@ -257,8 +294,7 @@ LIS_INT lis_precon_create(LIS_SOLVER solver, LIS_PRECON *precon)
 LIS_INT lis_precon_destroy(LIS_PRECON precon)
 {
 	if (precon && lisi_is_registered(precon)) {
-		if (precon->D) lis_vector_destroy(precon->D);
-		lisi_bjacobi_wd_free(precon);
+		lisi_precon_release(NULL, NULL, precon);
 		lisi_unregister(precon);
 		free(precon);
 	}
@@ -538,12 +574,10 @@ done:
  *   q = A p ; <p,q>                  the product, the dot in its epilogue
  *   x += alpha p ; r -= alpha q ; ||r|| ; rho' = <r, M^-1 r>     one pass
  * rho' is the next iteration's rho (the reference computes it at :180 from the same r).
- * LIS_AMD_NO_FUSION=1 runs the one-kernel-per-reference-call loop instead. */
-static LIS_INT run_cg_unfused(ctx_t *c);
-static LIS_INT run_cg_device(ctx_t *c);
+ * LIS_AMD_NO_FUSION=1, and a preconditioner that is no point diagonal, run the one-kernel-per-reference-call loop instead (lis_solver_more.c lisk_cg). */
 static LIS_INT run_cg(ctx_t *c)
 {
-	if (lisg.no_fusion || precon_by_calls(c)) return run_cg_unfused(c);
+	if (lisg.no_fusion || precon_by_calls(c)) return lisk_cg(c);
 	if (device_scalars_ok(c)) return run_cg_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -551,8 +585,7 @@ static LIS_INT run_cg(ctx_t *c)
 	TRY(work_alloc(c, 3));
 	double *q = c->work[0], *r = c->work[1], *p = c->work[2];
 	double alpha, beta, rho, rho_old = 1.0, dot_pq, nrm2 = 0.0, sums[2];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	/* rho of the first iteration; z lives in q for this one pass */
 	if (c->dinv) { KTRY(liship_pmul_f64(n, r, c->dinv, q, lisg.stream)); TRY(lisd_dot(n, r, q, &rho)); }
 	else TRY(lisd_dot(n, r, r, &rho));
@@ -562,7 +595,7 @@ static LIS_INT run_cg(ctx_t *c)
 		else         KTRY(liship_xpay_f64(n, r, beta, p, lisg.stream));
 		TRY(lisd_spmv_dot_launch(c->A, p, q, p, 0));
 		TRY(lisd_fetch(1, &dot_pq));
-		if (dot_pq == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		if (dot_pq == 0.0) FINISH(LIS_BREAKDOWN);
 		alpha = rho / dot_pq;
 		if (c->dinv) {
 			KTRY(liship_cg_update_jacobi_f64(n, alpha, p, q, c->dinv, c->x, r, lisg.reduce_out, lisg.reduce_work, lisg.stream));
@@ -574,44 +607,11 @@ static LIS_INT run_cg(ctx_t *c)
 		}
 		TRY(resid_from_sumsq(c, r, sums[0], &nrm2));
 		note(c, iter, nrm2);
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
 		rho_old = rho;
 		rho = sums[1];
 	}
-	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
-done:
-	work_free(c);
-	return err;
-}
-
-static LIS_INT run_cg_unfused(ctx_t *c)
-{
-	LIS_SOLVER s = c->s;
-	LIS_INT err = 0, iter;
-	const int n = c->n;
-	TRY(work_alloc(c, 4));
-	double *z = c->work[0], *q = c->work[1], *r = c->work[2], *p = c->work[3];
-	double alpha, beta, rho, rho_old = 1.0, dot_pq, nrm2 = 0.0;
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
-	KTRY(liship_set_all_f64(n, 0.0, p, lisg.stream));
-	for (iter = 1; iter <= c->maxiter; iter++) {
-		TRY(d_psolve(c, r, z));
-		TRY(lisd_dot(n, r, z, &rho));
-		beta = rho / rho_old;
-		KTRY(liship_xpay_f64(n, z, beta, p, lisg.stream));
-		TRY(d_matvec(c, p, q));
-		TRY(lisd_dot(n, p, q, &dot_pq));
-		if (dot_pq == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
-		alpha = rho / dot_pq;
-		KTRY(liship_axpy_f64(n, alpha, p, c->x, lisg.stream));
-		KTRY(liship_axpy_f64(n, -alpha, q, r, lisg.stream));
-		TRY(d_resid(c, r, &nrm2));
-		note(c, iter, nrm2);
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
-		rho_old = rho;
-	}
-	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
+	FINISH(LIS_MAXITER);
 done:
 	work_free(c);
 	return err;
@@ -624,11 +624,9 @@ done:
  *   t = A M^-1 s ; <t,s>, <t,t>                     product + epilogue
  *   x += alpha phat + omega shat                    one pass
  *   r = s - omega t ; ||r|| ; rho' = <rtld,r>       one pass (rho' is :190 of the next iteration) */
-static LIS_INT run_bicgstab_unfused(ctx_t *c);
-static LIS_INT run_bicgstab_device(ctx_t *c);
 static LIS_INT run_bicgstab(ctx_t *c)
 {
-	if (lisg.no_fusion || precon_by_calls(c)) return run_bicgstab_unfused(c);
+	if (lisg.no_fusion || precon_by_calls(c)) return lisk_bicgstab(c);
 	if (device_scalars_ok(c)) return run_bicgstab_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -639,12 +637,11 @@ static LIS_INT run_bicgstab(ctx_t *c)
 	double *phat = pre ? c->work[5] : p, *shat = pre ? c->work[6] : r;
 	double *sv = r;                                    /* s aliases r: lis_solver_bicgstab.c:160-161 */
 	double alpha = 1.0, omega = 1.0, rho_old = 1.0, rho, beta, nrm2 = 0.0, d1, d2[2], sums[2];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	TRY(d_copy(c, r, rtld));                           /* shadow residual = r0 (lis_solver.c:1862) */
 	TRY(lisd_dot(n, rtld, r, &rho));
 	for (iter = 1; iter <= c->maxiter; iter++) {
-		if (rho == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		if (rho == 0.0) FINISH(LIS_BREAKDOWN);
 		if (iter == 1) TRY(d_copy(c, r, p));
 		else {
 			beta = (rho / rho_old) * (alpha / omega);
@@ -660,7 +657,7 @@ static LIS_INT run_bicgstab(ctx_t *c)
 		if (nrm2 <= c->tol) {
 			note(c, iter, nrm2);
 			KTRY(liship_axpy_f64(n, alpha, phat, c->x, lisg.stream));
-			s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done;
+			FINISH(LIS_SUCCESS);
 		}
 		if (pre) KTRY(liship_pmul_f64(n, sv, c->dinv, shat, lisg.stream));
 		TRY(lisd_spmv_dot_launch(c->A, shat, t, sv, 1));
@@ -671,64 +668,12 @@ static LIS_INT run_bicgstab(ctx_t *c)
 		TRY(lisd_fetch(2, sums));
 		TRY(resid_from_sumsq(c, r, sums[0], &nrm2));
 		note(c, iter, nrm2);
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
-		if (omega == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
+		if (omega == 0.0) FINISH(LIS_BREAKDOWN);
 		rho_old = rho;
 		rho = sums[1];
 	}
-	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
-done:
-	work_free(c);
-	return err;
-}
-
-static LIS_INT run_bicgstab_unfused(ctx_t *c)
-{
-	LIS_SOLVER s = c->s;
-	LIS_INT err = 0, iter;
-	const int n = c->n;
-	TRY(work_alloc(c, 7));
-	double *rtld = c->work[0], *r = c->work[1], *t = c->work[2], *p = c->work[3], *v = c->work[4],
-	       *phat = c->work[5], *shat = c->work[6];
-	double *sv = r;                                    /* s aliases r: lis_solver_bicgstab.c:160-161 */
-	double alpha = 1.0, omega = 1.0, rho_old = 1.0, rho, beta, nrm2 = 0.0, d1, d2[2];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
-	TRY(d_copy(c, r, rtld));                           /* shadow residual = r0 (lis_solver.c:1862) */
-	for (iter = 1; iter <= c->maxiter; iter++) {
-		TRY(lisd_dot(n, rtld, r, &rho));
-		if (rho == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
-		if (iter == 1) TRY(d_copy(c, r, p));
-		else {
-			beta = (rho / rho_old) * (alpha / omega);
-			KTRY(liship_axpy_f64(n, -omega, v, p, lisg.stream));
-			KTRY(liship_xpay_f64(n, r, beta, p, lisg.stream));
-		}
-		TRY(d_psolve(c, p, phat));
-		TRY(d_matvec(c, phat, v));
-		TRY(lisd_dot(n, rtld, v, &d1));
-		alpha = rho / d1;
-		KTRY(liship_axpy_f64(n, -alpha, v, r, lisg.stream));
-		TRY(d_resid(c, sv, &nrm2));
-		if (nrm2 <= c->tol) {
-			note(c, iter, nrm2);
-			KTRY(liship_axpy_f64(n, alpha, phat, c->x, lisg.stream));
-			s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done;
-		}
-		TRY(d_psolve(c, sv, shat));
-		TRY(d_matvec(c, shat, t));
-		TRY(lisd_dot2(n, t, sv, d2));                   /* <t,s> and <t,t> in one pass (:267-268) */
-		omega = d2[0] / d2[1];
-		KTRY(liship_axpy_f64(n, alpha, phat, c->x, lisg.stream));
-		KTRY(liship_axpy_f64(n, omega, shat, c->x, lisg.stream));
-		KTRY(liship_axpy_f64(n, -omega, t, r, lisg.stream));
-		TRY(d_resid(c, r, &nrm2));
-		note(c, iter, nrm2);
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
-		if (omega == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
-		rho_old = rho;
-	}
-	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
+	FINISH(LIS_MAXITER);
 done:
 	work_free(c);
 	return err;
@@ -742,10 +687,9 @@ done:
  *   x += alpha p ; r -= alpha q ; ||r||                    one pass
  *   r~ -= alpha q~ ; rho' = <r~, M^-1 r>                   one pass (rho' is :187 of the next iteration) */
 static LIS_INT run_bicg_device(ctx_t *c);
-static LIS_INT run_bicg_unfused(ctx_t *c);
 static LIS_INT run_bicg(ctx_t *c)
 {
-	if (precon_by_calls(c)) return run_bicg_unfused(c);
+	if (precon_by_calls(c)) return lisk_bicg(c);
 	if (!lisg.no_fusion && device_scalars_ok(c)) return run_bicg_device(c);
 	LIS_SOLVER s = c->s;
 	LIS_INT err = 0, iter;
@@ -754,13 +698,12 @@ static LIS_INT run_bicg(ctx_t *c)
 	double *r = c->work[0], *rtld = c->work[1], *q = c->work[2], *qtld = c->work[3], *p = c->work[4], *ptld = c->work[5];
 	double *z = c->work[6];                            /* M^-1 r, only kept for the Jacobi dot */
 	double alpha, beta, rho, rho_old = 1.0, d1, nrm2 = 0.0, sums[2];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	TRY(d_copy(c, r, rtld));                           /* shadow residual = r0 (lis_solver.c:1862) */
 	if (c->dinv) { KTRY(liship_pmul_f64(n, r, c->dinv, z, lisg.stream)); TRY(lisd_dot(n, rtld, z, &rho)); }
 	else TRY(lisd_dot(n, rtld, r, &rho));
 	for (iter = 1; iter <= c->maxiter; iter++) {
-		if (rho == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		if (rho == 0.0) FINISH(LIS_BREAKDOWN);
 		beta = rho / rho_old;
 		if (c->dinv) {
 			KTRY(liship_pmul_xpay_f64(n, r, c->dinv, beta, p, lisg.stream));
@@ -772,62 +715,20 @@ static LIS_INT run_bicg(ctx_t *c)
 		TRY(lisd_spmv_dot_launch(c->A, p, q, ptld, 0));
 		TRY(lisd_fetch(1, &d1));
 		TRY(lisd_spmv_t(c->A, ptld, qtld));
-		if (d1 == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
+		if (d1 == 0.0) FINISH(LIS_BREAKDOWN);
 		alpha = rho / d1;
 		KTRY(liship_cg_update_f64(n, alpha, p, q, c->x, r, lisg.reduce_out, lisg.reduce_work, lisg.stream));
 		TRY(lisd_fetch(1, sums));
 		TRY(resid_from_sumsq(c, r, sums[0], &nrm2));
 		note(c, iter, nrm2);
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
 		if (c->dinv) KTRY(liship_pmul_f64(n, r, c->dinv, z, lisg.stream));
 		KTRY(liship_axpy_sumsq_dot_f64(n, -alpha, qtld, rtld, c->dinv ? z : r, lisg.reduce_out, lisg.reduce_work, lisg.stream));
 		TRY(lisd_fetch(2, sums));
 		rho_old = rho;
 		rho = sums[1];
 	}
-	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
-done:
-	work_free(c);
-	return err;
-}
-
-/* BiCG one call per reference statement (lis_solver_bicg.c:186-271): the form a preconditioner that is no diagonal needs, M^-H r~ by d_psolveh */
-static LIS_INT run_bicg_unfused(ctx_t *c)
-{
-	LIS_SOLVER s = c->s;
-	LIS_INT err = 0, iter;
-	const int n = c->n;
-	TRY(work_alloc(c, 6));
-	double *r = c->work[0], *rtld = c->work[1], *z = c->work[2], *ztld = c->work[3], *p = c->work[4], *ptld = c->work[5];
-	double *q = z, *qtld = ztld;                       /* aliases as in the reference (:167-168) */
-	double alpha, beta, rho, rho_old = 1.0, d1, nrm2 = 0.0;
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
-	TRY(d_copy(c, r, rtld));                           /* shadow residual = r0 (lis_solver.c:1862) */
-	KTRY(liship_set_all_f64(n, 0.0, p, lisg.stream));
-	KTRY(liship_set_all_f64(n, 0.0, ptld, lisg.stream));
-	for (iter = 1; iter <= c->maxiter; iter++) {
-		TRY(d_psolve(c, r, z));
-		TRY(d_psolveh(c, rtld, ztld));
-		TRY(lisd_dot(n, rtld, z, &rho));
-		if (rho == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
-		beta = rho / rho_old;
-		KTRY(liship_xpay_f64(n, z, beta, p, lisg.stream));
-		TRY(d_matvec(c, p, q));
-		KTRY(liship_xpay_f64(n, ztld, beta, ptld, lisg.stream));
-		TRY(lisd_spmv_t(c->A, ptld, qtld));
-		TRY(lisd_dot(n, ptld, q, &d1));
-		if (d1 == 0.0) { s->retcode = LIS_BREAKDOWN; s->iter = iter; s->resid = nrm2; err = LIS_BREAKDOWN; goto done; }
-		alpha = rho / d1;
-		KTRY(liship_axpy_f64(n, alpha, p, c->x, lisg.stream));
-		KTRY(liship_axpy_f64(n, -alpha, q, r, lisg.stream));
-		TRY(d_resid(c, r, &nrm2));
-		note(c, iter, nrm2);
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
-		KTRY(liship_axpy_f64(n, -alpha, qtld, rtld, lisg.stream));
-		rho_old = rho;
-	}
-	s->retcode = LIS_MAXITER; s->iter = iter; s->resid = nrm2; err = LIS_MAXITER;
+	FINISH(LIS_MAXITER);
 done:
 	work_free(c);
 	return err;
@@ -918,8 +819,7 @@ static LIS_INT run_gmres(ctx_t *c)
 	 * (all-gather + rank-order fold); the callback communicator folds on the host, so it takes the other branch */
 	const int chained = !lisg.no_fusion && (lisg.nprocs == 1 || lisg.comm_kind == 1);
 	if (chained) KTRY(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(m + 4)));
-	int st = initial_residual(c, v[0]);                /* :193 leaves the unpreconditioned residual in v0 */
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(v[0]);                /* :193 leaves the unpreconditioned residual in v0 */
 	while (iter < c->maxiter) {
 		TRY(lisd_nrm2(n, v[0], &rnorm));
 		KTRY(liship_scale_f64(n, 1.0 / rnorm, v[0], lisg.stream));
@@ -966,36 +866,12 @@ static LIS_INT run_gmres(ctx_t *c)
 				hc[i1] = t;
 				KTRY(liship_scale_f64(n, 1.0 / t, v[i1], lisg.stream));
 			}
-			for (int k = 1; k <= ii; k++) {                /* apply the previous rotations */
-				const int jj = k - 1;
-				const double tt = hc[jj];
-				double aa = h[jj + CS] * tt;  aa += h[jj + SN] * hc[k];
-				double bb = -h[jj + SN] * tt; bb += h[jj + CS] * hc[k];
-				hc[jj] = aa; hc[k] = bb;
-			}
-			double aa = hc[ii], bb = hc[i1];
-			const double a2 = aa * aa, b2 = bb * bb;
-			double rr = sqrt(a2 + b2);
-			if (rr == 0.0) rr = 1.0e-17;
-			h[ii + CS] = aa / rr;
-			h[ii + SN] = bb / rr;
-			g[i1] = -h[ii + SN] * g[ii];
-			g[ii] =  h[ii + CS] * g[ii];
-			aa  = h[ii + CS] * hc[ii];
-			aa += h[ii + SN] * hc[i1];
-			hc[ii] = aa;
-			nrm2 = fabs(g[i1]) * c->bnrm;
+			nrm2 = givens_column(h, hc, g, ii, CS, SN) * c->bnrm;
 			note(c, iter, nrm2);
 			if (c->tol >= nrm2) break;
 		} while (i < m && iter < c->maxiter);
 
-		g[ii] = g[ii] / h[ii + (size_t)ii * ld];           /* back substitution */
-		for (int k = 1; k <= ii; k++) {
-			const int jj = ii - k;
-			double tt = g[jj];
-			for (int j = jj + 1; j <= ii; j++) tt -= h[jj + (size_t)j * ld] * g[j];
-			g[jj] = tt / h[jj + (size_t)jj * ld];
-		}
+		hessenberg_solve(h, g, ii, ld);
 		if (!lisg.no_fusion) KTRY(liship_lincomb_f64(n, ii + 1, (const double *const *)v, g, 0, z, lisg.stream));   /* z = sum y_j v_j, one pass */
 		else {
 			KTRY(liship_scale_to_f64(n, g[0], v[0], z, lisg.stream));     /* z = y0 v0  (:290-296) */
@@ -1005,7 +881,7 @@ static LIS_INT run_gmres(ctx_t *c)
 			TRY(d_psolve(c, z, r));
 			KTRY(liship_axpy_f64(n, 1.0, r, c->x, lisg.stream));
 		} else KTRY(liship_axpy_f64(n, 1.0, z, c->x, lisg.stream));      /* the copy of psolve_none left out: same addend */
-		if (c->tol >= nrm2) { s->retcode = LIS_SUCCESS; s->iter = iter; s->resid = nrm2; goto done; }
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
 		for (int j = 1; j <= i; j++) {
 			const int jj = i1 - j + 1;
 			g[jj - 1] = -h[jj - 1 + SN] * g[jj];
@@ -1055,29 +931,18 @@ static void swap_transposed(lisd_mat *d)
 	tq = d->t_plan; d->t_plan = d->rt_plan; d->rt_plan = tq;
 }
 
-LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER solver, LIS_PRECON precon)
+/* ------------------------------------------------------------------ the stages of lis_solve_kernel, in its order */
+/* the solvers that multiply by A^T */
+static int solver_needs_transpose(LIS_INT nsolver)
 {
-	const LIS_INT nsolver = solver->options[LIS_OPTIONS_SOLVER], maxiter = solver->options[LIS_OPTIONS_MAXITER];
-	const LIS_INT output = solver->options[LIS_OPTIONS_OUTPUT], storage = solver->options[LIS_OPTIONS_STORAGE];
-	const LIS_INT conv = solver->options[LIS_OPTIONS_CONV_COND];
-	const double tol = solver->params[LIS_PARAMS_RESID - LIS_OPTIONS_LEN];
-	LIS_MATRIX Awork = A;
-	LIS_INT err = 0;
-	ctx_t c;
-	memset(&c, 0, sizeof(c));
-	/* SSOR, ILU and block Jacobi depend on the numbering (the sweeps follow the rows' order, the blocks the caller's rows): such a solve never runs renumbered, nor builds the renumbered form */
-	const int ilu = precon && precon->precon_type == LIS_PRECON_TYPE_ILU;
-	const int bjacobi = precon && precon->precon_type == LIS_PRECON_TYPE_BJACOBI;
-	const int sweeps = precon && (precon->precon_type == LIS_PRECON_TYPE_SSOR || ilu);
-	int renumbered = 0;                        /* the solve runs in the numbering of a reordered plan (below) */
-	const int *renum = NULL;
-	double *renum_b = NULL, *renum_d = NULL;
-	liship_csr_plan_t held_plan = NULL;
-	int *held_ptr = NULL, *held_index = NULL;
-	double *held_value = NULL;
+	return nsolver == LIS_SOLVER_BICG || nsolver == LIS_SOLVER_BICR || nsolver == LIS_SOLVER_CRS || nsolver == LIS_SOLVER_BICRSTAB ||
+	       nsolver == LIS_SOLVER_GPBICR || nsolver == LIS_SOLVER_BICRSAFE;
+}
 
-	if (lisp_lazy()) lisp_check_handler();          /* a SIGSEGV handler the program installed since would take the protected pages' faults away */
-	/* parameter checks, ref :482-537 */
+/* parameter checks, ref :482-537; then the solver object made ready for a solve */
+static LIS_INT check_options(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER solver)
+{
+	const LIS_INT nsolver = solver->options[LIS_OPTIONS_SOLVER], maxiter = solver->options[LIS_OPTIONS_MAXITER], conv = solver->options[LIS_OPTIONS_CONV_COND];
 	if (nsolver < 1 || nsolver > LIS_SOLVER_LEN) return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_SOLVER is %D (Set between 1 to %D)\n", nsolver, LIS_SOLVER_LEN);
 	switch (nsolver) {
 	case LIS_SOLVER_CG: case LIS_SOLVER_BICG: case LIS_SOLVER_BICGSTAB: case LIS_SOLVER_GMRES:
@@ -1092,7 +957,6 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	if (maxiter < 0) return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_MAXITER(=%D) is less than 0\n", maxiter);
 	if (conv > 0 && (nsolver == LIS_SOLVER_GMRES || nsolver == LIS_SOLVER_TFQMR || nsolver == LIS_SOLVER_FGMRES || nsolver == LIS_SOLVER_MINRES || nsolver == LIS_SOLVER_JACOBI)) return LISI_ERR(LIS_ERR_ILL_ARG, "Option conv_cond is not implemented for solver %s\n", solver_names[nsolver]);
 	if (solver->options[LIS_OPTIONS_PRECISION] != LIS_PRECISION_DOUBLE) return LISI_ERR(LIS_ERR_ILL_ARG, "Quad precision is not enabled\n");
-	LIS_INT scale = solver->options[LIS_OPTIONS_SCALE];
 	if ((nsolver == LIS_SOLVER_GMRES || nsolver == LIS_SOLVER_ORTHOMIN || nsolver == LIS_SOLVER_FGMRES) && solver->options[LIS_OPTIONS_RESTART] < 0)
 		return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_RESTART(=%D) is less than 0\n", solver->options[LIS_OPTIONS_RESTART]);
 	if (A->n != b->n || A->n != x->n) return LISI_ERR(LIS_ERR_ILL_ARG, "sizes of A, b and x do not match\n");
@@ -1103,205 +967,254 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	if (!solver->rhistory) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", maxiter + 2);
 	solver->rhistory[0] = 1.0;
 	solver->ptime = 0.0;
+	return LIS_SUCCESS;
+}
 
-	/* -scale: A and b are scaled in place and stay scaled, CG turns jacobi into symm_diag (ref :686-724).  The
-	 * Jacobi preconditioner was built from the UNSCALED matrix by lis_solve before this point, as in the reference. */
-	if (scale && storage == LIS_MATRIX_BSR && scale == LIS_SCALE_JACOBI) {
-		/* block-diagonal scaling: A becomes BSR, is split and multiplied by the inverse diagonal blocks, b likewise; the
-		 * iterations then run on the split product (ref :659-690) */
-		{	/* feasibility BEFORE A and b are touched: the solvers that multiply by A^T need the transposed split product, which lisd_mat_ready_t serves
-			 * for square blocks only (lis_matvech.c) -- a refusal after the retype / split / scaling would hand the caller back a mutated A and b */
-			const int needs_t = nsolver == LIS_SOLVER_BICG || nsolver == LIS_SOLVER_BICR || nsolver == LIS_SOLVER_CRS || nsolver == LIS_SOLVER_BICRSTAB ||
-			                    nsolver == LIS_SOLVER_GPBICR || nsolver == LIS_SOLVER_BICRSAFE;
-			const LIS_INT blk = solver->options[LIS_OPTIONS_STORAGE_BLOCK];
-			const int square = A->matrix_type == LIS_MATRIX_BSR ? A->bnr == A->bnc : (blk > 0 || A->conv_bnr == A->conv_bnc);      /* (-storage_block b: b x b blocks) */
-			if (needs_t && !square) {
-				solver->retcode = LIS_ERR_NOT_IMPLEMENTED;
-				return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "solver %s with -scale jacobi -storage bsr needs A^T x of a split matrix: served for square blocks only (A and b are untouched)\n", solver_names[nsolver]);
-			}
-		}
-		if (A->matrix_type != LIS_MATRIX_BSR) err = lisi_matrix_retype(A, LIS_MATRIX_BSR, solver->options[LIS_OPTIONS_STORAGE_BLOCK]);
-		if (!err) err = lisi_matrix_bscale_bsr(A, b);
-		if (err) { solver->retcode = err; return err; }
-		scale = 0;
+/* -scale: A and b are scaled in place and stay scaled, CG turns jacobi into symm_diag (ref :686-724).  The Jacobi preconditioner was built from
+ * the UNSCALED matrix by lis_solve before this point, as in the reference.  *scale_out: the scaling the iterations and x still have to know of */
+static LIS_INT scale_system(LIS_MATRIX A, LIS_VECTOR b, LIS_SOLVER solver, LIS_INT *scale_out)
+{
+	const LIS_INT nsolver = solver->options[LIS_OPTIONS_SOLVER], blk = solver->options[LIS_OPTIONS_STORAGE_BLOCK];
+	LIS_INT scale = solver->options[LIS_OPTIONS_SCALE], err = 0;
+	*scale_out = 0;
+	if (scale == LIS_SCALE_JACOBI && solver->options[LIS_OPTIONS_STORAGE] == LIS_MATRIX_BSR) {
+		/* block-diagonal scaling: A becomes BSR, is split and multiplied by the inverse diagonal blocks, b likewise; the iterations then run on
+		 * the split product (ref :659-690).  Feasibility BEFORE A and b are touched: the solvers that multiply by A^T need the transposed split
+		 * product, which lisd_mat_ready_t serves for square blocks only (lis_matvech.c) -- a refusal after the retype / split / scaling would
+		 * hand the caller back a mutated A and b */
+		const int square = A->matrix_type == LIS_MATRIX_BSR ? A->bnr == A->bnc : (blk > 0 || A->conv_bnr == A->conv_bnc);      /* (-storage_block b: b x b blocks) */
+		if (solver_needs_transpose(nsolver) && !square)
+			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "solver %s with -scale jacobi -storage bsr needs A^T x of a split matrix: served for square blocks only (A and b are untouched)\n", solver_names[nsolver]);
+		if (A->matrix_type != LIS_MATRIX_BSR) err = lisi_matrix_retype(A, LIS_MATRIX_BSR, blk);
+		return err ? err : lisi_matrix_bscale_bsr(A, b);
 	}
-	if (scale) {
-		if (!solver->d) { err = lis_vector_duplicate(A, &solver->d); if (err) { solver->retcode = err; return err; } }
-		if (scale == LIS_SCALE_JACOBI && nsolver == LIS_SOLVER_CG) scale = LIS_SCALE_SYMM_DIAG;
-		if (!A->is_scaled) err = lis_matrix_scale(A, b, solver->d, scale);
-		else if (!b->is_scaled) {
-			err = lisd_vec_host_write(b, 1);
-			if (!err) err = lisd_vec_to_host(solver->d);
-			if (!err) { for (LIS_INT i = 0; i < A->n; i++) b->value[i] = b->value[i] * solver->d->value[i]; lis_amd_vector_host_modified(b); }
-		}
-		if (err) { solver->retcode = err; return err; }
+	if (!scale) return LIS_SUCCESS;
+	if (!solver->d) LISCHK(lis_vector_duplicate(A, &solver->d));
+	if (scale == LIS_SCALE_JACOBI && nsolver == LIS_SOLVER_CG) scale = LIS_SCALE_SYMM_DIAG;
+	*scale_out = scale;
+	if (!A->is_scaled) return lis_matrix_scale(A, b, solver->d, scale);
+	if (!b->is_scaled) {
+		LISCHK(lisd_vec_host_write(b, 1));
+		LISCHK(lisd_vec_to_host(solver->d));
+		for (LIS_INT i = 0; i < A->n; i++) b->value[i] = b->value[i] * solver->d->value[i];
+		lis_amd_vector_host_modified(b);
 	}
+	return LIS_SUCCESS;
+}
+
+static void banner(LIS_MATRIX A, LIS_SOLVER solver, LIS_PRECON precon)
+{
+	lis_printf(LIS_COMM_WORLD, "initial vector x      : %s\n", solver->options[LIS_OPTIONS_INITGUESS_ZEROS] ? "all components set to 0" : "user defined");
+	lis_printf(LIS_COMM_WORLD, "precision             : double\n");
+	lis_printf(LIS_COMM_WORLD, "linear solver         : %s\n", solver_names[solver->options[LIS_OPTIONS_SOLVER]]);
+	lis_printf(LIS_COMM_WORLD, "preconditioner        : %s\n", precon_names[precon->precon_type]);
+	if (solver->options[LIS_OPTIONS_CONV_COND] == LIS_CONV_COND_NRM2_R) lis_printf(LIS_COMM_WORLD, "convergence condition : ||b-Ax||_2 <= %6.1e * ||b-Ax_0||_2\n", solver->params[LIS_PARAMS_RESID - LIS_OPTIONS_LEN]);
+	if (A->matrix_type == LIS_MATRIX_BSR) lis_printf(LIS_COMM_WORLD, "matrix storage format : %s(%D x %D)\n", storage_names[A->matrix_type - 1], A->bnr, A->bnc);
+	else lis_printf(LIS_COMM_WORLD, "matrix storage format : %s\n", storage_names[A->matrix_type - 1]);
+}
+
+/* doubles per work vector: np + pad + slack, and a BSR matrix's padded block rows and columns */
+static size_t work_len(LIS_MATRIX A)
+{
+	size_t len = (size_t)(A->np + A->pad) + 16;
+	if (A->matrix_type == LIS_MATRIX_BSR) {
+		const size_t a = (size_t)A->nc * A->bnc + 16, bb = (size_t)A->nr * A->bnr + 16;
+		if (a > len) len = a;
+		if (bb > len) len = bb;
+	}
+	return len;
+}
+
+/* A plan that renumbered the matrix (liship.h: liship_csr_plan_reorder -- the caller's numbering has no locality): the WHOLE solve runs in the plan's numbering.
+ * b, x0 and 1/diag are gathered once, the iterations see P A P^T as the matrix (its plan with its fused reductions, its arrays), x is scattered back at the end:
+ * no product pays for a permutation.  The same recurrences on renumbered vectors; their sums fold in another order, so not in the reference-order mode. */
+typedef struct {
+	int on;                        /* the renumbered form is swapped in */
+	const int *perm;               /* perm[new position] = row (HBM) */
+	double *b, *d; size_t bytes;   /* pool buffers of `bytes` each: b and 1/diag in the plan's numbering */
+	liship_csr_plan_t plan;        /* the caller's form, held while the plan's stands in its place */
+	int *ptr, *index;
+	double *value;
+} renumber_t;
+
+/* swaps the renumbered form in where A's HBM copy has one; the caller has decided that this solve may run renumbered */
+static LIS_INT renumber_enter(LIS_MATRIX A, renumber_t *st)
+{
+	lisd_mat *dm = MDEV(A);
+	liship_csr_plan_t in = NULL;
+	const int *rp = NULL, *ri = NULL;
+	const double *rv = NULL;
+	/* (several ranks: each rank renumbers its own rows and owned columns, the ghost columns and the halo slots keep their place -- lisc_halo_renumbered --; the
+	 * transposed copy of the swapped-in arrays has the np local columns as its rows like any rank's A^T, and the reverse halo adds the neighbours' sums at the
+	 * renumbered export rows: lisd_spmv_t / lisc_reduce_device read the same swapped tables) */
+	const int multi = lisg.nprocs > 1 && A->commtable;
+	LISCHK(lisd_mat_lazy_reorder(A));          /* the renumbered form is built LAZILY: by the first solve that finds the plan has served lisg.reorder_after products (lis_device.c) */
+	if (!(dm->type == LIS_MATRIX_CSR && !dm->split_jad && dm->plan && (A->np == A->n || (multi && A->matrix_type == LIS_MATRIX_CSR)) && dm->n == A->n &&
+	      liship_csr_plan_reordered_form(dm->plan, &in, &rp, &ri, &rv, &st->perm) == 0)) return LIS_SUCCESS;
+	if (multi) LISCHK(lisc_halo_renumbered(A, st->perm, liship_csr_plan_reordered_inner_rows(dm->plan)));
+	st->plan = dm->plan; st->ptr = dm->ptr; st->index = dm->index; st->value = dm->value;
+	dm->plan = in; dm->ptr = (int *)rp; dm->index = (int *)ri; dm->value = (double *)rv;
+	dm->solve_holds = 1;
+	st->on = 1;
+	swap_transposed(dm);
+	return LIS_SUCCESS;
+}
+
+/* the caller's matrix again, whatever happened, and the pool buffers back; harmless when renumber_enter did not run or did not swap */
+static void renumber_leave(LIS_MATRIX A, renumber_t *st)
+{
+	if (st->on) {
+		lisd_mat *dm = MDEV(A);
+		dm->plan = st->plan; dm->ptr = st->ptr; dm->index = st->index; dm->value = st->value;
+		dm->solve_holds = 0;
+		swap_transposed(dm);
+		lisc_halo_restore(A);
+	}
+	if (st->b) lisd_pool_put(st->b, st->bytes);
+	if (st->d) lisd_pool_put(st->d, st->bytes);
+}
+
+/* src[0 .. n) in the caller's numbering -> *out, a zeroed pool buffer (renumber_leave gives it back) in the plan's */
+static LIS_INT renumber_gather(renumber_t *st, int n, const double *src, double **out)
+{
+	LISCHK(lisd_pool_get(st->bytes, (void **)out));
+	HIPCHK(liship_memset(*out, 0, st->bytes, lisg.stream));
+	HIPCHK(liship_permute_gather_f64(n, st->perm, src, *out, lisg.stream));
+	return LIS_SUCCESS;
+}
+
+/* b: once over PCIe (or already resident); x: a private HBM iterate "xx" (ref :545-592), zero or copy of x */
+static LIS_INT vectors_in(ctx_t *c, LIS_VECTOR b, LIS_VECTOR x, renumber_t *rn)
+{
+	double *db, *dx0;
+	LISCHK(lisd_vec_in(b, &db));
+	c->b = db;
+	LISCHK(lisd_pool_get(c->len * sizeof(double), (void **)&c->x));
+	HIPCHK(liship_memset(c->x, 0, c->len * sizeof(double), lisg.stream));
+	if (rn->on) { LISCHK(renumber_gather(rn, c->n, db, &rn->b)); c->b = rn->b; }
+	if (!c->s->options[LIS_OPTIONS_INITGUESS_ZEROS]) {
+		LISCHK(lisd_vec_in(x, &dx0));
+		HIPCHK(rn->on ? liship_permute_gather_f64(c->n, rn->perm, dx0, c->x, lisg.stream) : liship_memcpy_d2d(c->x, dx0, sizeof(double) * (size_t)c->n, lisg.stream));
+	}
+	return LIS_SUCCESS;
+}
+
+/* CG + Jacobi on a constant diagonal (constant-coefficient stencils): z = r.*dinv is r*dinv[0] in every bit, and the fused CG passes need not read
+ * the array -- one counting pass per solve decides (every rank: the count is a collective, folded like any sum) */
+static LIS_INT jacobi_uniform(ctx_t *c)
+{
+	double d0 = 0.0, differ = 1.0;
+	if (c->n > 0) HIPCHK(liship_memcpy_d2h(&d0, c->dinv, sizeof(double), lisg.stream));
+	HIPCHK(liship_stream_synchronize(lisg.stream));
+	HIPCHK(liship_count_ne_f64(c->n, c->dinv, d0, lisg.reduce_out, lisg.reduce_work, lisg.stream));
+	LISCHK(lisd_fetch(1, &differ));
+	if (differ == 0.0) { c->duniform = 1; c->dconst = d0; }
+	lisg.last_uniform_jacobi = c->duniform;
+	return LIS_SUCCESS;
+}
+
+/* what the last solve did (lis_amd_last_solve_*) starts from nothing here, the one place; then the row's begin, and the Jacobi diagonal as the loops read it */
+static LIS_INT precon_begin(ctx_t *c, LIS_PRECON precon, renumber_t *rn)
+{
+	lisg.last_uniform_jacobi = 0;
+	lisg.last_graph_replays = 0;
+	lisg.last_renumbered = rn->on;
+	lisg.last_ssor = lisg.last_ilu = lisg.last_bjacobi = 0;
+	lisg.last_bjacobi_fallback = precon && lisi_is_registered(precon) && PPRIV(precon)->from_bjacobi && precon->precon_type == LIS_PRECON_TYPE_JACOBI;
+	LISCHK(c->pk->begin(c->A, c->s, &c->ps));
+	if (c->pk->type != LIS_PRECON_TYPE_JACOBI) return LIS_SUCCESS;
+	if (rn->on) { LISCHK(renumber_gather(rn, c->n, c->ps.dinv, &rn->d)); c->ps.dinv = rn->d; }
+	c->dinv = c->ps.dinv;
+	if (c->s->options[LIS_OPTIONS_SOLVER] == LIS_SOLVER_CG && !lisg.no_uniform_jacobi) LISCHK(jacobi_uniform(c));
+	return LIS_SUCCESS;
+}
+
+static LIS_INT dispatch(ctx_t *c)
+{
+	switch (c->s->options[LIS_OPTIONS_SOLVER]) {
+	case LIS_SOLVER_CG: case LIS_SOLVER_COCG: return run_cg(c);          /* real build: lis_cocg is lis_cg's arithmetic (lis_solver_cg.c:632-739) */
+	case LIS_SOLVER_BICG:     return run_bicg(c);
+	case LIS_SOLVER_BICGSTAB: return run_bicgstab(c);
+	case LIS_SOLVER_CGS:      return lisk_cgs(c);
+	case LIS_SOLVER_CR: case LIS_SOLVER_COCR: return lisk_cr(c);         /* and lis_cocr is lis_cr's (:1155-1274) */
+	case LIS_SOLVER_GPBICG:   return lisk_gpbicg(c);
+	case LIS_SOLVER_TFQMR:    return lisk_tfqmr(c);
+	case LIS_SOLVER_BICGSAFE: return lisk_bicgsafe(c);
+	case LIS_SOLVER_ORTHOMIN: return lisk_orthomin(c);
+	case LIS_SOLVER_BICR:     return lisk_bicr(c);
+	case LIS_SOLVER_CRS:      return lisk_crs(c);
+	case LIS_SOLVER_BICRSTAB: return lisk_bicrstab(c);
+	case LIS_SOLVER_GPBICR:   return lisk_gpbicr(c);
+	case LIS_SOLVER_BICRSAFE: return lisk_bicrsafe(c);
+	case LIS_SOLVER_FGMRES:   return lisk_fgmres(c);
+	case LIS_SOLVER_MINRES:   return lisk_minres(c);
+	case LIS_SOLVER_IDRS: case LIS_SOLVER_IDR1: return lisk_idrs(c);
+	case LIS_SOLVER_BICGSTABL: return lisk_bicgstabl(c);
+	case LIS_SOLVER_JACOBI:   return lisk_jacobi(c);
+	default:                  return run_gmres(c);
+	}
+}
+
+/* xx -> x (ref :890), and the stream drained */
+static LIS_INT vector_out(ctx_t *c, LIS_VECTOR x, LIS_INT scale, const renumber_t *rn)
+{
+	double *dx, *dd;
+	LISCHK(lisd_vec_out(x, &dx));
+	if (scale == LIS_SCALE_SYMM_DIAG) {             /* x = xx .* d  (ref :876-885) */
+		LISCHK(lisd_vec_in(c->s->d, &dd));
+		HIPCHK(liship_pmul_f64(c->n, c->x, dd, dx, lisg.stream));
+	} else if (rn->on) HIPCHK(liship_permute_scatter_f64(c->n, rn->perm, c->x, dx, lisg.stream));
+	else HIPCHK(liship_memcpy_d2d(dx, c->x, sizeof(double) * (size_t)c->n, lisg.stream));
+	LISCHK(lisd_vec_done(x));
+	HIPCHK(liship_stream_synchronize(lisg.stream));
+	return LIS_SUCCESS;
+}
+
+LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER solver, LIS_PRECON precon)
+{
+	const LIS_INT nsolver = solver->options[LIS_OPTIONS_SOLVER], storage = solver->options[LIS_OPTIONS_STORAGE];
+	const LIS_INT output = solver->options[LIS_OPTIONS_OUTPUT];
+	LIS_INT err = 0, scale;
+	renumber_t rn;
+	ctx_t c;
+	memset(&c, 0, sizeof(c));
+	memset(&rn, 0, sizeof(rn));
+	if (lisp_lazy()) lisp_check_handler();          /* a SIGSEGV handler the program installed since would take the protected pages' faults away */
+	LISCHK(check_options(A, b, x, solver));
+	if ((err = scale_system(A, b, solver, &scale))) { solver->retcode = err; return err; }
 
 	double t_itime = lis_wtime();
-	/* -storage: the caller's matrix itself is converted and stays converted (ref lis_matrix_convert_self,
-	 * lis_matrix_ops.c:326-372) */
+	/* -storage: the caller's matrix itself is converted and stays converted (ref lis_matrix_convert_self, lis_matrix_ops.c:326-372) */
 	if (storage && storage != A->matrix_type) {
 		err = lisi_matrix_retype(A, storage, storage == LIS_MATRIX_BSR ? solver->options[LIS_OPTIONS_STORAGE_BLOCK] : 0);
 		if (err) { solver->retcode = err; return err; }
 	}
+	if (output) banner(A, solver, precon);
 
-	if (output) {
-		lis_printf(LIS_COMM_WORLD, "initial vector x      : %s\n", solver->options[LIS_OPTIONS_INITGUESS_ZEROS] ? "all components set to 0" : "user defined");
-		lis_printf(LIS_COMM_WORLD, "precision             : double\n");
-		lis_printf(LIS_COMM_WORLD, "linear solver         : %s\n", solver_names[nsolver]);
-		lis_printf(LIS_COMM_WORLD, "preconditioner        : %s\n", precon_names[precon->precon_type]);
-		if (conv == LIS_CONV_COND_NRM2_R) lis_printf(LIS_COMM_WORLD, "convergence condition : ||b-Ax||_2 <= %6.1e * ||b-Ax_0||_2\n", tol);
-		if (Awork->matrix_type == LIS_MATRIX_BSR) lis_printf(LIS_COMM_WORLD, "matrix storage format : %s(%D x %D)\n", storage_names[Awork->matrix_type - 1], Awork->bnr, Awork->bnc);
-		else lis_printf(LIS_COMM_WORLD, "matrix storage format : %s\n", storage_names[Awork->matrix_type - 1]);
-	}
+	c.s = solver; c.A = A; c.n = A->n;
+	c.output = output; c.maxiter = solver->options[LIS_OPTIONS_MAXITER];
+	c.pk = lisi_precon_kind_of(precon ? precon->precon_type : LIS_PRECON_TYPE_NONE);
+	if (!c.pk) c.pk = lisi_precon_kind_of(LIS_PRECON_TYPE_NONE);
+	if ((err = lisd_mat_ready(A))) goto out;
+	c.len = work_len(A);
+	rn.bytes = c.len * sizeof(double);
+	/* may this solve run renumbered?  Not with a preconditioner that depends on the numbering (by_calls), nor scaled, nor in the reference-order mode.  A^T x: the
+	 * HBM copy is transposed in HBM (lis_matvech.c) -- of an unsplit CSR matrix, that is P A P^T's while it is swapped in; it gets a set of fields of its own */
+	const int t_ok = !solver_needs_transpose(nsolver) || (A->matrix_type == LIS_MATRIX_CSR && !A->is_splited);
+	const int may_renumber = !c.pk->by_calls && !scale && !A->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok;
+	if (may_renumber && (err = renumber_enter(A, &rn))) goto out;
+	if ((err = vectors_in(&c, b, x, &rn))) goto out;
+	solver->precon = precon;
+	if ((err = precon_begin(&c, precon, &rn))) goto out;
+	solver->x = NULL; solver->xx = x;
 
-	c.s = solver; c.A = Awork; c.n = A->n;
-	c.output = output; c.maxiter = maxiter;
-	if ((err = lisd_mat_ready(Awork))) goto out;
-	{
-		size_t len = (size_t)(Awork->np + Awork->pad) + 16;
-		if (Awork->matrix_type == LIS_MATRIX_BSR) {
-			const size_t a = (size_t)Awork->nc * Awork->bnc + 16, bb = (size_t)Awork->nr * Awork->bnr + 16;
-			if (a > len) len = a;
-			if (bb > len) len = bb;
-		}
-		c.len = len;
-	}
-	/* A plan that renumbered the matrix (liship.h: liship_csr_plan_reorder -- the caller's numbering has no locality): the WHOLE solve runs in the plan's numbering.
-	 * b, x0 and 1/diag are gathered once, the iterations see P A P^T as the matrix (its plan with its fused reductions, its arrays), x is scattered back at the end:
-	 * no product pays for a permutation.  The same recurrences on renumbered vectors; their sums fold in another order, so not in the reference-order mode. */
-	{
-		lisd_mat *dm = MDEV(Awork);
-		const int needs_t = nsolver == LIS_SOLVER_BICG || nsolver == LIS_SOLVER_BICR || nsolver == LIS_SOLVER_CRS || nsolver == LIS_SOLVER_BICRSTAB ||
-		                    nsolver == LIS_SOLVER_GPBICR || nsolver == LIS_SOLVER_BICRSAFE;
-		liship_csr_plan_t in = NULL;
-		const int *rp = NULL, *ri = NULL;
-		const double *rv = NULL;
-		/* A^T x: the HBM copy is transposed in HBM (lis_matvech.c) -- of an unsplit CSR matrix, that is P A P^T's while it is swapped in; it gets a set of fields of its own */
-		/* (several ranks: each rank renumbers its own rows and owned columns, the ghost columns and the halo slots keep their place -- lisc_halo_renumbered --; the
-		 * transposed copy of the swapped-in arrays has the np local columns as its rows like any rank's A^T, and the reverse halo adds the neighbours' sums at the
-		 * renumbered export rows: lisd_spmv_t / lisc_reduce_device read the same swapped tables) */
-		const int t_ok = !needs_t || (Awork->matrix_type == LIS_MATRIX_CSR && !Awork->is_splited);
-		const int multi = lisg.nprocs > 1 && Awork->commtable;
-		/* the renumbered form is built LAZILY: by the first solve that finds the plan has served lisg.reorder_after products (lis_device.c) */
-		if (!sweeps && !bjacobi && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok) { if ((err = lisd_mat_lazy_reorder(Awork))) goto out; }
-		if (!sweeps && !bjacobi && !scale && !Awork->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok && dm->type == LIS_MATRIX_CSR && !dm->split_jad &&
-		    dm->plan && (Awork->np == Awork->n || (multi && Awork->matrix_type == LIS_MATRIX_CSR)) && dm->n == Awork->n && liship_csr_plan_reordered_form(dm->plan, &in, &rp, &ri, &rv, &renum) == 0) {
-			if (multi && (err = lisc_halo_renumbered(Awork, renum, liship_csr_plan_reordered_inner_rows(dm->plan)))) goto out;
-			held_plan = dm->plan; held_ptr = dm->ptr; held_index = dm->index; held_value = dm->value;
-			dm->plan = in; dm->ptr = (int *)rp; dm->index = (int *)ri; dm->value = (double *)rv;
-			dm->solve_holds = 1;
-			renumbered = 1;
-			swap_transposed(dm);
-		}
-	}
-	/* b: once over PCIe (or already resident); x: a private HBM iterate "xx" (ref :545-592), zero or copy of x */
-	{
-		double *db, *dx0;
-		if ((err = lisd_vec_in(b, &db))) goto out;
-		c.b = db;
-		if ((err = lisd_pool_get(c.len * sizeof(double), (void **)&c.x))) goto out;
-		int rc = liship_memset(c.x, 0, c.len * sizeof(double), lisg.stream);
-		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-		if (renumbered) {
-			if ((err = lisd_pool_get(c.len * sizeof(double), (void **)&renum_b))) goto out;
-			if ((rc = liship_memset(renum_b, 0, c.len * sizeof(double), lisg.stream)) || (rc = liship_permute_gather_f64(A->n, renum, db, renum_b, lisg.stream))) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-			c.b = renum_b;
-		}
-		if (!solver->options[LIS_OPTIONS_INITGUESS_ZEROS]) {
-			if ((err = lisd_vec_in(x, &dx0))) goto out;
-			rc = renumbered ? liship_permute_gather_f64(A->n, renum, dx0, c.x, lisg.stream) : liship_memcpy_d2d(c.x, dx0, sizeof(double) * (size_t)A->n, lisg.stream);
-			if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-		}
-	}
-	lisg.last_uniform_jacobi = 0;
-	lisg.last_graph_replays = 0;
-	lisg.last_renumbered = renumbered;
-	lisg.last_ssor = 0;
-	lisg.last_ilu = 0;
-	lisg.last_bjacobi = 0;
-	lisg.last_bjacobi_fallback = precon && lisi_is_registered(precon) && PPRIV(precon)->from_bjacobi && precon->precon_type == LIS_PRECON_TYPE_JACOBI;
-	if (bjacobi) {
-		c.bjacobi = 1;
-		if ((err = lisd_bjacobi_begin(Awork))) goto out;
-	}
-	if (ilu) {
-		c.sweeps = 1; c.ilu = 1; c.ilu_fill = (int)solver->options[LIS_OPTIONS_FILL];
-		if ((err = lisd_ilu_begin(Awork, c.ilu_fill, &c.sweeps_T))) goto out;
-	} else if (sweeps) {
-		c.sweeps = 1;
-		if ((err = lisd_ssor_begin(Awork, &c.sweeps_T))) goto out;
-	}
-	if (precon && precon->precon_type == LIS_PRECON_TYPE_JACOBI) {
-		if ((err = lisd_vec_in(precon->D, &c.dinv))) goto out;
-		if (renumbered) {
-			int rc;
-			if ((err = lisd_pool_get(c.len * sizeof(double), (void **)&renum_d))) goto out;
-			if ((rc = liship_memset(renum_d, 0, c.len * sizeof(double), lisg.stream)) || (rc = liship_permute_gather_f64(A->n, renum, c.dinv, renum_d, lisg.stream))) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-			c.dinv = renum_d;
-		}
-		if (nsolver == LIS_SOLVER_CG && !lisg.no_uniform_jacobi) {        /* (every rank: the count below is a collective) */
-			/* a constant diagonal (constant-coefficient stencils): z = r.*dinv is r*dinv[0] in every bit, and the fused CG passes
-			 * need not read the array -- one counting pass per solve decides (all ranks: the count is folded like any sum) */
-			double d0 = 0.0, differ = 1.0;
-			int rc = A->n > 0 ? liship_memcpy_d2h(&d0, c.dinv, sizeof(double), lisg.stream) : 0;
-			if (!rc) rc = liship_stream_synchronize(lisg.stream);
-			if (!rc) rc = liship_count_ne_f64(A->n, c.dinv, d0, lisg.reduce_out, lisg.reduce_work, lisg.stream);
-			if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-			if ((err = lisd_fetch(1, &differ))) goto out;
-			if (differ == 0.0) { c.duniform = 1; c.dconst = d0; }
-			lisg.last_uniform_jacobi = c.duniform;
-		}
-	}
-	solver->x = NULL; solver->xx = x; solver->precon = precon;
-
-	switch (nsolver) {
-	case LIS_SOLVER_CG:       err = run_cg(&c); break;
-	case LIS_SOLVER_BICG:     err = run_bicg(&c); break;
-	case LIS_SOLVER_BICGSTAB: err = run_bicgstab(&c); break;
-	case LIS_SOLVER_CGS:      err = lisk_cgs(&c); break;
-	case LIS_SOLVER_CR:       err = lisk_cr(&c); break;
-	case LIS_SOLVER_GPBICG:   err = lisk_gpbicg(&c); break;
-	case LIS_SOLVER_TFQMR:    err = lisk_tfqmr(&c); break;
-	case LIS_SOLVER_BICGSAFE: err = lisk_bicgsafe(&c); break;
-	case LIS_SOLVER_ORTHOMIN: err = lisk_orthomin(&c); break;
-	case LIS_SOLVER_BICR:     err = lisk_bicr(&c); break;
-	case LIS_SOLVER_CRS:      err = lisk_crs(&c); break;
-	case LIS_SOLVER_BICRSTAB: err = lisk_bicrstab(&c); break;
-	case LIS_SOLVER_GPBICR:   err = lisk_gpbicr(&c); break;
-	case LIS_SOLVER_BICRSAFE: err = lisk_bicrsafe(&c); break;
-	case LIS_SOLVER_FGMRES:   err = lisk_fgmres(&c); break;
-	case LIS_SOLVER_MINRES:   err = lisk_minres(&c); break;
-	case LIS_SOLVER_IDRS: case LIS_SOLVER_IDR1: err = lisk_idrs(&c); break;
-	case LIS_SOLVER_BICGSTABL: err = lisk_bicgstabl(&c); break;
-	case LIS_SOLVER_JACOBI:   err = lisk_jacobi(&c); break;
-	case LIS_SOLVER_COCG:     err = run_cg(&c); break;          /* real build: lis_cocg is lis_cg's arithmetic (lis_solver_cg.c:632-739) */
-	case LIS_SOLVER_COCR:     err = lisk_cr(&c); break;         /* and lis_cocr is lis_cr's (:1155-1274) */
-	default:                  err = run_gmres(&c); break;
-	}
+	err = dispatch(&c);
 	const LIS_INT solver_code = err;
 	if (err == LIS_MAXITER || err == LIS_BREAKDOWN) err = 0;    /* reported through retcode only (ref :874,952) */
 	else if (err) goto out;
 	solver->retcode = solver_code;
 
-	/* xx -> x (ref :890) */
-	{
-		double *dx;
-		if ((err = lisd_vec_out(x, &dx))) goto out;
-		int rc;
-		if (scale == LIS_SCALE_SYMM_DIAG) {             /* x = xx .* d  (ref :876-885) */
-			double *dd;
-			if ((err = lisd_vec_in(solver->d, &dd))) goto out;
-			rc = liship_pmul_f64(A->n, c.x, dd, dx, lisg.stream);
-		} else if (renumbered) rc = liship_permute_scatter_f64(A->n, renum, c.x, dx, lisg.stream);
-		else rc = liship_memcpy_d2d(dx, c.x, sizeof(double) * (size_t)A->n, lisg.stream);
-		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-		if ((err = lisd_vec_done(x))) goto out;
-	}
-	{
-		int rc = liship_stream_synchronize(lisg.stream);
-		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; }
-	}
+	if ((err = vector_out(&c, x, scale, &rn))) goto out;
 	t_itime = lis_wtime() - t_itime;
 	solver->itime = t_itime; solver->p_i_time = 0.0; solver->p_c_time = 0.0; solver->ptime = 0.0;
 	solver->time = t_itime;
@@ -1311,15 +1224,7 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 		else lis_printf(LIS_COMM_WORLD, "linear solver status  : normal end\n\n");
 	}
 out:
-	if (renumbered) {           /* the caller's matrix again, whatever happened */
-		lisd_mat *dm = MDEV(Awork);
-		dm->plan = held_plan; dm->ptr = held_ptr; dm->index = held_index; dm->value = held_value;
-		dm->solve_holds = 0;
-		swap_transposed(dm);
-		lisc_halo_restore(Awork);
-	}
-	if (renum_b) lisd_pool_put(renum_b, c.len * sizeof(double));
-	if (renum_d) lisd_pool_put(renum_d, c.len * sizeof(double));
+	renumber_leave(A, &rn);
 	if (c.x) lisd_pool_put(c.x, c.len * sizeof(double));
 	solver->precon = NULL;
 	if (err) solver->retcode = err;

@@ -1,11 +1,13 @@
 /*
- * lis_solver_more.c -- the other short-recurrence Krylov solvers of Lis on the same HBM work vectors and the
- * same kernels: CGS, CR, GPBiCG, TFQMR, BiCGSafe, Orthomin(m).
+ * lis_solver_more.c -- every Krylov loop that is one kernel per reference call, on the same HBM work vectors and the same
+ * kernels: CG, BiCG and BiCGSTAB in that form (lisk_cg / lisk_bicg / lisk_bicgstab: what -p ssor, ilu and bjacobi iterate with,
+ * and LIS_AMD_NO_FUSION=1) and the other short-recurrence solvers of Lis: CGS, CR, GPBiCG, TFQMR, BiCGSafe,
+ * Orthomin(m).
  *
  * Each loop issues the reference's vector operations in the reference's order, one kernel per call
  * (element-wise results are bit-identical, reductions are the deterministic trees of vector_ops.hip), so the
- * recurrences see the same numbers as the CPU path up to the reduction order.  No pass fusion here: these are
- * coverage, CG / BiCG / BiCGSTAB / GMRES in lis_solver.c are the tuned ones.
+ * recurrences see the same numbers as the CPU path up to the reduction order, written in the vocabulary of lis_krylov.h.
+ * No pass fusion here: the fused and device-driven CG / BiCG / BiCGSTAB and GMRES are in lis_solver.c.
  *   CGS       src/solver/lis_solver_cgs.c:134-276        CR         lis_solver_cg.c:821-940
  *   GPBiCG    lis_solver_gpbicg.c:145-351                TFQMR      lis_solver_qmr.c:113-299
  *   BiCGSafe  lis_solver_bicgsafe.c:145-322              Orthomin   lis_solver_orthomin.c:124-250
@@ -18,17 +20,131 @@
  */
 #include "lis_krylov.h"
 
-#define AXPY(a, x, y)      KTRY(liship_axpy_f64(n, (a), (x), (y), lisg.stream))          /* y += a x     */
-#define XPAY(x, a, y)      KTRY(liship_xpay_f64(n, (x), (a), (y), lisg.stream))          /* y = x + a y  */
-#define AXPYZ(a, x, y, z)  KTRY(liship_axpyz_f64(n, (a), (x), (y), (z), lisg.stream))    /* z = a x + y  */
-#define SCALE(a, x)        KTRY(liship_scale_f64(n, (a), (x), lisg.stream))
-#define COPY(src, dst)     TRY(d_copy(c, (src), (dst)))
-#define DOT(x, y, out)     TRY(lisd_dot(n, (x), (y), (out)))
-#define MATVEC(x, y)       TRY(d_matvec(c, (x), (y)))
-#define PSOLVE(r, z)       TRY(d_psolve(c, (r), (z)))
-#define PSOLVEH(r, z)      TRY(d_psolveh(c, (r), (z)))
-#define RESID(r, out)      TRY(d_resid(c, (r), (out)))
-#define FINISH(code) do { s->retcode = (code); s->iter = iter; s->resid = nrm2; err = ((code) == LIS_SUCCESS) ? 0 : (code); goto done; } while (0)
+/* CG one call per reference statement (lis_solver_cg.c:176-215): what LIS_AMD_NO_FUSION=1 and a preconditioner that is no point diagonal run */
+LIS_INT lisk_cg(ctx_t *c)
+{
+	LIS_SOLVER s = c->s;
+	LIS_INT err = 0, iter = 0;
+	const int n = c->n;
+	double nrm2 = 0.0, alpha, beta, rho, rho_old = 1.0, dot_pq;
+	TRY(work_alloc(c, 4));
+	double *z = c->work[0], *q = c->work[1], *r = c->work[2], *p = c->work[3];
+	START(r);
+	KTRY(liship_set_all_f64(n, 0.0, p, lisg.stream));
+	for (iter = 1; iter <= c->maxiter; iter++) {
+		PSOLVE(r, z);
+		DOT(r, z, &rho);
+		beta = rho / rho_old;
+		XPAY(z, beta, p);
+		MATVEC(p, q);
+		DOT(p, q, &dot_pq);
+		if (dot_pq == 0.0) FINISH(LIS_BREAKDOWN);
+		alpha = rho / dot_pq;
+		AXPY(alpha, p, c->x);
+		AXPY(-alpha, q, r);
+		RESID(r, &nrm2);
+		note(c, iter, nrm2);
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
+		rho_old = rho;
+	}
+	FINISH(LIS_MAXITER);
+done:
+	work_free(c);
+	return err;
+}
+
+/* BiCG one call per reference statement (lis_solver_bicg.c:186-271): the form a preconditioner that is no point diagonal needs, M^-H r~ by PSOLVEH */
+LIS_INT lisk_bicg(ctx_t *c)
+{
+	LIS_SOLVER s = c->s;
+	LIS_INT err = 0, iter = 0;
+	const int n = c->n;
+	double nrm2 = 0.0, alpha, beta, rho, rho_old = 1.0, d1;
+	TRY(work_alloc(c, 6));
+	double *r = c->work[0], *rtld = c->work[1], *z = c->work[2], *ztld = c->work[3], *p = c->work[4], *ptld = c->work[5];
+	double *q = z, *qtld = ztld;                       /* aliases as in the reference (:167-168) */
+	START(r);
+	COPY(r, rtld);                                     /* shadow residual = r0 (lis_solver.c:1862) */
+	KTRY(liship_set_all_f64(n, 0.0, p, lisg.stream));
+	KTRY(liship_set_all_f64(n, 0.0, ptld, lisg.stream));
+	for (iter = 1; iter <= c->maxiter; iter++) {
+		PSOLVE(r, z);
+		PSOLVEH(rtld, ztld);
+		DOT(rtld, z, &rho);
+		if (rho == 0.0) FINISH(LIS_BREAKDOWN);
+		beta = rho / rho_old;
+		XPAY(z, beta, p);
+		MATVEC(p, q);
+		XPAY(ztld, beta, ptld);
+		TRY(lisd_spmv_t(c->A, ptld, qtld));
+		DOT(ptld, q, &d1);
+		if (d1 == 0.0) FINISH(LIS_BREAKDOWN);
+		alpha = rho / d1;
+		AXPY(alpha, p, c->x);
+		AXPY(-alpha, q, r);
+		RESID(r, &nrm2);
+		note(c, iter, nrm2);
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
+		AXPY(-alpha, qtld, rtld);
+		rho_old = rho;
+	}
+	FINISH(LIS_MAXITER);
+done:
+	work_free(c);
+	return err;
+}
+
+/* BiCGSTAB one call per reference statement (lis_solver_bicgstab.c:186-290) */
+LIS_INT lisk_bicgstab(ctx_t *c)
+{
+	LIS_SOLVER s = c->s;
+	LIS_INT err = 0, iter = 0;
+	const int n = c->n;
+	double nrm2 = 0.0, alpha = 1.0, omega = 1.0, rho_old = 1.0, rho, beta, d1, d2[2];
+	TRY(work_alloc(c, 7));
+	double *rtld = c->work[0], *r = c->work[1], *t = c->work[2], *p = c->work[3], *v = c->work[4],
+	       *phat = c->work[5], *shat = c->work[6];
+	double *sv = r;                                    /* s aliases r: lis_solver_bicgstab.c:160-161 */
+	START(r);
+	COPY(r, rtld);                                     /* shadow residual = r0 (lis_solver.c:1862) */
+	for (iter = 1; iter <= c->maxiter; iter++) {
+		DOT(rtld, r, &rho);
+		if (rho == 0.0) FINISH(LIS_BREAKDOWN);
+		if (iter == 1) COPY(r, p);
+		else {
+			beta = (rho / rho_old) * (alpha / omega);
+			AXPY(-omega, v, p);
+			XPAY(r, beta, p);
+		}
+		PSOLVE(p, phat);
+		MATVEC(phat, v);
+		DOT(rtld, v, &d1);
+		alpha = rho / d1;
+		AXPY(-alpha, v, r);
+		RESID(sv, &nrm2);
+		if (nrm2 <= c->tol) {
+			note(c, iter, nrm2);
+			AXPY(alpha, phat, c->x);
+			FINISH(LIS_SUCCESS);
+		}
+		PSOLVE(sv, shat);
+		MATVEC(shat, t);
+		TRY(lisd_dot2(n, t, sv, d2));                   /* <t,s> and <t,t> in one pass (:267-268) */
+		omega = d2[0] / d2[1];
+		AXPY(alpha, phat, c->x);
+		AXPY(omega, shat, c->x);
+		AXPY(-omega, t, r);
+		RESID(r, &nrm2);
+		note(c, iter, nrm2);
+		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
+		if (omega == 0.0) FINISH(LIS_BREAKDOWN);
+		rho_old = rho;
+	}
+	FINISH(LIS_MAXITER);
+done:
+	work_free(c);
+	return err;
+}
 
 LIS_INT lisk_cgs(ctx_t *c)
 {
@@ -39,8 +155,7 @@ LIS_INT lisk_cgs(ctx_t *c)
 	TRY(work_alloc(c, 7));
 	double *rtld = c->work[0], *r = c->work[1], *p = c->work[2], *phat = c->work[3], *q = c->work[4],
 	       *qhat = c->work[5], *u = c->work[5], *uhat = c->work[6], *vhat = c->work[6];      /* aliases as in the reference */
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, rtld);
 	for (iter = 1; iter <= c->maxiter; iter++) {
 		DOT(rtld, r, &rho);
@@ -79,8 +194,7 @@ LIS_INT lisk_cr(ctx_t *c)
 	double nrm2 = 0.0, rho, alpha, beta, dot_rq, dot_zq;
 	TRY(work_alloc(c, 6));
 	double *z = c->work[0], *q = c->work[1], *r = c->work[2], *p = c->work[3], *qtld = c->work[4], *az = c->work[5];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	PSOLVE(r, p);
 	MATVEC(p, q);
 	COPY(p, z);
@@ -133,8 +247,7 @@ static LIS_INT gpbi(ctx_t *c, int cr)
 	double *rtld = c->work[0], *r = c->work[1], *mr = c->work[2], *p = c->work[3], *ap = c->work[4], *map = c->work[5],
 	       *t = c->work[6], *mt = c->work[7], *amt = c->work[8], *u = c->work[9], *y = c->work[10], *w = c->work[11],
 	       *z = c->work[12], *mt_old = c->work[13];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	if (cr) { COPY(r, p); TRY(lisd_spmv_t(c->A, p, rtld)); } else COPY(r, rtld);
 	PSOLVE(r, p);
 	DOT(rtld, cr ? p : r, &rho_old);
@@ -197,8 +310,7 @@ LIS_INT lisk_tfqmr(ctx_t *c)
 	TRY(work_alloc(c, 9));
 	double *r = c->work[0], *rtld = c->work[1], *u = c->work[2], *p = c->work[3], *d = c->work[4], *t = c->work[5],
 	       *t1 = c->work[6], *q = c->work[7], *v = c->work[8];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, rtld);
 	COPY(r, p);
 	COPY(r, u);
@@ -257,8 +369,7 @@ LIS_INT lisk_bicgsafe(ctx_t *c)
 	TRY(work_alloc(c, 12));
 	double *rtld = c->work[0], *r = c->work[1], *mr = c->work[2], *amr = c->work[3], *p = c->work[4], *ap = c->work[5],
 	       *t = c->work[6], *mt = c->work[7], *y = c->work[8], *u = c->work[9], *z = c->work[10], *au = c->work[11];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, rtld);
 	PSOLVE(r, mr);
 	MATVEC(mr, amr);
@@ -316,8 +427,7 @@ LIS_INT lisk_orthomin(ctx_t *c)
 	if (!dotsave) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", m + 1); goto done; }
 	TRY(work_alloc(c, 2 + 3 * (m + 1)));
 	double *r = c->work[0], *rtld = c->work[1], **p = &c->work[2], **ap = &c->work[(m + 1) + 2], **aptld = &c->work[2 * (m + 1) + 2];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	PSOLVE(r, rtld);                              /* the M != NULL form of the initial residual (lis_solver.c:1083-1087) */
 	while (iter <= c->maxiter) {
 		const int ip = (iter - 1) % (m + 1);
@@ -363,8 +473,7 @@ LIS_INT lisk_bicr(ctx_t *c)
 	TRY(work_alloc(c, 10));
 	double *r = c->work[0], *rtld = c->work[1], *z = c->work[2], *ztld = c->work[3], *p = c->work[4], *ptld = c->work[5],
 	       *ap = c->work[6], *az = c->work[7], *map = c->work[8], *aptld = c->work[9];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, rtld);
 	PSOLVE(r, z);
 	PSOLVEH(rtld, ztld);                          /* M^-H: M^-1 for none / Jacobi, the transposed sweeps for SSOR / ILU */
@@ -410,8 +519,7 @@ LIS_INT lisk_crs(ctx_t *c)
 	TRY(work_alloc(c, 6));
 	double *r = c->work[0], *rtld = c->work[1], *p = c->work[2], *z = c->work[3], *u = c->work[3], *uq = c->work[3],
 	       *q = c->work[4], *ap = c->work[4], *map = c->work[5], *auq = c->work[5];           /* aliases as in the reference */
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, p);
 	TRY(lisd_spmv_t(c->A, p, rtld));              /* shadow residual A^T r0 */
 	KTRY(liship_set_all_f64(n, 0.0, q, lisg.stream));
@@ -454,8 +562,7 @@ LIS_INT lisk_bicrstab(ctx_t *c)
 	TRY(work_alloc(c, 9));
 	double *rtld = c->work[0], *r = c->work[1], *sv = c->work[2], *ms = c->work[3], *ams = c->work[4], *p = c->work[5],
 	       *ap = c->work[6], *map = c->work[7], *z = c->work[8];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, p);
 	TRY(lisd_spmv_t(c->A, p, rtld));
 	PSOLVE(r, z);
@@ -508,8 +615,7 @@ LIS_INT lisk_bicrsafe(ctx_t *c)
 	double *rtld = c->work[0], *r = c->work[1], *mr = c->work[2], *amr = c->work[3], *p = c->work[4], *ap = c->work[5],
 	       *map = c->work[6], *my = c->work[7], *y = c->work[8], *u = c->work[9], *z = c->work[10], *au = c->work[11],
 	       *artld = c->work[12];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	COPY(r, rtld);
 	TRY(lisd_spmv_t(c->A, rtld, artld));
 	PSOLVE(r, mr);
@@ -574,8 +680,7 @@ LIS_INT lisk_fgmres(ctx_t *c)
 	if (!h || !g) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", ld); goto done; }
 	TRY(work_alloc(c, 2 * m + 3));
 	double **z = &c->work[0], **v = &c->work[m + 1];
-	int st = initial_residual(c, v[0]);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(v[0]);
 	bnrm2 = c->bnrm;
 	rnorm = 1.0 / bnrm2;
 	while (iter < c->maxiter) {
@@ -598,34 +703,11 @@ LIS_INT lisk_fgmres(ctx_t *c)
 			TRY(lisd_nrm2(n, v[i1], &t));
 			hc[i1] = t;
 			SCALE(1.0 / t, v[i1]);
-			for (int k = 1; k <= ii; k++) {
-				const int jj = k - 1;
-				const double tt = hc[jj];
-				double aa = h[jj + CS] * tt;  aa += h[jj + SN] * hc[k];
-				double bb = -h[jj + SN] * tt; bb += h[jj + CS] * hc[k];
-				hc[jj] = aa; hc[k] = bb;
-			}
-			double aa = hc[ii], bb = hc[i1];
-			double rr = sqrt(aa * aa + bb * bb);
-			if (rr == 0.0) rr = 1.0e-17;
-			h[ii + CS] = aa / rr;
-			h[ii + SN] = bb / rr;
-			g[i1] = -h[ii + SN] * g[ii];
-			g[ii] =  h[ii + CS] * g[ii];
-			aa  = h[ii + CS] * hc[ii];
-			aa += h[ii + SN] * hc[i1];
-			hc[ii] = aa;
-			nrm2 = fabs(g[i1]);
+			nrm2 = givens_column(h, hc, g, ii, CS, SN);
 			note(c, iter, nrm2);
 			if (c->tol >= nrm2) break;
 		} while (i < m && iter < c->maxiter);
-		g[ii] = g[ii] / h[ii + (size_t)ii * ld];
-		for (int k = 1; k <= ii; k++) {
-			const int jj = ii - k;
-			double tt = g[jj];
-			for (int j = jj + 1; j <= ii; j++) tt -= h[jj + (size_t)j * ld] * g[j];
-			g[jj] = tt / h[jj + (size_t)jj * ld];
-		}
+		hessenberg_solve(h, g, ii, ld);
 		for (int j = 0; j <= ii; j++) AXPY(g[j], z[j], c->x);
 		if (c->tol >= nrm2) FINISH(LIS_SUCCESS);
 		MATVEC(c->x, v[0]);
@@ -633,7 +715,8 @@ LIS_INT lisk_fgmres(ctx_t *c)
 		TRY(lisd_nrm2(n, v[0], &rnorm));
 		bnrm2 = 1.0 / rnorm;
 	}
-	s->retcode = LIS_MAXITER; s->iter = iter + 1; s->resid = nrm2; err = LIS_MAXITER;
+	iter++;                                            /* the reference reports iter + 1 here (lis_solver_gmres.c:1298) */
+	FINISH(LIS_MAXITER);
 done:
 	work_free(c);
 	free(h); free(g);
@@ -809,8 +892,7 @@ LIS_INT lisk_idrs(ctx_t *c)
 	TRY(work_alloc(c, 4 + 3 * sd));
 	double *r = c->work[0], *t = c->work[1], *v = c->work[2], *av = c->work[3];
 	double **dX = &c->work[4], **P = &c->work[4 + sd], **dR = &c->work[4 + 2 * sd];
-	int st = initial_residual(c, r);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r);
 	{
 		mt19937 g;
 		const unsigned long key[4] = {0x123, 0x234, 0x345, 0x456};
@@ -908,8 +990,7 @@ LIS_INT lisk_bicgstabl(ctx_t *c)
 	double *gamma = tau + zd * zd, *gamma1 = gamma + zd, *gamma2 = gamma1 + zd, *sigma = gamma2 + zd;
 	TRY(work_alloc(c, 4 + 2 * (l + 1)));
 	double *rtld = c->work[0], *xp = c->work[1], *bp = c->work[2], *t = c->work[3], **r = &c->work[4], **u = &c->work[l + 1 + 4];
-	int st = initial_residual(c, r[0]);
-	if (st) { err = st < 0 ? -st : 0; goto done; }
+	START(r[0]);
 	COPY(r[0], rtld);
 	COPY(r[0], bp);
 	COPY(c->x, xp);

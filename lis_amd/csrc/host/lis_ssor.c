@@ -18,7 +18,6 @@
 #include <stdio.h>
 #include "lis_krylov.h"
 
-
 typedef lisi_sweep_t sweep_t;              /* lis_internal.h: shared with lis_ilu.c */
 
 typedef struct {
@@ -144,42 +143,44 @@ void lisi_ssor_wd_free(LIS_MATRIX A)
 	if (A->WD) { free(A->WD->value); free(A->WD); A->WD = NULL; }
 }
 
-/* ------------------------------------------------------------------ the solve's side (lis_krylov.h d_psolve / d_psolveh) */
-LIS_INT lisd_ssor_begin(LIS_MATRIX A, int *T)
+/* ------------------------------------------------------------------ the solve's side (the SSOR row of lisi_precon_kinds) */
+LIS_INT lisd_ssor_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st)
 {
 	const liship_sweep_t *f, *b;
 	const double *wd;
-	*T = lisi_sweep_blocks();
-	LISCHK(get_sweep(A, *T, SW_L, &f));
-	LISCHK(get_sweep(A, *T, SW_U, &b));
+	(void)solver;
+	st->A = A; st->n = A->n; st->T = lisi_sweep_blocks();
+	LISCHK(get_sweep(A, st->T, SW_L, &f));
+	LISCHK(get_sweep(A, st->T, SW_U, &b));
 	LISCHK(upload_wd(A, &wd));
-	lisg.last_ssor = 1; lisg.last_ssor_blocks = *T;
+	lisg.last_ssor = 1; lisg.last_ssor_blocks = st->T;
 	lisg.last_ssor_levels_fwd = f->nlev; lisg.last_ssor_levels_bwd = b->nlev;
 	lisg.last_ssor_launches = f->ngroups + b->ngroups;
 	return LIS_SUCCESS;
 }
 
-LIS_INT lisd_ssor_psolve(LIS_MATRIX A, int T, const double *b, double *x)
+/* the kernels of a solve with the sweep s1, then s2 (NULL: LOWER or UPPER alone); herm: X = B first (lis_matrix_solveh_csr :1774), then the scatter sweeps in place */
+static LIS_INT run_sweeps(const liship_sweep_t *s1, const liship_sweep_t *s2, int herm, int n, const double *wd, const double *b, double *x)
 {
-	const liship_sweep_t *f, *u;
-	LISCHK(get_sweep(A, T, SW_L, &f));
-	LISCHK(get_sweep(A, T, SW_U, &u));
-	const double *wd = ((lisd_ssor *)MDEV(A)->ssor)->wd;
-	HIPCHK(liship_sweep_f64(f, LISHIP_SWEEP_MUL, b, x, wd, lisg.stream));
-	HIPCHK(liship_sweep_f64(u, LISHIP_SWEEP_SUB, NULL, x, wd, lisg.stream));
+	if (!herm) {
+		HIPCHK(liship_sweep_f64(s1, LISHIP_SWEEP_MUL, b, x, wd, lisg.stream));
+		if (s2) HIPCHK(liship_sweep_f64(s2, LISHIP_SWEEP_SUB, NULL, x, wd, lisg.stream));
+		return LIS_SUCCESS;
+	}
+	if (x != b) HIPCHK(liship_memcpy_d2d(x, b, sizeof(double) * (size_t)n, lisg.stream));
+	if (s2) {
+		HIPCHK(liship_sweep_f64(s1, LISHIP_SWEEP_SCAT, x, x, wd, lisg.stream));
+		HIPCHK(liship_sweep_f64(s2, LISHIP_SWEEP_MUL, x, x, wd, lisg.stream));
+	} else HIPCHK(liship_sweep_f64(s1, LISHIP_SWEEP_MUL, x, x, wd, lisg.stream));
 	return LIS_SUCCESS;
 }
 
-LIS_INT lisd_ssor_psolveh(LIS_MATRIX A, int T, const double *b, double *x)
-{
-	const liship_sweep_t *ut, *lt;
-	LISCHK(get_sweep(A, T, SW_UT, &ut));
-	LISCHK(get_sweep(A, T, SW_LT, &lt));
-	const double *wd = ((lisd_ssor *)MDEV(A)->ssor)->wd;
-	if (b != x) HIPCHK(liship_memcpy_d2d(x, b, sizeof(double) * (size_t)A->n, lisg.stream));
-	HIPCHK(liship_sweep_f64(ut, LISHIP_SWEEP_SCAT, x, x, wd, lisg.stream));
-	HIPCHK(liship_sweep_f64(lt, LISHIP_SWEEP_MUL, x, x, wd, lisg.stream));
-	return LIS_SUCCESS;
+LIS_INT lisd_ssor_apply(const lisi_precon_state *st, int transposed, const double *b, double *x)
+{	/* x = M^-1 b, or M^-H b (b may be x): get_sweep finds the built sweep, or builds it again on a copy that a product rebuilt in mid-solve */
+	const liship_sweep_t *s1, *s2;
+	LISCHK(get_sweep(st->A, st->T, transposed ? SW_UT : SW_L, &s1));
+	LISCHK(get_sweep(st->A, st->T, transposed ? SW_LT : SW_U, &s2));
+	return run_sweeps(s1, s2, transposed, st->n, ((lisd_ssor *)MDEV(st->A)->ssor)->wd, b, x);
 }
 
 /* ------------------------------------------------------------------ lis_matrix_solve / lis_matrix_solveh (ref lis_matrix_ops.c, CSR only)
@@ -205,16 +206,7 @@ static LIS_INT solve_common(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT fl
 	LISCHK(lisd_vec_in(B, &db));
 	if (X == B) dx = db;
 	else LISCHK(lisd_vec_out(X, &dx));
-	if (!herm) {
-		HIPCHK(liship_sweep_f64(s1, LISHIP_SWEEP_MUL, db, dx, wd, lisg.stream));
-		if (s2) HIPCHK(liship_sweep_f64(s2, LISHIP_SWEEP_SUB, NULL, dx, wd, lisg.stream));
-	} else {                                      /* X = B first (lis_matrix_solveh_csr :1774), then the scatter sweeps in place */
-		if (dx != db) HIPCHK(liship_memcpy_d2d(dx, db, sizeof(double) * (size_t)A->n, lisg.stream));
-		if (s2) {
-			HIPCHK(liship_sweep_f64(s1, LISHIP_SWEEP_SCAT, dx, dx, wd, lisg.stream));
-			HIPCHK(liship_sweep_f64(s2, LISHIP_SWEEP_MUL, dx, dx, wd, lisg.stream));
-		} else HIPCHK(liship_sweep_f64(s1, LISHIP_SWEEP_MUL, dx, dx, wd, lisg.stream));
-	}
+	LISCHK(run_sweeps(s1, s2, herm, A->n, wd, db, dx));
 	return lisd_vec_done(X);
 }
 
@@ -261,21 +253,21 @@ LIS_INT lis_amd_ssor_sweep_info(LIS_MATRIX A, LIS_INT sweep, LIS_INT info[6])
 	return LIS_SUCCESS;
 }
 
-typedef struct { LIS_MATRIX A; int T; const double *b; double *x; } psolve_args;
-static LIS_INT psolve_once(void *ctx) { const psolve_args *p = (const psolve_args *)ctx; return lisd_ssor_psolve(p->A, p->T, p->b, p->x); }
+typedef struct { lisi_precon_state st; const double *b; double *x; } psolve_args;
+static LIS_INT psolve_once(void *ctx) { const psolve_args *p = (const psolve_args *)ctx; return lisd_ssor_apply(&p->st, 0, p->b, p->x); }
 
 LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms)
 {	/* reps psolves X = M^-1 B on the library's stream, each timed by device events (ms[k]) */
 	LISCHK(check_split(A));
 	LISCHK(lisd_mat_ready(A));
 	const double *wd;
-	int T = lisi_sweep_blocks();
-	LISCHK(lisd_ssor_begin(A, &T));
+	psolve_args args;
+	LISCHK(lisd_ssor_begin(A, NULL, &args.st));
 	LISCHK(upload_wd(A, &wd));
 	double *db, *dx;
 	LISCHK(lisd_vec_in(B, &db));
 	LISCHK(lisd_vec_out(X, &dx));
-	psolve_args args = {A, T, db, dx};
+	args.b = db; args.x = dx;
 	LISCHK(lisi_sweep_times(reps, psolve_once, &args, ms));
 	return lisd_vec_done(X);
 }
