@@ -481,11 +481,18 @@ static LIS_INT convert_impl(LIS_MATRIX Ain, LIS_MATRIX Aout)
 	LISCHK(lisi_matrix_check(Ain, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisi_matrix_check(Aout, LISI_CHECK_NULL));
 	const LIS_INT want = Aout->matrix_type;
-	if (MDEV(Ain)->device_only) {          /* born in HBM: the conversions that are built there (ELL, DIA, CSC, BSR) are served, the host routines have nothing to read */
+	if (MDEV(Ain)->device_only) {          /* born in HBM: ELL, DIA, CSC and BSR are built there; what they leave to the host (JAD, rows out of order for DIA / CSC,
+		                                        * block rows of more than 96 blocks) runs on a host copy of the arrays, made for this conversion */
 		int done = 0;
 		if (Ain->matrix_type == LIS_MATRIX_CSR && want != LIS_MATRIX_CSR) LISCHK(lisd_convert_csr(Ain, Aout, &done));
 		if (done) return LIS_SUCCESS;
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "matrix lives in HBM only: this conversion runs on host arrays -- convert the host matrix before uploading\n");
+		if (Ain->matrix_type != LIS_MATRIX_CSR || want == LIS_MATRIX_CSR)
+			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "matrix lives in HBM only: this conversion runs on host arrays -- convert the host matrix before uploading\n");
+		LIS_MATRIX home;
+		LISCHK(lisd_csr_home(Ain, &home));
+		LIS_INT err = lisi_convert_csr_to(home, Aout);
+		lis_matrix_destroy(home);
+		return err;
 	}
 	LISCHK(lis_matrix_merge(Ain));         /* ref lis_matrix_ops.c:142: a split input is merged first */
 	if (Ain->matrix_type == want && !Ain->is_block) { LISCHK(lisp_fill_matrix(Ain)); return lisi_matrix_deep_copy(Ain, Aout); }

@@ -1283,6 +1283,35 @@ LIS_INT lisd_convert_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done)
 	return LIS_SUCCESS;
 }
 
+/* A host copy of a CSR matrix that lives in HBM only (lis_amd_matrix_set_csr_device / lis_amd_matrix_poisson3d): what lis_matrix_convert hands to the host routines
+ * when the conversion asked for is not built in HBM -- JAD (its row order is the reference's sort on the host), DIA and CSC of rows that are not in ascending column
+ * order, BSR rows of more than 96 blocks.  One rank, no ghost columns, at least one entry (what lisd_convert_csr asks too;
+ * anything else is refused as before).  The caller destroys *home. */
+LIS_INT lisd_csr_home(LIS_MATRIX Ain, LIS_MATRIX *home)
+{
+	lisd_mat *sd = MDEV(Ain);
+	*home = NULL;
+	if (!sd->device_only || sd->type != LIS_MATRIX_CSR || !sd->ptr || lisg.nprocs > 1 || Ain->np != Ain->n || Ain->n <= 0 || Ain->nnz <= 0)
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "matrix lives in HBM only: this conversion runs on host arrays -- convert the host matrix before uploading\n");
+	const LIS_INT n = Ain->n, nnz = Ain->nnz;
+	LIS_MATRIX H = NULL; LIS_INT *p = NULL, *i = NULL; LIS_SCALAR *v = NULL;
+	LISCHK(lis_matrix_duplicate(Ain, &H));
+	LIS_INT err = lis_matrix_malloc_csr(n, nnz, &p, &i, &v);
+	if (!err) {
+		int rc = liship_memcpy_d2h(p, sd->ptr, sizeof(int) * ((size_t)n + 1), lisg.stream);
+		if (!rc) rc = liship_memcpy_d2h(i, sd->index, sizeof(int) * (size_t)nnz, lisg.stream);
+		if (!rc) rc = liship_memcpy_d2h(v, sd->value, sizeof(double) * (size_t)nnz, lisg.stream);
+		if (!rc) rc = liship_stream_synchronize(lisg.stream);
+		if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
+	}
+	if (!err) err = lis_matrix_set_csr(nnz, p, i, v, H);
+	if (err) { lis_free(p); lis_free(i); lis_free(v); lis_matrix_destroy(H); return err; }
+	/* assembled as far as the host routines care -- they read n, np, nnz and the three arrays -- without lis_matrix_assemble, which would build an HBM copy of the copy */
+	H->matrix_type = LIS_MATRIX_CSR; H->status = LIS_MATRIX_CSR;
+	*home = H;
+	return LIS_SUCCESS;
+}
+
 LIS_INT lis_amd_matrix_upload(LIS_MATRIX A) { return lisd_mat_ready(A); }
 LIS_INT lis_amd_matrix_index_codes(LIS_MATRIX A)
 {

@@ -336,6 +336,7 @@ LIS_INT lisi_convert_csr_to(LIS_MATRIX Ain, LIS_MATRIX Aout);  /* Aout->matrix_t
 LIS_INT lisi_convert_to_csr(LIS_MATRIX Ain, LIS_MATRIX Aout);
 LIS_INT lisi_jad_order(LIS_MATRIX A, LIS_INT *maxnzr, LIS_INT **perm, LIS_INT **ptr);      /* the reference's length-sorted row order + jagged-diagonal starts */
 LIS_INT lisd_convert_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done);   /* csr -> ell / dia / csc / bsr in HBM when Ain lives there (lis_device.c) */
+LIS_INT lisd_csr_home(LIS_MATRIX Ain, LIS_MATRIX *home);               /* a host copy of a CSR matrix born in HBM, for the conversions the host routines serve (lis_device.c) */
 LIS_INT lisi_matrix_deep_copy(LIS_MATRIX Ain, LIS_MATRIX Aout);
 
 /* args (lis_initialize / lis_solver_set_option share the tokenizer) */

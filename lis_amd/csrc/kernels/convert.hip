@@ -3,7 +3,8 @@
 // The reference converts on the host (src/matrix/lis_matrix_ell.c:958-1070 csr2ell, lis_matrix_dia.c:1191-1304 csr2dia,
 // lis_matrix_csc.c:904-1087 csr2csc, lis_matrix_bsr.c:351-552 csr2bsr); its own drivers convert once per format per run
 // (test/spmvtest3.c:214-218).  These kernels produce the SAME arrays -- same padding, same diagonal order, same block order, bit for bit
-// (the host versions in lis_convert.c are the checker: tests compare against the reference-made goldens either way) -- from the HBM copy,
+// (tests/test_convert_gpu.py compares every entry point below, and lis_matrix_convert through them, with the plain-C oracle, index by index and bit by bit;
+// tests/test_convert_cpu.py holds that oracle and the host versions in lis_convert.c to the reference on the same matrices) -- from the HBM copy,
 // so a conversion costs a pass over HBM instead of a pass over host memory plus an upload.  Integer work; setup-time, not the hot path.
 #include "common.hpp"
 #include "liship.h"
