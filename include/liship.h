@@ -481,6 +481,9 @@ int  liship_csr_diagonal_f64(int n, const int *ptr, const int *index, const doub
  * one eighth of every plane and walks the planes in order, so the +-plane neighbours of a row are in its own L2 (the CSR kernels learn their plane at plan time:
  * liship_csr_plan_strip_rows).  0: the natural workgroup order.  An order of the workgroups only: the bits cannot depend on it. */
 int  liship_spmv_formats_set_plane(int rows);
+/* workgroups per plane that a whole-matrix ELL / DIA launch of `grid` workgroups of `rows_per_wg` rows (512: 256 lanes of two rows) takes from the plane set now;
+ * 0: that launch runs in natural order (plane not whole workgroups, fewer than 64 or not a multiple of 8 workgroups per plane, fewer than four planes) */
+int  liship_spmv_formats_plane_blocks(int rows_per_wg, int grid);
 /* the plane of a structured grid from ELL arrays in HBM: the largest |column - row| when at least half of the rows reach it (as liship_csr_plan_scan_band), else 0 */
 int  liship_ell_scan_band(int n, int maxnzr, const int *index, int *plane_rows, void *stream);
 /* the same for the native ELL arrays (first slot whose index is the row; padding gives 0: src/matrix/lis_matrix_ell.c lis_matrix_get_diagonal_ell) and the

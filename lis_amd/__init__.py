@@ -183,6 +183,7 @@ _LISHIP = {
     "liship_ell_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
     "liship_dia_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
     "liship_spmv_formats_set_plane": (_ci, [_ci]),
+    "liship_spmv_formats_plane_blocks": (_ci, [_ci, _ci]),
     "liship_ell_scan_band": (_ci, [_ci, _ci, _vp, _vp, _vp]),
     "liship_spmv_csr_transposed_chunked_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_bsr_to_rows": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
