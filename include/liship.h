@@ -387,7 +387,15 @@ int  liship_scale_inv_norm_f64(int n, const double *sumsq, double *x, void *stre
  * use.  While a guard flag is installed (liship_krylov_guard), every vector / reduction / fused-product kernel
  * launched returns immediately if *flag != 0, so the host may enqueue a batch of iterations, read the block
  * back once, and find x, r and the iteration count exactly as the one-synchronisation-per-scalar loop leaves
- * them. */
+ * them.  Lowered means 0.0 or -0.0; anything else, NaN included, is raised.
+ * Behind a raised flag no kernel writes a vector element, and a scalar step whose state has DONE up re-arms
+ * NOT_HALF and changes nothing else.  The RESULT slots of a guarded reduction, fused update pass or fused-dot
+ * product are UNSPECIFIED then: the first-level kernel returns at once, but the folds that follow it when the
+ * reduction takes more than one workgroup are not guarded and rewrite result[] from whatever partials the work
+ * buffer holds (one workgroup, and the reference-order mode, leave result[] alone).  A device loop never reads
+ * those sums again once DONE is up.
+ * The installed guard and the announced step are per-process and hold the raw pointers they were given: remove the guard
+ * (NULL) and withdraw the step (0) before the memory they point at is freed. */
 enum {
 	LISHIP_KS_RHO = 0, LISHIP_KS_RHO_OLD, LISHIP_KS_ALPHA, LISHIP_KS_NALPHA, LISHIP_KS_BETA, LISHIP_KS_OMEGA,
 	LISHIP_KS_NOMEGA, LISHIP_KS_DOT0, LISHIP_KS_DOT1, LISHIP_KS_SUM0, LISHIP_KS_SUM1, LISHIP_KS_NRM2,
@@ -416,7 +424,10 @@ enum {
 int  liship_krylov_guard(const double *flag);
 /* one scalar step on `state`; rhistory (device, may be NULL) receives the residual norm of each completed
  * iteration at [iter].  In a multi-rank job `gathered` holds nranks x count per-rank sums (rank-major), which are
- * added in rank order into the slots the step reads, before it runs; NULL otherwise. */
+ * added in rank order, from 0.0, into the slots the step reads, before it runs; NULL otherwise (nranks is then ignored).
+ * Slot and count per step: CG_ALPHA, BICGSTAB_ALPHA, BICG_ALPHA: DOT0, 1;  BICGSTAB_OMEGA: DOT0, 2;
+ * CG_RESID, BICGSTAB_HALF, BICG_RESID: SUM0, 1;  CG_RESID_PRE, BICGSTAB_RESID, BICG_RHO: SUM0, 2.
+ * A step outside CG_ALPHA .. BICG_RHO or a NULL state: LISHIP_ERR_ARG, nothing is launched. */
 int  liship_krylov_step(int step, double *state, double *rhistory, const double *gathered, int nranks, void *stream);
 /* single-rank jobs: announce the step BEFORE launching the reduction whose sums it reads; it then runs in that
  * reduction's last kernel instead of a launch of its own.  liship_krylov_chain_flush runs a step that was announced

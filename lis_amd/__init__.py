@@ -160,6 +160,19 @@ _LISHIP = {
     "liship_cg_update_jacobi_f64": (_ci, [_ci, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_pmul_xpay_f64": (_ci, [_ci, _vp, _vp, _cd, _vp, _vp]),
     "liship_bicgstab_end_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_krylov_guard": (_ci, [_vp]),
+    "liship_krylov_step": (_ci, [_ci, _vp, _vp, _vp, _ci, _vp]),
+    "liship_krylov_chain": (_ci, [_ci, _vp, _vp]),
+    "liship_krylov_chain_flush": (_ci, [_vp]),
+    "liship_rank_fold_f64": (_ci, [_ci, _vp, _ci, _vp, _vp]),
+    "liship_xpay_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
+    "liship_pmul_xpay_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
+    "liship_axpy_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
+    "liship_axpy2_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_axpy_xpay_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_cg_update_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_axpy_sumsq_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_axpy_sumsq_dot_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_cg_direction_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_cg_residual_jacobi_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_cg_direction_uniform_dev_f64": (_ci, [_ci, _vp, _vp, _vp, _cd, _vp, _vp, _vp]),
