@@ -341,10 +341,24 @@ int  liship_csr_scale_f64(int n, const int *ptr, const int *index, double *value
  * one pass over HBM instead of two or three */
 int  liship_axpy2_f64(int n, double a, const double *x, double b, const double *w, double *y, void *stream);       /* y += a*x; y += b*w   (lis_solver_bicgstab.c:272-273) */
 int  liship_axpy_xpay_f64(int n, double a, const double *x, const double *w, double b, double *y, void *stream);   /* y += a*x; y = w + b*y (lis_solver_bicgstab.c:212-213) */
-/* two-stage reductions (wavefront shuffle + LDS, then one fixed-order pass over the partials):
- * src/vector/lis_vector_ops.c dot :58-127, nrm2 :210-271, nrm1 :278-342, sum :418-478.
- * `result` is a DEVICE pointer to `count` doubles, `work` a device scratch of liship_reduce_work_bytes().
- * *_partial variants leave the un-rooted local sum (for a cross-GPU all-reduce before sqrt). */
+/* reductions: src/vector/lis_vector_ops.c dot :58-127, nrm2 :210-271, nrm1 :278-342, sum :418-478.
+ * `result` is a DEVICE pointer to as many doubles as the entry point has sums (one, or two where its comment names two; nothing
+ * behind them is written), `work` a device scratch of liship_reduce_work_bytes() whose contents on entry do not matter.
+ * The ORDER of every sum is fixed and part of the contract (the Krylov iteration counts hang on its bits); it depends on n and on
+ * the alignment of the arrays only.  tests/reduction_model.py restates it, tests/test_reduction_tree_gpu.py holds every entry
+ * point to that:
+ *   level 1   workgroups of 256 lanes, 2048 elements each, grid = max(1, ceil(((n + 1) / 2) / 1024)); every lane starts from 0.0.
+ *             Every array (inputs and in-place outputs) 16 B aligned: lane t of block b takes the pairs p = 1024 b + t + 256 u,
+ *             u = 0..3, p < n / 2, and adds the term of element 2p, then of 2p + 1; lane 0 of block 0 adds the last element of an
+ *             odd n after its own pairs.  Any array only 8 B aligned: lane t of block b adds the elements 2048 b + t + 256 u, u = 0..7.
+ *   wavefront six butterfly steps, v += v[lane ^ k] for k = 32, 16, 8, 4, 2, 1, read from lane 0
+ *   workgroup the wavefronts' sums added in wavefront order, from 0.0
+ *   folds     over the workgroups' partials: one partial is copied; up to 2^14 are summed by one workgroup of 1024 lanes (lane t
+ *             adds partial[t], partial[t + 1024], ..., then the wavefront and workgroup steps above over 16 wavefronts); more are
+ *             first summed in blocks of 2048 laid out as the 8 B aligned level 1, then folded again
+ *   root      nrm2 takes sqrt once, of the final sum
+ * A second sum accumulates separately, in the same order.  The fused forms add the terms their comments give, each product and
+ * each sum rounded once (no FMA); -alpha and -*hprev are negations. */
 size_t liship_reduce_work_bytes(void);
 /* T > 0: the reductions below (and the fused update passes) add their terms in the reference's order for OMP_NUM_THREADS = T -- chunk t of T is
  * LIS_GET_ISIE(t, T, n) (include/lis.h:1067-1078), summed left to right from 0.0 by one lane, the T partials added serially in chunk order
