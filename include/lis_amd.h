@@ -100,11 +100,22 @@ LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4]);
 LIS_INT lis_amd_ssor_sweep_info(LIS_MATRIX A, LIS_INT sweep, LIS_INT info[6]);
 /* reps psolves X = M^-1 B, each timed by device events into ms[k] (tools/ssor_probe.py) */
 LIS_INT lis_amd_ssor_psolve_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *ms);
-/* ---- ILU(k) (-p ilu -ilu_fill k; A in CSR storage, not split, one rank).  All of these work at the current block count: 1, or T of
+/* ---- ILU(k) (-p ilu -ilu_fill k; A in CSR or BSR storage, not split, one rank).  All of these work at the current block count: 1, or T of
  * lis_amd_set_reference_reductions(T) (the reference at T threads factorises T row blocks on their own). */
 /* 1 when the last lis_solve ran -p ilu (else 0, and 0 in every field; lis_amd_last_solve_ssor answers 0 then, and the other way
  * round): its fill level, row blocks, forward levels (= the levels of the factorisation) and the kernel launches of one psolve */
 LIS_INT lis_amd_last_solve_ilu(LIS_INT *fill, LIS_INT *blocks, LIS_INT *levels, LIS_INT *launches_per_psolve);
+/* A in BSR storage with square blocks of bn = 1, 2 or 3 (as given by lis_matrix_set_bsr or made by lis_matrix_convert; not split,
+ * -storage absent or bsr) is served by the block ILU(k) of the reference (lis_precon_iluk.c:102-109): the pattern on the block graph,
+ * dense bn x bn block arithmetic, every diagonal block inverted, block sweeps.  M^-1 only: solvers that apply M^-H (BiCG, BiCR, CRS,
+ * BiCRSTAB, GPBiCR, BiCRSafe) and lis_amd_ilu_psolve(.., transposed = 1) answer LIS_ERR_NOT_IMPLEMENTED on such a matrix -- the
+ * reference's OpenMP build applies M^-1 there, which is neither reproduced nor replaced.  Larger blocks are refused as well: the
+ * reference's block sweeps keep a block's result in w[3].  For a BSR matrix the entry points below count in blocks:
+ * sizes = {nr, blocks(L), blocks(U)}, lptr / uptr hold nr + 1 entries, lindex / uindex block columns, lvalue / uvalue bn*bn doubles per
+ * block (column-major) and d the nr*bn*bn doubles of the INVERTED diagonal blocks; levels, launches and rows are block rows.
+ * lis_amd_last_solve_ilu_block: bn when the last lis_solve ran the block ILU, 0 otherwise (before any solve, after a CSR -p ilu solve,
+ * after any other solve); lis_amd_last_solve_ilu reports fill, row blocks, levels and launches for both forms. */
+LIS_INT lis_amd_last_solve_ilu_block(void);
 /* factorise A at fill level `fill` in HBM (pattern and schedule are cached on A's HBM copy, the numbers are made anew);
  * sizes = {n, nnz(L), nnz(U)}, the room lis_amd_ilu_copy needs */
 LIS_INT lis_amd_ilu_factor(LIS_MATRIX A, LIS_INT fill, LIS_INT sizes[3]);

@@ -610,6 +610,28 @@ typedef struct {
 } liship_ilu_t;
 int  liship_ilu_factor_f64(const liship_ilu_t *ilu, const liship_sweep_t *schedule, void *stream);
 
+/* ------------------------------------------------------------------ block ILU(k) on BSR storage (kernels/bilu.hip on kernels/level_schedule.hpp)
+ * liship_ilu_t with a block where it has a number: nr = ceil(n / bn) block rows, bn = 1, 2, 3; A = (aptr, aindex, avalue) the BSR
+ * arrays in native layout (block k at avalue[k*bn*bn], column-major); the pattern over block rows and block columns; lval / uval
+ * bn*bn doubles per pattern place, d the nr diagonal blocks, INVERTED on return (lis_array_ge, after 1.0 on the diagonal of the last
+ * block's padding when bn does not divide n).  buf = L_ij Dinv_j stored, target -= buf U_jc: every entry of a product summed left to
+ * right from its first product, then one subtraction.  `schedule` over the nr block rows as for liship_ilu_factor_f64: long block
+ * rows a workgroup each (one whole block update per thread, pivots in order), one thread when serial != 0. */
+typedef struct {
+	int n, nr, bn, serial;
+	const int *aptr, *aindex;
+	const double *avalue;
+	const int *lptr, *lcol, *uptr, *ucol, *uskey, *uspos;
+	double *lval, *uval, *d;
+} liship_bilu_t;
+int  liship_bilu_factor_f64(const liship_bilu_t *ilu, const liship_sweep_t *schedule, void *stream);
+/* one block sweep over a layout of ceil(n / bn) block rows whose val holds bn*bn doubles per place: x_i = b_i, then per term in order
+ * x_i[r] = x_i[r] - ((a[r] xj[0] + a[r+bn] xj[1]) + a[r+2bn] xj[2]); dinv not NULL: x_i = dinv_i x_i at the end (same sums).  x reads
+ * as +0.0 from n on and is never written there; b may equal x. */
+int  liship_bilu_sweep_f64(const liship_sweep_t *sweep, int n, int bn, const double *dinv, const double *b, double *x, void *stream);
+/* dst block p = src block perm[p], blocks of bs doubles: liship_permute_gather_f64 for the values of a block layout */
+int  liship_block_gather_f64(int nblocks, int bs, const int *perm, const double *src, double *dst, void *stream);
+
 /* ------------------------------------------------------------------ block diagonal (kernels/bdiag.hip, -p bjacobi)
  * d: nr = ceil(n / bn) blocks of bn x bn doubles, block b at d[b*bn*bn], entry (i, j) at i + j*bn (LIS_MATRIX_DIAG).
  * inverse: every block replaced by its inverse, by the reference's lis_array_ge (LU without pivoting, no pivot check: 1 / 0 = inf goes on), after the

@@ -222,6 +222,7 @@ _AMD_PROTOS = {
     "lis_amd_ssor_sweep_info": (LIS_INT, [PM, LIS_INT, P_INT]),
     "lis_amd_ssor_psolve_times": (LIS_INT, [PM, PV, PV, LIS_INT, P_DBL]),
     "lis_amd_last_solve_ilu": (LIS_INT, [P_INT, P_INT, P_INT, P_INT]),
+    "lis_amd_last_solve_ilu_block": (LIS_INT, []),
     "lis_amd_ilu_factor": (LIS_INT, [PM, LIS_INT, P_INT]),
     "lis_amd_ilu_copy": (LIS_INT, [PM, LIS_INT, P_INT, P_INT, P_DBL, P_INT, P_INT, P_DBL, P_DBL]),
     "lis_amd_ilu_psolve": (LIS_INT, [PM, LIS_INT, PV, PV, LIS_INT]),

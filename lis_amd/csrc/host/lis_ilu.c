@@ -21,12 +21,22 @@
  *   psolve : x = b; forward on L (no diagonal); backward on U, then x[i] = d[i] x[i]           (ref :880-934)
  *   psolveh: x = b; forward on U^T with x[i] = d[i] x[i] first; backward on L^T (no diagonal)    (ref :1086-1140)
  * The numbers are refactorised by every lis_precon_create, from A's values as they lie in HBM.
+ *
+ * BSR storage (bnr == bnc in 1..3): block ILU(k) (ref :102-109, :1289-1468, :1714-1819, :2006-2037; kernels/bilu.hip).  The same entry
+ * with a block where the point form has a number: the symbolic step runs unchanged on (nr, bptr, bindex) with the T row blocks of
+ * LIS_GET_ISIE over the nr block rows, the schedule and the L and U layouts come from the same builders (a place holds bn*bn doubles,
+ * filled by the block gather), d holds the INVERTED diagonal blocks.  The factorisation reads A's blocks in native layout: the HBM
+ * copy's own arrays, or -- when the copy is held in its row form (lis_device.c try_bsr_row_form) -- a native upload kept on the entry,
+ * which dies with the copy like everything else here.  psolve only: the reference's OpenMP build applies M^-1 where M^-H is meant
+ * (:2098-2165 is a copy of psolve), which this library neither reproduces nor replaces, so solvers that need M^-H are refused.
  */
 #include <stdio.h>
 #include "lis_krylov.h"
 
 typedef struct {
-	int used, fill, T, n;
+	int used, fill, T, n;                      /* n: the rows of the pattern -- A's rows, or its block rows */
+	int bn, an;                                /* BSR: the block size and A's rows (bn = 0: the point form on CSR storage) */
+	int *d_ap, *d_ai; double *d_av;            /* BSR whose HBM copy is held in row form: A's native arrays, uploaded for the factorisation */
 	int lnnz, unnz;
 	int serial;                                /* some row of A stores a column twice (liship_ilu_t.serial) */
 	int *lp, *lc, *up, *uc;                    /* host: the pattern in term order */
@@ -44,6 +54,8 @@ typedef struct {
 	int next;
 } lisd_ilu;
 
+#define ENTRY_BS(e) ((size_t)((e)->bn ? (e)->bn * (e)->bn : 1))      /* doubles per place of the pattern */
+
 static void entry_free(ilu_entry *e)
 {
 	free(e->lp); free(e->lc); free(e->up); free(e->uc);
@@ -51,6 +63,7 @@ static void entry_free(ilu_entry *e)
 	if (e->d_uskey != e->d_uc) (void)liship_free(e->d_uskey);
 	(void)liship_free(e->d_uc); (void)liship_free(e->d_uspos);
 	(void)liship_free(e->d_lval); (void)liship_free(e->d_uval); (void)liship_free(e->d_d);
+	(void)liship_free(e->d_ap); (void)liship_free(e->d_ai); (void)liship_free(e->d_av);
 	lisi_sweep_free(&e->sched);
 	for (int w = 0; w < SW_COUNT; w++) { lisi_sweep_free(&e->sw[w]); (void)liship_free(e->d_src[w]); }
 	memset(e, 0, sizeof(*e));
@@ -186,12 +199,14 @@ static LIS_INT sweep_make(ilu_entry *e, int which)
 	int *src = NULL, *tp = NULL, *tc = NULL, *tid = NULL;
 	LIS_INT err;
 	if ((err = lisi_sweep_terms(n, lower ? e->lp : e->up, lower ? e->lc : e->uc, NULL, SW_TERMS(which), &tp, &tc, &tid))) goto out;
-	if ((err = lisi_sweep_build(&e->sw[which], n, tp, tc, NULL, SW_DESC(which), NULL, &src))) goto out;
+	if ((err = lisi_sweep_build_places(&e->sw[which], n, tp, tc, NULL, SW_DESC(which), NULL, &src, (int)ENTRY_BS(e)))) goto out;   /* a place holds a block */
 	for (int k = 0; k < nnz; k++) src[k] = tid[src[k]];
 	if ((err = lisd_upload_i(&e->d_src[which], src, (size_t)nnz))) goto out;
 	{	int rc = liship_stream_synchronize(lisg.stream);
 		if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
-	e->sw[which].bytes = lisi_sweep_bytes(n, nnz, lower ? 16.0 : 24.0);
+	/* per (block) row: b and x, and the diagonal (block) where the sweep has one */
+	const double rowlen = e->bn ? (double)e->bn : 1.0;
+	e->sw[which].bytes = lisi_sweep_bytes_places(n, nnz, (int)ENTRY_BS(e), 16.0 * rowlen + (lower ? 0.0 : 8.0 * (double)ENTRY_BS(e)));
 out:
 	free(src); free(tp); free(tc); free(tid);
 	if (err) { lisi_sweep_free(&e->sw[which]); (void)liship_free(e->d_src[which]); e->d_src[which] = NULL; }
@@ -201,7 +216,9 @@ out:
 static LIS_INT fill_sweep(ilu_entry *e, int which)
 {
 	const int nnz = e->sw[which].k.nnz;
-	if (nnz > 0) HIPCHK(liship_permute_gather_f64(nnz, e->d_src[which], (which == SW_L || which == SW_LT) ? e->d_lval : e->d_uval, e->sw[which].val, lisg.stream));
+	const double *from = (which == SW_L || which == SW_LT) ? e->d_lval : e->d_uval;
+	if (nnz > 0 && e->bn) HIPCHK(liship_block_gather_f64(nnz, (int)ENTRY_BS(e), e->d_src[which], from, e->sw[which].val, lisg.stream));
+	else if (nnz > 0) HIPCHK(liship_permute_gather_f64(nnz, e->d_src[which], from, e->sw[which].val, lisg.stream));
 	return LIS_SUCCESS;
 }
 
@@ -222,6 +239,12 @@ static LIS_INT host_pattern(LIS_MATRIX A, int **ptr, int **idx, int *owned)
 {
 	lisd_mat *d = MDEV(A);
 	*owned = 0;
+	if (A->matrix_type == LIS_MATRIX_BSR) {      /* the block graph (a BSR matrix always has host arrays; those of a conversion in HBM come home here) */
+		LISCHK(lisp_fill_matrix(A));
+		if (!A->bptr || (!A->bindex && A->bnnz > 0)) return LISI_ERR(LIS_ERR_ILL_ARG, "matrix A has no BSR arrays\n");
+		*ptr = A->bptr; *idx = A->bindex;
+		return LIS_SUCCESS;
+	}
 	if (!d->device_only) {
 		LISCHK(lisp_fill_matrix(A));
 		if (A->ptr && (A->index || A->nnz == 0)) { *ptr = A->ptr; *idx = A->index; return LIS_SUCCESS; }
@@ -241,12 +264,14 @@ static LIS_INT host_pattern(LIS_MATRIX A, int **ptr, int **idx, int *owned)
 
 static LIS_INT entry_build(LIS_MATRIX A, ilu_entry *e, int fill, int T)
 {
-	const int n = A->n;
+	const int block = A->matrix_type == LIS_MATRIX_BSR;
+	const int n = block ? A->nr : A->n;
 	int *ptr = NULL, *idx = NULL, owned = 0;
 	int *weight = NULL;
 	LIS_INT err;
 	const double t0 = lis_wtime();
-	e->used = 1; e->fill = fill; e->T = T; e->n = n;
+	e->used = 1; e->fill = fill; e->T = T; e->n = n; e->bn = block ? A->bnr : 0; e->an = A->n;
+	if ((long long)n * (long long)ENTRY_BS(e) >= 0x7fffffffLL) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "the ILU factor does not fit\n"); goto out; }
 	if ((err = host_pattern(A, &ptr, &idx, &owned))) goto out;
 	if ((err = symbolic(e, n, ptr, idx, fill, T))) goto out;
 	weight = (int *)malloc(sizeof(int) * (size_t)(n + 1));
@@ -255,9 +280,10 @@ static LIS_INT entry_build(LIS_MATRIX A, ilu_entry *e, int fill, int T)
 	if ((err = lisi_sweep_build(&e->sched, n, e->lp, e->lc, NULL, 0, weight, NULL))) goto out;
 	if ((err = lisd_upload_i(&e->d_lp, e->lp, (size_t)n + 1)) || (err = lisd_upload_i(&e->d_lc, e->lc, (size_t)e->lnnz)) ||
 	    (err = lisd_upload_i(&e->d_up, e->up, (size_t)n + 1)) || (err = lisd_upload_i(&e->d_uc, e->uc, (size_t)e->unnz))) goto out;
-	{	int rc = lisd_malloc((void **)&e->d_lval, ((size_t)e->lnnz + 2) * sizeof(double));
-		if (!rc) rc = lisd_malloc((void **)&e->d_uval, ((size_t)e->unnz + 2) * sizeof(double));
-		if (!rc) rc = lisd_malloc((void **)&e->d_d, ((size_t)n + 2) * sizeof(double));
+	if (((long long)e->lnnz + e->unnz) * (long long)ENTRY_BS(e) >= 0x7fffffffLL) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "the ILU factor does not fit\n"); goto out; }
+	{	int rc = lisd_malloc((void **)&e->d_lval, ((size_t)e->lnnz * ENTRY_BS(e) + 2) * sizeof(double));
+		if (!rc) rc = lisd_malloc((void **)&e->d_uval, ((size_t)e->unnz * ENTRY_BS(e) + 2) * sizeof(double));
+		if (!rc) rc = lisd_malloc((void **)&e->d_d, ((size_t)n * ENTRY_BS(e) + 2) * sizeof(double));
 		if (!rc) rc = liship_stream_synchronize(lisg.stream);
 		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; } }
 	if ((err = upload_search_keys(e))) goto out;
@@ -269,14 +295,29 @@ out:
 	return err;
 }
 
-/* A: an assembled CSR matrix, not split, on one rank */
+/* A: an assembled CSR matrix, or a BSR matrix with square blocks of 1 .. 3, not split, on one rank */
 static LIS_INT check_served(LIS_MATRIX A, LIS_INT fill)
 {
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
-	if (A->matrix_type != LIS_MATRIX_CSR) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu is served for CSR storage only (A is untouched)\n");
+	if (A->matrix_type == LIS_MATRIX_BSR) {
+		if (A->bnr != A->bnc) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu on %D x %D blocks is not served: block ILU wants square blocks (A is untouched)\n", A->bnr, A->bnc);
+		if (A->bnr > 3 || A->bnr < 1)
+			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu on %D x %D blocks is not served: the reference's block sweeps hold a block's result in w[3] "
+			                "(lis_precon_iluk.c:1977), which defines block ILU for blocks of 1, 2 and 3 only (A is untouched)\n", A->bnr, A->bnc);
+		if (A->is_splited) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu on a split BSR matrix (an earlier -p bjacobi solve splits A) is not served: lis_matrix_merge(A) first (A is untouched)\n");
+	} else if (A->matrix_type != LIS_MATRIX_CSR) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu is served for CSR and BSR storage only (A is untouched)\n");
 	if (A->is_splited) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu on a split matrix (an earlier -p ssor solve splits A) is not served: lis_matrix_merge(A) first (A is untouched)\n");
 	if (lisg.nprocs > 1) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu is served on one rank only (A is untouched)\n");
 	if (fill < 0) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-ilu_fill %D is not served: the fill level is 0 or more (A is untouched)\n", fill);
+	return LIS_SUCCESS;
+}
+
+/* -p ilu on BSR storage applies M^-1 only */
+static LIS_INT check_solver(LIS_MATRIX A, LIS_SOLVER solver)
+{
+	if (A->matrix_type == LIS_MATRIX_BSR && lisi_solver_needs_transpose(solver->options[LIS_OPTIONS_SOLVER]))
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu on BSR storage with a solver that applies M^-H (-i %D) is not served: the reference's OpenMP build applies M^-1 there "
+		                "(lis_precon_iluk.c:2098-2165), which this library neither reproduces nor replaces (A is untouched)\n", solver->options[LIS_OPTIONS_SOLVER]);
 	return LIS_SUCCESS;
 }
 
@@ -285,11 +326,12 @@ static LIS_INT get_entry(LIS_MATRIX A, int fill, int T, ilu_entry **out)
 {
 	LISCHK(lisd_mat_ready(A));
 	lisd_mat *d = MDEV(A);
-	if (d->type != LIS_MATRIX_CSR || !d->ptr || (A->nnz > 0 && (!d->index || !d->value))) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu needs the CSR arrays of A in HBM\n");
+	const int block = A->matrix_type == LIS_MATRIX_BSR, rows = block ? A->nr : A->n;
+	if (!block && (d->type != LIS_MATRIX_CSR || !d->ptr || (A->nnz > 0 && (!d->index || !d->value)))) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu needs the CSR arrays of A in HBM\n");
 	if (!d->ilu) { d->ilu = calloc(1, sizeof(lisd_ilu)); if (!d->ilu) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(lisd_ilu)); }
 	lisd_ilu *il = (lisd_ilu *)d->ilu;
 	ilu_entry *e = NULL;
-	for (int t = 0; t < 2; t++) if (il->e[t].used && il->e[t].fill == fill && il->e[t].T == T && il->e[t].n == A->n) e = &il->e[t];
+	for (int t = 0; t < 2; t++) if (il->e[t].used && il->e[t].fill == fill && il->e[t].T == T && il->e[t].n == rows && il->e[t].bn == (block ? A->bnr : 0)) e = &il->e[t];
 	if (!e) {
 		e = &il->e[il->next];
 		il->next ^= 1;
@@ -304,6 +346,28 @@ static LIS_INT get_entry(LIS_MATRIX A, int fill, int T, ilu_entry **out)
 static LIS_INT factorise(LIS_MATRIX A, ilu_entry *e)
 {
 	lisd_mat *d = MDEV(A);
+	if (e->bn) {
+		liship_bilu_t bf;
+		memset(&bf, 0, sizeof(bf));
+		bf.n = e->an; bf.nr = e->n; bf.bn = e->bn; bf.serial = e->serial;
+		if (d->type == LIS_MATRIX_BSR && d->bptr && (A->bnnz == 0 || (d->bindex && d->value))) { bf.aptr = d->bptr; bf.aindex = d->bindex; bf.avalue = d->value; }
+		else {                                   /* the copy is held in its row form: A's native arrays, uploaded once per entry */
+			if (!e->d_ap) {
+				LISCHK(lisp_fill_matrix(A));
+				LISCHK(lisd_upload_i(&e->d_ap, A->bptr, (size_t)e->n + 1));
+				LISCHK(lisd_upload_i(&e->d_ai, A->bindex, (size_t)A->bnnz));
+				LISCHK(lisd_upload_d(&e->d_av, A->value, (size_t)A->bnnz * ENTRY_BS(e)));
+				HIPCHK(liship_stream_synchronize(lisg.stream));
+			}
+			bf.aptr = e->d_ap; bf.aindex = e->d_ai; bf.avalue = e->d_av;
+		}
+		bf.lptr = e->d_lp; bf.lcol = e->d_lc; bf.uptr = e->d_up; bf.ucol = e->d_uc; bf.uskey = e->d_uskey; bf.uspos = e->d_uspos;
+		bf.lval = e->d_lval; bf.uval = e->d_uval; bf.d = e->d_d;
+		HIPCHK(liship_bilu_factor_f64(&bf, &e->sched.k, lisg.stream));
+		e->factored = 1;
+		for (int w = 0; w < SW_COUNT; w++) if (e->sw[w].built) LISCHK(fill_sweep(e, w));
+		return LIS_SUCCESS;
+	}
 	liship_ilu_t f;
 	memset(&f, 0, sizeof(f));
 	f.n = e->n; f.serial = e->serial;
@@ -324,10 +388,12 @@ LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon)
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisd_init());                         /* no device: the no-device code, before anything that could succeed */
 	/* refusals first: A is left as it was */
-	if (storage && storage != LIS_MATRIX_CSR) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu is served for CSR storage only, not with -storage %D (A is untouched)\n", storage);
+	if (storage && (storage != A->matrix_type || (storage != LIS_MATRIX_CSR && storage != LIS_MATRIX_BSR)))
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu is served for the CSR or BSR storage A already has, not with a conversion by -storage %D (A is untouched)\n", storage);
 	if (solver->options[LIS_OPTIONS_SCALE] != LIS_SCALE_NONE) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu together with -scale is not served (A is untouched)\n");
 	if (solver->options[LIS_OPTIONS_ADDS]) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ilu with -adds true is not served (A is untouched)\n");
 	LISCHK(check_served(A, fill));
+	LISCHK(check_solver(A, solver));
 	ilu_entry *e;
 	LISCHK(get_entry(A, (int)fill, lisi_sweep_blocks(), &e));
 	const liship_sweep_t *s;
@@ -345,11 +411,12 @@ LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st)
 	const liship_sweep_t *f, *b;
 	st->A = A; st->n = A->n; st->fill = (int)solver->options[LIS_OPTIONS_FILL]; st->T = lisi_sweep_blocks();
 	LISCHK(check_served(A, st->fill));
+	LISCHK(check_solver(A, solver));
 	LISCHK(get_entry(A, st->fill, st->T, &e));
 	LISCHK(get_sweep(e, SW_L, &f));
 	LISCHK(get_sweep(e, SW_U, &b));
 	if (!e->factored) LISCHK(factorise(A, e));   /* (the HBM copy was rebuilt since lis_precon_create) */
-	lisg.last_ilu = 1; lisg.last_ilu_fill = st->fill; lisg.last_ilu_blocks = st->T;
+	lisg.last_ilu = 1; lisg.last_ilu_fill = st->fill; lisg.last_ilu_blocks = st->T; lisg.last_ilu_bn = e->bn;
 	lisg.last_ilu_levels = f->nlev; lisg.last_ilu_launches = f->ngroups + b->ngroups;
 	return LIS_SUCCESS;
 }
@@ -358,6 +425,14 @@ LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st)
 static LIS_INT apply_on(ilu_entry *e, int transposed, const double *b, double *x)
 {
 	const liship_sweep_t *first, *second;
+	if (e->bn) {
+		if (transposed) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "M^-H of -p ilu on BSR storage is not served: the reference's OpenMP build applies M^-1 there\n");
+		LISCHK(get_sweep(e, SW_L, &first));
+		LISCHK(get_sweep(e, SW_U, &second));
+		HIPCHK(liship_bilu_sweep_f64(first, e->an, e->bn, NULL, b, x, lisg.stream));
+		HIPCHK(liship_bilu_sweep_f64(second, e->an, e->bn, e->d_d, x, x, lisg.stream));
+		return LIS_SUCCESS;
+	}
 	LISCHK(get_sweep(e, transposed ? SW_UT : SW_L, &first));
 	LISCHK(get_sweep(e, transposed ? SW_LT : SW_U, &second));
 	if (!transposed) {
@@ -387,6 +462,8 @@ LIS_INT lis_amd_last_solve_ilu(LIS_INT *fill, LIS_INT *blocks_out, LIS_INT *leve
 	if (launches_per_psolve) *launches_per_psolve = lisg.last_ilu ? lisg.last_ilu_launches : 0;
 	return lisg.last_ilu;
 }
+
+LIS_INT lis_amd_last_solve_ilu_block(void) { return lisg.last_ilu ? lisg.last_ilu_bn : 0; }
 
 static LIS_INT tool_entry(LIS_MATRIX A, LIS_INT fill, ilu_entry **e)
 {
@@ -418,9 +495,9 @@ LIS_INT lis_amd_ilu_copy(LIS_MATRIX A, LIS_INT fill, LIS_INT *lptr, LIS_INT *lin
 	if (lindex && e->lnnz) memcpy(lindex, e->lc, sizeof(int) * (size_t)e->lnnz);
 	if (uindex && e->unnz) memcpy(uindex, e->uc, sizeof(int) * (size_t)e->unnz);
 	HIPCHK(liship_stream_synchronize(lisg.stream));
-	if (lvalue && e->lnnz) LISCHK(lisd_staged_d2h(lvalue, e->d_lval, sizeof(double) * (size_t)e->lnnz));
-	if (uvalue && e->unnz) LISCHK(lisd_staged_d2h(uvalue, e->d_uval, sizeof(double) * (size_t)e->unnz));
-	if (d && n) LISCHK(lisd_staged_d2h(d, e->d_d, sizeof(double) * n));
+	if (lvalue && e->lnnz) LISCHK(lisd_staged_d2h(lvalue, e->d_lval, sizeof(double) * (size_t)e->lnnz * ENTRY_BS(e)));
+	if (uvalue && e->unnz) LISCHK(lisd_staged_d2h(uvalue, e->d_uval, sizeof(double) * (size_t)e->unnz * ENTRY_BS(e)));
+	if (d && n) LISCHK(lisd_staged_d2h(d, e->d_d, sizeof(double) * n * ENTRY_BS(e)));
 	return LIS_SUCCESS;
 }
 
@@ -429,6 +506,7 @@ LIS_INT lis_amd_ilu_psolve(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR 
 	ilu_entry *e;
 	LISCHK(tool_entry(A, fill, &e));
 	if (B->n != A->n || X->n != A->n) return LISI_ERR(LIS_ERR_ILL_ARG, "sizes of A, B and X do not match\n");
+	if (e->bn && transposed) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "M^-H of -p ilu on BSR storage is not served: the reference's OpenMP build applies M^-1 there\n");
 	if (!e->factored) LISCHK(factorise(A, e));
 	double *db, *dx;
 	LISCHK(lisd_vec_in(B, &db));

@@ -194,6 +194,7 @@ typedef struct {
 	int no_direct_halo;        /* LIS_AMD_NO_DIRECT_HALO=1: boundary rows that form a run are packed like any other list instead of being sent straight from x (A/B) */
 	lis_amd_comm_callbacks cb;
 	int last_ilu, last_ilu_fill, last_ilu_blocks, last_ilu_levels, last_ilu_launches;                  /* lis_amd_last_solve_ilu */
+	int last_ilu_bn;                                                                                   /* lis_amd_last_solve_ilu_block: the block size of a block ILU, 0 for the point form */
 	int last_bjacobi, last_bjacobi_bn, last_bjacobi_nr, last_bjacobi_fallback;                         /* lis_amd_last_solve_bjacobi */
 	int last_ssor, last_ssor_blocks, last_ssor_levels_fwd, last_ssor_levels_bwd, last_ssor_launches;   /* lis_amd_last_solve_ssor */
 } lisi_globals;
@@ -304,11 +305,14 @@ int     lisi_sweep_blocks(void);                                             /* 
 int    *lisi_block_of(int n, int T);                                         /* block of every row among T blocks of LIS_GET_ISIE (caller frees) */
 LIS_INT lisi_sweep_terms(int n, const int *ptr, const int *idx, const int *blk, int order, int **tp, int **tc, int **tid);   /* the terms of a sweep, row by row; tid: their places in idx */
 LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out);
+LIS_INT lisi_sweep_build_places(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out, int place);   /* `place` doubles of room per term */
+double  lisi_sweep_bytes_places(int n, int nnz, int place, double vec_bytes_per_row);
 void    lisi_sweep_free(lisi_sweep_t *s);
 double  lisi_sweep_bytes(int n, int nnz, double vec_bytes_per_row);          /* one application: 24 B per row of vectors with a diagonal, 16 B plain */
 void    lisi_sweep_census(const liship_sweep_t *s, LIS_INT census[5]);       /* {levels, launches, own-launch levels, long rows in those, long rows in runs} */
 LIS_INT lisi_sweep_times(LIS_INT reps, LIS_INT (*apply)(void *ctx), void *ctx, double *ms);   /* reps event-timed calls of apply: ms[k] */
 /* ---- ILU(k) (lis_ilu.c) */
+int     lisi_solver_needs_transpose(LIS_INT nsolver);                       /* the solver applies A^T and M^-H (lis_solver.c) */
 LIS_INT lisi_ilu_create(LIS_SOLVER solver, LIS_PRECON precon);              /* refusals, symbolic step (cached), factorisation on the device */
 void    lisd_ilu_free(void *ilu);
 LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);    /* the factor of A for a solve (made now if the HBM copy was rebuilt since create) */

@@ -938,6 +938,7 @@ static int solver_needs_transpose(LIS_INT nsolver)
 	return nsolver == LIS_SOLVER_BICG || nsolver == LIS_SOLVER_BICR || nsolver == LIS_SOLVER_CRS || nsolver == LIS_SOLVER_BICRSTAB ||
 	       nsolver == LIS_SOLVER_GPBICR || nsolver == LIS_SOLVER_BICRSAFE;
 }
+int lisi_solver_needs_transpose(LIS_INT nsolver) { return solver_needs_transpose(nsolver); }
 
 /* parameter checks, ref :482-537; then the solver object made ready for a solve */
 static LIS_INT check_options(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER solver)

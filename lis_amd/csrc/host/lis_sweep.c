@@ -79,6 +79,13 @@ void lisi_sweep_free(lisi_sweep_t *s)
  * row instead of its term count; src_out: for every place of the layout the term (index into tc) that lies there (caller frees) */
 LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out)
 {
+	return lisi_sweep_build_places(s, n, tp, tc, tv, desc, weight, src_out, 1);
+}
+
+/* the same with `place` doubles of room per term in val (block layouts: bn*bn; values given by tv only for place == 1) */
+LIS_INT lisi_sweep_build_places(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out, int place)
+{
+	if (place < 1 || (tv && place != 1)) return LISI_ERR(LIS_ERR_ILL_ARG, "a sweep layout takes its values at build time only with one double per term\n");
 	LIS_INT err = LIS_SUCCESS;
 	const int nnz = tp[n];
 	int *lev = (int *)malloc(sizeof(int) * (size_t)(n + 1));
@@ -129,7 +136,7 @@ LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, c
 		}
 	}
 	if ((err = lisd_upload_i(&s->lptr, lptr, (size_t)nlev + 1)) || (err = lisd_upload_i(&s->llong, llong, (size_t)nlev + 1)) || (err = lisd_upload_i(&s->rows, rows, (size_t)n)) ||
-	    (err = lisd_upload_i(&s->rptr, rptr, (size_t)n + 1)) || (err = lisd_upload_i(&s->col, col, (size_t)nnz)) || ((tv || src_out) && (err = lisd_upload_d(&s->val, val, (size_t)nnz)))) goto out;      /* (values that arrive later: room only) */
+	    (err = lisd_upload_i(&s->rptr, rptr, (size_t)n + 1)) || (err = lisd_upload_i(&s->col, col, (size_t)nnz)) || ((tv || src_out) && (err = lisd_upload_d(&s->val, val, (size_t)nnz * (size_t)place)))) goto out;      /* (values that arrive later: room only) */
 	{	int rc = liship_stream_synchronize(lisg.stream);          /* (the host arrays go below) */
 		if (rc) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); goto out; } }
 	s->k.nlev = nlev; s->k.nrows = n; s->k.nnz = nnz; s->k.ngroups = ng;
@@ -148,7 +155,12 @@ out:
  * vec_bytes_per_row = 24 with a diagonal (b, x, wd), 16 plain (b, x) */
 double lisi_sweep_bytes(int n, int nnz, double vec_bytes_per_row)
 {
-	return 4.0 * n + 4.0 * (n + 1) + 12.0 * nnz + vec_bytes_per_row * n;
+	return lisi_sweep_bytes_places(n, nnz, 1, vec_bytes_per_row);
+}
+/* ... with `place` doubles per term (a block layout: n block rows, vec_bytes_per_row per block row) */
+double lisi_sweep_bytes_places(int n, int nnz, int place, double vec_bytes_per_row)
+{
+	return 4.0 * n + 4.0 * (n + 1) + (4.0 + 8.0 * place) * nnz + vec_bytes_per_row * n;
 }
 
 /* the launches of a schedule: {levels, launches, levels on a launch of their own, long rows in those levels, long rows in runs} */

@@ -20,7 +20,7 @@
 // block) are +0.0, rows at or beyond n are not written.  Plain form: term j of lane i reads d[b*bs + i + j*bn], consecutive lanes
 // consecutive addresses.  Transposed form: d[b*bs + i*bn + j], stride bn between lanes -- the bn terms of the 64 lanes cover
 // whole lines, each line fetched once from HBM and served from L1 / L2 for the other terms.
-#include "common.hpp"
+#include "block_ops.hpp"
 #include "liship.h"
 
 namespace {
@@ -28,53 +28,11 @@ namespace {
 constexpr int BD_THREADS = 256;
 constexpr int BD_MAX_FIXED = 8;       // block sizes with a compile-time instantiation of the inverse
 
-// lis_array_ge on a block `a` with its LU copy `lu`, both indexed through accessors so that registers and HBM share the statement
-template <typename A, typename L>
-__device__ __forceinline__ void invert_block(const int n, A a, L lu)
-{
-    for (int e = 0; e < n * n; e++) lu(e) = a(e);
-    for (int k = 0; k < n; k++) {
-        lu(k + k * n) = 1.0 / lu(k + k * n);
-        for (int i = k + 1; i < n; i++) {
-            const double t = lu(i + k * n) * lu(k + k * n);
-            for (int j = k + 1; j < n; j++) lu(i + j * n) -= t * lu(k + j * n);
-            lu(i + k * n) = t;
-        }
-    }
-    for (int k = 0; k < n; k++) {
-        for (int i = 0; i < n; i++) {
-            double t = (i == k) ? 1.0 : 0.0;
-            for (int j = 0; j < i; j++) t -= lu(i + j * n) * a(j + k * n);
-            a(i + k * n) = t;
-        }
-        for (int i = n - 1; i >= 0; i--) {
-            double t = a(i + k * n);
-            for (int j = i + 1; j < n; j++) t -= lu(i + j * n) * a(j + k * n);
-            a(k * n + i) = t * lu(i + i * n);
-        }
-    }
-}
-
-struct RegRef {
-    double *p;
-    __device__ __forceinline__ double &operator()(int e) const { return p[e]; }
-};
 struct StridedRef {
     double *p; size_t stride;
     __device__ __forceinline__ double &operator()(int e) const { return p[(size_t)e * stride]; }
 };
 
-// the 1.0 on the padding's diagonal: block nr - 1 when n % bn != 0.  The fixed sizes walk every i under a predicate: a loop with a
-// run-time bound would index the register array dynamically and send the whole block to scratch.
-template <int BN>
-__device__ __forceinline__ void pad_last_block(int n, int nr, int b, double *blk)
-{
-    const int k = n % BN;
-    const bool last = k != 0 && b == nr - 1;
-#pragma unroll
-    for (int i = 0; i < BN; i++)
-        if (last && i >= k) blk[i * (BN + 1)] = 1.0;
-}
 __device__ __forceinline__ void pad_last_block(int n, int nr, int bn, int b, double *blk)
 {
     const int k = n % bn;

@@ -16,6 +16,7 @@
 // the last one answers (the reference's jw[] keeps the later place of a column stored twice).  When a row of A stores a column
 // twice a pivot may hit one target twice: `serial` hands such matrices' long rows to one thread.
 #include "level_schedule.hpp"
+#include "ilu_pattern.hpp"
 
 namespace {
 
@@ -28,35 +29,13 @@ struct Fac {
     const int *slptr, *sllong, *srows;  // the schedule: levels, first long row of each, rows in level order
 };
 
-// the last index in [lo, hi) whose key is c, or -1
-__device__ __forceinline__ int find_last(const int *key, int lo, int hi, int c)
-{
-    int a = lo, b = hi;
-    while (a < b) {
-        const int m = (a + b) >> 1;
-        if (key[m] <= c) a = m + 1; else b = m;
-    }
-    return (a > lo && key[a - 1] == c) ? a - 1 : -1;
-}
-
-struct Row { int i, l0, l1, u0, u1; };
-
-__device__ __forceinline__ Row row_of(const Fac &f, int i)
-{
-    return Row{i, f.lptr[i], f.lptr[i + 1], f.uptr[i], f.uptr[i + 1]};
-}
-
 // where row r keeps column c: in L, as the pivot, in U -- or nowhere
 __device__ __forceinline__ double *place(const Fac &f, const Row &r, int c)
 {
     if (c == r.i) return f.d + r.i;
-    if (c < r.i) {
-        const int p = find_last(f.lcol, r.l0, r.l1, c);
-        return p < 0 ? nullptr : f.lval + p;
-    }
-    const int p = find_last(f.uskey, r.u0, r.u1, c);
-    if (p < 0) return nullptr;
-    return f.uval + (f.uspos ? f.uspos[p] : p);
+    bool lower;
+    const int p = place_index(f, r, c, &lower);
+    return p < 0 ? nullptr : (lower ? f.lval : f.uval) + p;
 }
 
 __device__ __forceinline__ void update(const Fac &f, const Row &r, double l, int k)
