@@ -591,8 +591,9 @@ int  liship_sweep_f64(const liship_sweep_t *sweep, int mode, const double *b, do
 /* the same rows without a diagonal: x[i] = b[i] - sum v x[j]; b may equal x (ILU: forward on L, backward on L^T) */
 int  liship_sweep_plain_f64(const liship_sweep_t *sweep, const double *b, double *x, void *stream);
 
-/* ------------------------------------------------------------------ ILU(k) numerical factorisation (kernels/ilu.hip on kernels/level_schedule.hpp)
- * A = (aptr, aindex, avalue) as it lies in HBM.  The symbolic pattern: row i of L = lcol[lptr[i] .. lptr[i+1]) ascending (a column
+/* ------------------------------------------------------------------ ILU(k) numerical factorisation, the point form (kernels/ilu.hip on kernels/level_schedule.hpp)
+ * The block factorisation below at bn = 1 behind a struct of its own: this entry checks its arguments, translates (nr = n, bn = 1) and
+ * runs the same kernels.  A = (aptr, aindex, avalue) as it lies in HBM.  The symbolic pattern: row i of L = lcol[lptr[i] .. lptr[i+1]) ascending (a column
  * held twice: twice, side by side), of U = ucol[uptr[i] .. uptr[i+1]) in term order.  To find the place of a column in row i of U:
  * uskey = the row's columns ascending (ties by position), uspos = where each of them lies in ucol / uval; uspos NULL: the rows of
  * U are ascending as they are and uskey is ucol.  Of a column held twice the later place takes A's value and the updates.
@@ -610,9 +611,9 @@ typedef struct {
 } liship_ilu_t;
 int  liship_ilu_factor_f64(const liship_ilu_t *ilu, const liship_sweep_t *schedule, void *stream);
 
-/* ------------------------------------------------------------------ block ILU(k) on BSR storage (kernels/bilu.hip on kernels/level_schedule.hpp)
+/* ------------------------------------------------------------------ ILU(k) on blocks (kernels/ilu.hip on kernels/level_schedule.hpp): THE factorisation
  * liship_ilu_t with a block where it has a number: nr = ceil(n / bn) block rows, bn = 1, 2, 3; A = (aptr, aindex, avalue) the BSR
- * arrays in native layout (block k at avalue[k*bn*bn], column-major); the pattern over block rows and block columns; lval / uval
+ * arrays in native layout (block k at avalue[k*bn*bn], column-major) -- at bn = 1 a CSR matrix's own arrays, and every bit of the point form; the pattern over block rows and block columns; lval / uval
  * bn*bn doubles per pattern place, d the nr diagonal blocks, INVERTED on return (lis_array_ge, after 1.0 on the diagonal of the last
  * block's padding when bn does not divide n).  buf = L_ij Dinv_j stored, target -= buf U_jc: every entry of a product summed left to
  * right from its first product, then one subtraction.  `schedule` over the nr block rows as for liship_ilu_factor_f64: long block
@@ -627,7 +628,8 @@ typedef struct {
 int  liship_bilu_factor_f64(const liship_bilu_t *ilu, const liship_sweep_t *schedule, void *stream);
 /* one block sweep over a layout of ceil(n / bn) block rows whose val holds bn*bn doubles per place: x_i = b_i, then per term in order
  * x_i[r] = x_i[r] - ((a[r] xj[0] + a[r+bn] xj[1]) + a[r+2bn] xj[2]); dinv not NULL: x_i = dinv_i x_i at the end (same sums).  x reads
- * as +0.0 from n on and is never written there; b may equal x. */
+ * as +0.0 from n on and is never written there; b may equal x.  bn = 1: liship_sweep_plain_f64 (dinv NULL) or liship_sweep_f64 in mode
+ * LISHIP_SWEEP_MUL with wd = dinv, after this entry's own argument checks -- the same roundings in the same order. */
 int  liship_bilu_sweep_f64(const liship_sweep_t *sweep, int n, int bn, const double *dinv, const double *b, double *x, void *stream);
 /* dst block p = src block perm[p], blocks of bs doubles: liship_permute_gather_f64 for the values of a block layout */
 int  liship_block_gather_f64(int nblocks, int bs, const int *perm, const double *src, double *dst, void *stream);

@@ -14,7 +14,7 @@
  * for T (lis_amd_set_reference_reductions(T)), which reproduces the reference at T threads.
  *
  * From the pattern: the forward levels (level of row i = 1 + the largest level of the rows its L pattern names), which the
- * factorisation (kernels/ilu.hip) and the forward sweep share, and four level-ordered sweep layouts (lis_sweep.c, the engine
+ * factorisation (kernels/ilu.hip, a place of the pattern one double: bn = 1) and the forward sweep share, and four level-ordered sweep layouts (lis_sweep.c, the engine
  * SSOR runs on too): L, U, and for M^-H the transposed U^T (terms by source row ascending) and L^T (by source row descending,
  * ties by place in the source row) -- as row-wise sums these are the reference's scatters bit for bit.  The layouts hold copies of the values:
  * after every factorisation a gather kernel per layout fills them in HBM from the factor (the permutation kept from the build).
@@ -22,7 +22,7 @@
  *   psolveh: x = b; forward on U^T with x[i] = d[i] x[i] first; backward on L^T (no diagonal)    (ref :1086-1140)
  * The numbers are refactorised by every lis_precon_create, from A's values as they lie in HBM.
  *
- * BSR storage (bnr == bnc in 1..3): block ILU(k) (ref :102-109, :1289-1468, :1714-1819, :2006-2037; kernels/bilu.hip).  The same entry
+ * BSR storage (bnr == bnc in 1..3): block ILU(k) (ref :102-109, :1289-1468, :1714-1819, :2006-2037; the same kernels at bn = 2, 3).  The same entry
  * with a block where the point form has a number: the symbolic step runs unchanged on (nr, bptr, bindex) with the T row blocks of
  * LIS_GET_ISIE over the nr block rows, the schedule and the L and U layouts come from the same builders (a place holds bn*bn doubles,
  * filled by the block gather), d holds the INVERTED diagonal blocks.  The factorisation reads A's blocks in native layout: the HBM
@@ -35,7 +35,8 @@
 
 typedef struct {
 	int used, fill, T, n;                      /* n: the rows of the pattern -- A's rows, or its block rows */
-	int bn, an;                                /* BSR: the block size and A's rows (bn = 0: the point form on CSR storage) */
+	int bn, an;                                /* a place of the pattern holds bn x bn doubles (CSR storage: 1); A's rows */
+	int bsr;                                   /* A is held in BSR storage: which arrays the factorisation reads, no M^-H */
 	int *d_ap, *d_ai; double *d_av;            /* BSR whose HBM copy is held in row form: A's native arrays, uploaded for the factorisation */
 	int lnnz, unnz;
 	int serial;                                /* some row of A stores a column twice (liship_ilu_t.serial) */
@@ -54,7 +55,7 @@ typedef struct {
 	int next;
 } lisd_ilu;
 
-#define ENTRY_BS(e) ((size_t)((e)->bn ? (e)->bn * (e)->bn : 1))      /* doubles per place of the pattern */
+#define ENTRY_BS(e) ((size_t)((e)->bn * (e)->bn))      /* doubles per place of the pattern */
 
 static void entry_free(ilu_entry *e)
 {
@@ -205,8 +206,7 @@ static LIS_INT sweep_make(ilu_entry *e, int which)
 	{	int rc = liship_stream_synchronize(lisg.stream);
 		if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
 	/* per (block) row: b and x, and the diagonal (block) where the sweep has one */
-	const double rowlen = e->bn ? (double)e->bn : 1.0;
-	e->sw[which].bytes = lisi_sweep_bytes_places(n, nnz, (int)ENTRY_BS(e), 16.0 * rowlen + (lower ? 0.0 : 8.0 * (double)ENTRY_BS(e)));
+	e->sw[which].bytes = lisi_sweep_bytes_places(n, nnz, (int)ENTRY_BS(e), 16.0 * (double)e->bn + (lower ? 0.0 : 8.0 * (double)ENTRY_BS(e)));
 out:
 	free(src); free(tp); free(tc); free(tid);
 	if (err) { lisi_sweep_free(&e->sw[which]); (void)liship_free(e->d_src[which]); e->d_src[which] = NULL; }
@@ -217,8 +217,8 @@ static LIS_INT fill_sweep(ilu_entry *e, int which)
 {
 	const int nnz = e->sw[which].k.nnz;
 	const double *from = (which == SW_L || which == SW_LT) ? e->d_lval : e->d_uval;
-	if (nnz > 0 && e->bn) HIPCHK(liship_block_gather_f64(nnz, (int)ENTRY_BS(e), e->d_src[which], from, e->sw[which].val, lisg.stream));
-	else if (nnz > 0) HIPCHK(liship_permute_gather_f64(nnz, e->d_src[which], from, e->sw[which].val, lisg.stream));
+	if (nnz > 0 && e->bn == 1) HIPCHK(liship_permute_gather_f64(nnz, e->d_src[which], from, e->sw[which].val, lisg.stream));
+	else if (nnz > 0) HIPCHK(liship_block_gather_f64(nnz, (int)ENTRY_BS(e), e->d_src[which], from, e->sw[which].val, lisg.stream));
 	return LIS_SUCCESS;
 }
 
@@ -270,7 +270,7 @@ static LIS_INT entry_build(LIS_MATRIX A, ilu_entry *e, int fill, int T)
 	int *weight = NULL;
 	LIS_INT err;
 	const double t0 = lis_wtime();
-	e->used = 1; e->fill = fill; e->T = T; e->n = n; e->bn = block ? A->bnr : 0; e->an = A->n;
+	e->used = 1; e->fill = fill; e->T = T; e->n = n; e->bsr = block; e->bn = block ? A->bnr : 1; e->an = A->n;
 	if ((long long)n * (long long)ENTRY_BS(e) >= 0x7fffffffLL) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "the ILU factor does not fit\n"); goto out; }
 	if ((err = host_pattern(A, &ptr, &idx, &owned))) goto out;
 	if ((err = symbolic(e, n, ptr, idx, fill, T))) goto out;
@@ -331,7 +331,7 @@ static LIS_INT get_entry(LIS_MATRIX A, int fill, int T, ilu_entry **out)
 	if (!d->ilu) { d->ilu = calloc(1, sizeof(lisd_ilu)); if (!d->ilu) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(lisd_ilu)); }
 	lisd_ilu *il = (lisd_ilu *)d->ilu;
 	ilu_entry *e = NULL;
-	for (int t = 0; t < 2; t++) if (il->e[t].used && il->e[t].fill == fill && il->e[t].T == T && il->e[t].n == rows && il->e[t].bn == (block ? A->bnr : 0)) e = &il->e[t];
+	for (int t = 0; t < 2; t++) if (il->e[t].used && il->e[t].fill == fill && il->e[t].T == T && il->e[t].n == rows && il->e[t].bsr == block && il->e[t].bn == (block ? A->bnr : 1)) e = &il->e[t];
 	if (!e) {
 		e = &il->e[il->next];
 		il->next ^= 1;
@@ -346,35 +346,24 @@ static LIS_INT get_entry(LIS_MATRIX A, int fill, int T, ilu_entry **out)
 static LIS_INT factorise(LIS_MATRIX A, ilu_entry *e)
 {
 	lisd_mat *d = MDEV(A);
-	if (e->bn) {
-		liship_bilu_t bf;
-		memset(&bf, 0, sizeof(bf));
-		bf.n = e->an; bf.nr = e->n; bf.bn = e->bn; bf.serial = e->serial;
-		if (d->type == LIS_MATRIX_BSR && d->bptr && (A->bnnz == 0 || (d->bindex && d->value))) { bf.aptr = d->bptr; bf.aindex = d->bindex; bf.avalue = d->value; }
-		else {                                   /* the copy is held in its row form: A's native arrays, uploaded once per entry */
-			if (!e->d_ap) {
-				LISCHK(lisp_fill_matrix(A));
-				LISCHK(lisd_upload_i(&e->d_ap, A->bptr, (size_t)e->n + 1));
-				LISCHK(lisd_upload_i(&e->d_ai, A->bindex, (size_t)A->bnnz));
-				LISCHK(lisd_upload_d(&e->d_av, A->value, (size_t)A->bnnz * ENTRY_BS(e)));
-				HIPCHK(liship_stream_synchronize(lisg.stream));
-			}
-			bf.aptr = e->d_ap; bf.aindex = e->d_ai; bf.avalue = e->d_av;
-		}
-		bf.lptr = e->d_lp; bf.lcol = e->d_lc; bf.uptr = e->d_up; bf.ucol = e->d_uc; bf.uskey = e->d_uskey; bf.uspos = e->d_uspos;
-		bf.lval = e->d_lval; bf.uval = e->d_uval; bf.d = e->d_d;
-		HIPCHK(liship_bilu_factor_f64(&bf, &e->sched.k, lisg.stream));
-		e->factored = 1;
-		for (int w = 0; w < SW_COUNT; w++) if (e->sw[w].built) LISCHK(fill_sweep(e, w));
-		return LIS_SUCCESS;
-	}
-	liship_ilu_t f;
+	liship_bilu_t f;
 	memset(&f, 0, sizeof(f));
-	f.n = e->n; f.serial = e->serial;
-	f.aptr = d->ptr; f.aindex = d->index; f.avalue = d->value;
+	f.n = e->an; f.nr = e->n; f.bn = e->bn; f.serial = e->serial;
+	if (!e->bsr) { f.aptr = d->ptr; f.aindex = d->index; f.avalue = d->value; }
+	else if (d->type == LIS_MATRIX_BSR && d->bptr && (A->bnnz == 0 || (d->bindex && d->value))) { f.aptr = d->bptr; f.aindex = d->bindex; f.avalue = d->value; }
+	else {                                       /* the copy is held in its row form: A's native arrays, uploaded once per entry */
+		if (!e->d_ap) {
+			LISCHK(lisp_fill_matrix(A));
+			LISCHK(lisd_upload_i(&e->d_ap, A->bptr, (size_t)e->n + 1));
+			LISCHK(lisd_upload_i(&e->d_ai, A->bindex, (size_t)A->bnnz));
+			LISCHK(lisd_upload_d(&e->d_av, A->value, (size_t)A->bnnz * ENTRY_BS(e)));
+			HIPCHK(liship_stream_synchronize(lisg.stream));
+		}
+		f.aptr = e->d_ap; f.aindex = e->d_ai; f.avalue = e->d_av;
+	}
 	f.lptr = e->d_lp; f.lcol = e->d_lc; f.uptr = e->d_up; f.ucol = e->d_uc; f.uskey = e->d_uskey; f.uspos = e->d_uspos;
 	f.lval = e->d_lval; f.uval = e->d_uval; f.d = e->d_d;
-	HIPCHK(liship_ilu_factor_f64(&f, &e->sched.k, lisg.stream));
+	HIPCHK(liship_bilu_factor_f64(&f, &e->sched.k, lisg.stream));
 	e->factored = 1;
 	for (int w = 0; w < SW_COUNT; w++) if (e->sw[w].built) LISCHK(fill_sweep(e, w));
 	return LIS_SUCCESS;
@@ -416,28 +405,23 @@ LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st)
 	LISCHK(get_sweep(e, SW_L, &f));
 	LISCHK(get_sweep(e, SW_U, &b));
 	if (!e->factored) LISCHK(factorise(A, e));   /* (the HBM copy was rebuilt since lis_precon_create) */
-	lisg.last_ilu = 1; lisg.last_ilu_fill = st->fill; lisg.last_ilu_blocks = st->T; lisg.last_ilu_bn = e->bn;
+	lisg.last_ilu = 1; lisg.last_ilu_fill = st->fill; lisg.last_ilu_blocks = st->T; lisg.last_ilu_bn = e->bsr ? e->bn : 0;
 	lisg.last_ilu_levels = f->nlev; lisg.last_ilu_launches = f->ngroups + b->ngroups;
 	return LIS_SUCCESS;
 }
 
-/* x = M^-1 b: forward on L, backward on U and D; x = M^-H b: forward on U^T with D first, backward on L^T */
+#define NO_BSR_TRANSPOSE "M^-H of -p ilu on BSR storage is not served: the reference's OpenMP build applies M^-1 there\n"
+
+/* x = M^-1 b: forward on L, backward on U and D (every bn); x = M^-H b (CSR storage): forward on U^T with D first, backward on L^T */
 static LIS_INT apply_on(ilu_entry *e, int transposed, const double *b, double *x)
 {
 	const liship_sweep_t *first, *second;
-	if (e->bn) {
-		if (transposed) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "M^-H of -p ilu on BSR storage is not served: the reference's OpenMP build applies M^-1 there\n");
-		LISCHK(get_sweep(e, SW_L, &first));
-		LISCHK(get_sweep(e, SW_U, &second));
-		HIPCHK(liship_bilu_sweep_f64(first, e->an, e->bn, NULL, b, x, lisg.stream));
-		HIPCHK(liship_bilu_sweep_f64(second, e->an, e->bn, e->d_d, x, x, lisg.stream));
-		return LIS_SUCCESS;
-	}
+	if (transposed && e->bsr) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, NO_BSR_TRANSPOSE);
 	LISCHK(get_sweep(e, transposed ? SW_UT : SW_L, &first));
 	LISCHK(get_sweep(e, transposed ? SW_LT : SW_U, &second));
 	if (!transposed) {
-		HIPCHK(liship_sweep_plain_f64(first, b, x, lisg.stream));
-		HIPCHK(liship_sweep_f64(second, LISHIP_SWEEP_MUL, x, x, e->d_d, lisg.stream));
+		HIPCHK(liship_bilu_sweep_f64(first, e->an, e->bn, NULL, b, x, lisg.stream));
+		HIPCHK(liship_bilu_sweep_f64(second, e->an, e->bn, e->d_d, x, x, lisg.stream));
 	} else {
 		HIPCHK(liship_sweep_f64(first, LISHIP_SWEEP_MUL, b, x, e->d_d, lisg.stream));
 		HIPCHK(liship_sweep_plain_f64(second, x, x, lisg.stream));
@@ -506,7 +490,7 @@ LIS_INT lis_amd_ilu_psolve(LIS_MATRIX A, LIS_INT fill, LIS_VECTOR B, LIS_VECTOR 
 	ilu_entry *e;
 	LISCHK(tool_entry(A, fill, &e));
 	if (B->n != A->n || X->n != A->n) return LISI_ERR(LIS_ERR_ILL_ARG, "sizes of A, B and X do not match\n");
-	if (e->bn && transposed) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "M^-H of -p ilu on BSR storage is not served: the reference's OpenMP build applies M^-1 there\n");
+	if (e->bsr && transposed) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, NO_BSR_TRANSPOSE);
 	if (!e->factored) LISCHK(factorise(A, e));
 	double *db, *dx;
 	LISCHK(lisd_vec_in(B, &db));

@@ -1,4 +1,4 @@
-// block_ops.hpp -- what the kernels on dense bn x bn blocks share (bdiag.hip: -p bjacobi; bilu.hip: -p ilu on BSR storage): the
+// block_ops.hpp -- what the kernels on dense bn x bn blocks share (bdiag.hip: -p bjacobi; ilu.hip: -p ilu): the
 // reference's block inverse, lis_array_ge, operation for operation, and the 1.0 on the diagonal of the last block's padding.
 #pragma once
 #include "common.hpp"

@@ -1,5 +1,5 @@
-// level_schedule.hpp -- the walker of a level schedule (liship_sweep_t), shared by the triangular sweeps (sptrsv.hip) and the ILU(k)
-// factorisation (ilu.hip).
+// level_schedule.hpp -- the walker of a level schedule (liship_sweep_t), shared by the triangular sweeps (sptrsv.hip) and by the ILU(k)
+// factorisation and block sweeps (ilu.hip).
 //
 // A schedule is a list of levels; the rows of one level do not depend on each other, every row depends only on rows of earlier
 // levels.  Inside a level the short rows come first, the long ones last (lptr[l] .. llong[l] .. lptr[l + 1]).  Dependencies

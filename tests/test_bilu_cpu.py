@@ -11,6 +11,7 @@ import pytest
 
 import bilu_cases
 import bilu_oracle
+import ilu_cases
 import lis_amd
 import orc
 
@@ -106,6 +107,68 @@ def test_block_size_one_is_the_point_ilu():
         f, _ = model("nonsym", 1, fill)
         g = ilu_oracle.factor(*bilu_oracle.csr_to_bsr(ptr, idx, val, 1), fill)
         assert bilu_cases.factor_differences(f, g) == []
+
+
+SPECIAL_PIVOTS = (0.0, -0.0, float("inf"), 5e-324, float("nan"))
+
+
+def special_pivot_systems():
+    """dense 3-row matrices with the special value as the first pivot (rows 1 and 2 scale by its inverse and are updated through
+    it) and as the second (reached through an update of its own)"""
+    for p in SPECIAL_PIVOTS:
+        for at in (0, 1):
+            val = np.array([4.0, -1.0, 0.5, -2.0, 3.0, 1.5, 0.25, -0.75, 5.0])
+            val[4 * at] = p
+            if at == 1:
+                val[1] = 0.0                                                      # row 1's pivot stays what was stored: 3.0 -> p, minus l * 0.0
+            yield (p, at), (np.array([0, 3, 6, 9], np.int32), np.array([0, 1, 2, 0, 1, 2, 0, 1, 2], np.int32), val)
+
+
+def test_block_size_one_is_the_point_model_in_every_bit():
+    """the identity kernels/ilu.hip rests on: the point form is the block form at bn = 1.  On the CSR arrays as they are
+    (unsorted rows, columns stored twice, a row without a diagonal entry), for every fill and row-block count: the same pattern in the
+    same term order, every bit of L, U and D, every bit of M^-1 b; and the same through pivots of +0.0, -0.0, inf, a denormal and NaN
+    (NaN sign and payload left out, as everywhere in this project)"""
+    import ilu_oracle
+    cases = [((name, fill, T), ilu_cases.system(name), fill, T, True) for name in ilu_cases.NAMED for fill in ilu_cases.FILLS for T in ilu_cases.THREADS]
+    cases += [(tag, sys3, 0, 1, False) for tag, sys3 in special_pivot_systems()]
+    assert len(cases) == len(ilu_cases.NAMED) * len(ilu_cases.FILLS) * len(ilu_cases.THREADS) + 2 * len(SPECIAL_PIVOTS)
+    for tag, (ptr, idx, val), fill, T, payload in cases:
+        n = len(ptr) - 1
+        b = bilu_cases.rhs(n)
+        with np.errstate(all="ignore"):
+            point = ilu_oracle.factor(ptr, idx, val, fill, T)
+            block = bilu_oracle.factor(ptr, idx, val, 1, n, fill, T)
+            assert ilu_cases.factor_differences(block, point, payload) == [], tag
+            assert ilu_cases.same_bits(bilu_oracle.psolve(block, b, T), ilu_oracle.psolve(point, b, T), payload), tag
+    special = [ilu_oracle.factor(*sys3, 0, 1)["D"] for _, sys3 in special_pivot_systems()]
+    assert any(np.isinf(d).any() for d in special) and any(np.isnan(d).any() for d in special)      # the special pivots did reach the factor
+
+
+def test_ilu_kernels_are_the_ones_meant_and_keep_their_blocks_in_registers(tmp_path):
+    """kernels/ilu.hip compiled to gfx950 assembly with the library's flags (csrc/Makefile, HIPFLAGS), its kernel metadata read: ONE
+    factorisation (level and run kernel for bn = 1, 2, 3) that CSR and BSR storage share, block sweeps for bn = 2, 3 only (bn = 1 runs
+    the sweeps of sptrsv.hip), one gather; and no kernel with more private memory than before the point and block forms were joined
+    (factorisation 24 bytes at bn = 1, 2, none at bn = 3; sweeps and gather none): a bn = 3 block that leaves the registers shows here"""
+    import re
+    csrc = os.path.join(os.path.dirname(HERE), "lis_amd", "csrc")
+    hipcc = os.environ.get("HIPCC") or os.path.join(os.environ.get("ROCM", "/opt/rocm"), "bin", "hipcc")
+    asm = str(tmp_path / "ilu.s")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(os.path.dirname(HERE), "include"),
+                    "-I" + os.path.join(csrc, "kernels"), "--cuda-device-only", "-S", os.path.join(csrc, "kernels", "ilu.hip"), "-o", asm],
+                   check=True, capture_output=True, text=True)
+    meta = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", open(asm).read())
+    sizes = {name: int(size) for name, size in meta}
+    factor = {(k, bn): [s for name, s in sizes.items() if k in name and "FacRowsILi%dE" % bn in name] for k in ("level_kernel", "run_kernel") for bn in (1, 2, 3)}
+    sweeps = {(k, bn, d): [s for name, s in sizes.items() if k in name and "BSweepRowsILi%dELb%dE" % (bn, d) in name]
+              for k in ("level_kernel", "run_kernel") for bn in (2, 3) for d in (0, 1)}
+    gather = [s for name, s in sizes.items() if "block_gather_kernel" in name]
+    assert all(len(v) == 1 for v in factor.values()) and all(len(v) == 1 for v in sweeps.values()) and len(gather) == 1, sorted(sizes)
+    assert len(sizes) == 6 + 8 + 1, sorted(sizes)
+    print("ILU KERNELS private segment:", sizes)
+    for (k, bn), (size,) in factor.items():
+        assert size <= (24 if bn < 3 else 0), (k, bn, size)
+    assert all(size == 0 for (size,) in sweeps.values()) and gather == [0], sizes
 
 
 def test_model_factor_reproduces_A_on_its_pattern():

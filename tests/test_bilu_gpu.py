@@ -1,4 +1,4 @@
-"""-p ilu on BSR storage on the GPU (lis_ilu.c on lis_sweep.c, kernels/bilu.hip) against tests/bilu_oracle.py in every bit, against
+"""-p ilu on BSR storage on the GPU (lis_ilu.c on lis_sweep.c, kernels/ilu.hip) against tests/bilu_oracle.py in every bit, against
 tests/golden/bilu_bits.npz, and against the reference library at one thread in a child process (bilu_cases: the reference's block ILU
 is defined for bn <= 3 and usable at one thread only).
 
@@ -197,6 +197,68 @@ def test_zero_pivot_block_without_padding(lib, bn):
         wx = bilu_oracle.psolve(want, bilu_cases.rhs(n), 1)
         assert (np.isinf(want["D"]).any() if bn == 1 else np.isnan(want["D"]).any()) and np.isnan(wx).any() and np.isfinite(wx[:n // 2]).all()
         check_against_model(lib, bsr, fill, 1, want, wx, bilu_cases.rhs(n), ("zero pivot", bn, fill))
+
+
+_doors = {}
+
+
+def two_doors_system(name):
+    """(ptr, idx, val) given to the library once as CSR and once as BSR with 1 x 1 blocks.  "handmade": columns stored twice, hence
+    `serial`.  "edges": built to order (tests/ssor_cases.py) for the launch edges of the one factorisation kernel -- forward levels of
+    1024 rows (the last size that joins a run), 1025 (the first on a launch of its own) and 30 (a run); rows of 63 kept terms (the last
+    a thread takes) and of 64 (the first a workgroup takes) in the level on its own launch and in the run.  The rows from 1024 on
+    hold no term of U (the backward pattern's first level mirrors onto them), so their L terms are all their kept terms at fill 0"""
+    if name not in _doors:
+        if name == "handmade":
+            _doors[name] = ilu_cases.handmade()
+        else:
+            fwd = ssor_cases._sizes([1024, 1025, 30], {1: (63, 64), 2: (63, 64, 70)})
+            bwd = ssor_cases._sizes([1055, 1024])
+            _doors[name] = ssor_cases.matrices(ssor_cases.pattern(fwd, 41), ssor_cases.pattern(bwd, 42), 43)[0]
+    return _doors[name]
+
+
+@pytest.mark.parametrize("fill", [0, 1])
+@pytest.mark.parametrize("name", ["handmade", "edges"])
+def test_csr_and_bsr_1x1_give_the_same_factor_and_psolve(lib, name, fill):
+    """one factorisation behind two doors: the same arrays as a CSR matrix and as a BSR matrix of 1 x 1 blocks give L, U, D
+    (lis_amd_ilu_copy) and M^-1 b (lis_amd_ilu_psolve) equal in every bit, in the default mode and in the reference-order mode at 1
+    and 3 row blocks.  Each case first shows through lis_amd_ilu_factor_info that it got the launches it is for"""
+    from test_ilu_gpu import library_factor as csr_factor
+    ptr, idx, val = two_doors_system(name)
+    n = len(ptr) - 1
+    b = np.random.default_rng(6).uniform(-1.0, 1.0, n)
+    for mode in (0, 1, 3):
+        assert lib.dll.lis_amd_set_reference_reductions(mode) == 0
+        try:
+            Ac, Ab = lisdrv.make_csr(lib, ptr, idx, val), bilu_cases.make_bsr(lib, (ptr, idx, val, 1, n))
+            fc, fb = (C.c_int * 6)(), (C.c_int * 6)()
+            assert lib.dll.lis_amd_ilu_factor_info(Ac, fill, fc) == 0 and lib.dll.lis_amd_ilu_factor_info(Ab, fill, fb) == 0
+            assert list(fc) == list(fb), (name, fill, mode, list(fc), list(fb))
+            if mode < 3:
+                Lc, Uc = bilu_oracle.symbolic(ptr, idx, fill, 1)
+                weight = [len(l) + len(u) for l, u in zip(Lc, Uc)]
+                sizes = np.bincount(ssor_cases.levels_of([[(c, 0.0) for c in r] for r in Lc], 0)).tolist()
+                print("TWO DOORS %s fill %d mode %d factor=%s level sizes=%s longest=%d" % (name, fill, mode, list(fc), sizes[:8], max(weight)))
+                if name == "handmade":
+                    assert fc[5] == 1                                                  # serial: a column stored twice
+                elif fill == 0:
+                    assert sizes == [1024, 1025, 30] and fc[:3] == [3, 3, 1]            # run, own launch, run
+                    assert 63 in weight[1024:2049] and 64 in weight[1024:2049] and fc[3] == 1       # thread against workgroup on the own launch
+                    assert 63 in weight[2049:] and 64 in weight[2049:] and fc[4] == 2 and fc[5] == 0   # and inside the run: the rows of 64 and 70
+                else:                                                                  # the fill-in chains the 1025 rows: small levels, one run, longer rows
+                    assert fc[0] == len(sizes) > 3 and fc[4] >= 3 and fc[5] == 0 and max(weight) > 2 * ssor_cases.LONG_ROW
+            got_c, got_b = csr_factor(lib, Ac, fill), bilu_cases.library_factor(lib, Ab, fill)
+            assert bilu_cases.factor_differences(got_b, got_c) == [], (name, fill, mode)
+            assert name == "handmade" or np.isfinite(got_c["D"]).all()                 # (handmade at 3 row blocks: a row without a stored diagonal entry alone in its block, 1 / 0)
+            for alias in (False, True):
+                ec, xc = bilu_cases.library_psolve(lib, Ac, fill, b, alias)
+                eb, xb = bilu_cases.library_psolve(lib, Ab, fill, b, alias)
+                assert ec == 0 and eb == 0 and bilu_cases.same_bits(xb, xc), (name, fill, mode, alias)
+            lib.lis_matrix_destroy(Ac)
+            lib.lis_matrix_destroy(Ab)
+        finally:
+            lib.dll.lis_amd_set_reference_reductions(0)
 
 
 def last_ilu(lib):

@@ -1,4 +1,4 @@
-"""The launch edges of the block ILU (kernels/bilu.hip on kernels/level_schedule.hpp), on BSR matrices built to order: each case first
+"""The launch edges of the block ILU (kernels/ilu.hip on kernels/level_schedule.hpp), on BSR matrices built to order: each case first
 proves through lis_amd_ilu_factor_info / lis_amd_ilu_info that it got the launches it is for -- the levels and launches the library
 reports equal the ones computed here from the model's pattern with the schedule rules restated in tests/ssor_cases.py -- and then
 holds factor and psolve (b apart from x, and b aliased with x) to tests/bilu_oracle.py in every bit.
