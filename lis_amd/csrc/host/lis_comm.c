@@ -467,7 +467,7 @@ static LIS_INT halo_rccl(LIS_MATRIX A, double *dx, void *stream)
 	LIS_COMMTABLE t = A->commtable;
 	const LIS_INT n = A->n, pad = t->pad;
 	/* EVERY forward exchange goes over the halo communicator when there is one, whichever stream it is queued on.  Whether a product overlaps its exchange with the
-	 * interior rows is decided rank by rank (lisd_spmv: "at least half of my rows touch no ghost column"), so two neighbours may well decide differently -- 3 planes
+	 * interior rows is decided rank by rank (lis_product.c overlap_ok: "at least half of my rows touch no ghost column"), so two neighbours may well decide differently -- 3 planes
 	 * per rank on 3 ranks: the end ranks overlap, the middle one does not -- and a Send on one communicator never meets a Recv on the other (the job hung
 	 * until the watchdog).  The communicator must therefore not depend on that decision; only the STREAM does.  Order on each communicator is program order on every
 	 * rank (exchanges on nccl_halo, folds and reverse exchanges on nccl_comm), and on one rank the two never run concurrently: an overlapped exchange is fenced

@@ -479,10 +479,6 @@ static void fmt_find_plane(lisd_mat *d, const int *host_dia_offsets)
 		if (liship_ell_scan_band(d->n, d->maxnzr, d->index, &plane, lisg.stream) == 0) d->xs_rows = plane;
 	}
 }
-static void fmt_strips(const lisd_mat *d)        /* in front of every whole-matrix launch of a native ELL / DIA kernel */
-{
-	(void)liship_spmv_formats_set_plane((d->xs_rows > 0 && (size_t)d->n * sizeof(double) > ((size_t)256 << 20)) ? d->xs_rows : 0);
-}
 
 /* the permutation the last reordered plan found (liship_csr_plan_reorder), tried first by the next plan of the same size: a program that edits A->value between solves
  * rebuilds the HBM copy and its plan each time, and the walk (1.4 s on the Queen-class matrix) is most of that.  One entry; a hint is only ever a hint. */
@@ -1400,180 +1396,7 @@ LIS_INT lis_amd_matrix_host_modified(LIS_MATRIX A)
 	return LIS_SUCCESS;
 }
 
-/* y = A x on device pointers.  In a multi-GPU job the ghost part of x is filled first; the rows that do
- * not touch ghosts are issued before the exchange completes (same stream ordering via RCCL). */
-LIS_INT lisd_spmv(LIS_MATRIX A, double *dx, double *dy)
-{
-	lisd_mat *d = MDEV(A);
-	LISCHK(lisd_mat_ready(A));
-	d->served++;
-	if (lisg.nprocs > 1 && A->commtable && d->type == LIS_MATRIX_CSR && !lisg.no_overlap &&
-	    d->inner_end - d->inner_begin >= d->n / 2) {
-		/* rows [inner_begin, inner_end) reference no ghost column: they run while the halo is in flight; the
-		 * boundary rows follow once the ghosts have landed (same kernel, same bits: rows are independent) */
-		LISCHK(lisc_halo_begin(A, dx));
-		HIPCHK(liship_spmv_csr_rows_f64(d->plan, d->inner_begin, d->inner_end, d->ptr, d->index, d->value, dx, dy, lisg.stream));
-		LISCHK(lisc_halo_end(A, dx));
-		if (d->inner_begin > 0)
-			HIPCHK(liship_spmv_csr_rows_f64(d->plan, 0, d->inner_begin, d->ptr, d->index, d->value, dx, dy, lisg.stream));
-		if (d->inner_end < d->n)
-			HIPCHK(liship_spmv_csr_rows_f64(d->plan, d->inner_end, d->n, d->ptr, d->index, d->value, dx, dy, lisg.stream));
-		return LIS_SUCCESS;
-	}
-	if (lisg.nprocs > 1 && A->commtable && (d->type == LIS_MATRIX_ELL || d->type == LIS_MATRIX_DIA) && !lisg.no_overlap &&
-	    d->inner_end - d->inner_begin >= d->n / 2) {
-		/* the native ELL / DIA layouts likewise: interior rows under the halo, boundary rows behind it (an odd cut makes that part run
-		 * one row per lane) */
-		LISCHK(lisc_halo_begin(A, dx));
-		for (int part = 0; part < 3; part++) {
-			const int rb = part == 0 ? d->inner_begin : part == 1 ? 0 : d->inner_end, re = part == 0 ? d->inner_end : part == 1 ? d->inner_begin : d->n;
-			if (part == 1) LISCHK(lisc_halo_end(A, dx));
-			if (rb >= re) continue;
-			if (d->type == LIS_MATRIX_ELL) HIPCHK(liship_spmv_ell_rows_f64(d->n, d->maxnzr, d->index, d->ell_codes, d->ell_dict, d->value, dx, dy, rb, re, lisg.stream));
-			else HIPCHK(liship_spmv_dia_rows_f64(d->n, d->np, d->nnd, d->index, d->value, dx, dy, rb, re, lisg.stream));
-		}
-		return LIS_SUCCESS;
-	}
-	if (lisg.nprocs > 1 && A->commtable && d->type == LIS_MATRIX_BSR && !lisg.no_overlap && d->inner_end - d->inner_begin >= d->nr / 2) {
-		/* BSR likewise, in block rows (inner_begin / inner_end count block rows for this format) */
-		LISCHK(lisc_halo_begin(A, dx));
-		HIPCHK(liship_spmv_bsr_rows_f64(d->nr, A->bnnz, d->bnr, d->bnc, d->bptr, d->bindex, d->value, dx, dy, d->inner_begin, d->inner_end, lisg.stream));
-		LISCHK(lisc_halo_end(A, dx));
-		HIPCHK(liship_spmv_bsr_rows_f64(d->nr, A->bnnz, d->bnr, d->bnc, d->bptr, d->bindex, d->value, dx, dy, 0, d->inner_begin, lisg.stream));
-		HIPCHK(liship_spmv_bsr_rows_f64(d->nr, A->bnnz, d->bnr, d->bnc, d->bptr, d->bindex, d->value, dx, dy, d->inner_end, d->nr, lisg.stream));
-		return LIS_SUCCESS;
-	}
-	if (lisg.nprocs > 1 && A->commtable) LISCHK(lisc_halo_device(A, dx));
-	if (d->split_jad) {
-		/* y = (D x + L x) + U x, the two sparse sums each formed from 0 on their own: w = L x; w = D.*x + 1*w (exact: 1*w is w);
-		 * y = U x; y += 1*w (a + b and b + a are the same double) */
-		HIPCHK(liship_spmv_csr_f64(d->plan, d->ptr, d->index, d->value, dx, d->jw, lisg.stream));
-		HIPCHK(liship_pmul_xpay_f64(d->n, d->dsplit, dx, 1.0, d->jw, lisg.stream));
-		HIPCHK(liship_spmv_csr_f64(d->u_plan, d->u_ptr, d->u_index, d->u_value, dx, dy, lisg.stream));
-		HIPCHK(liship_axpy_f64(d->n, 1.0, d->jw, dy, lisg.stream));
-		return LIS_SUCCESS;
-	}
-	switch (d->type) {
-	case LIS_MATRIX_CSR:
-		HIPCHK(liship_spmv_csr_f64(d->plan, d->ptr, d->index, d->value, dx, dy, lisg.stream));
-		break;
-	case LIS_MATRIX_ELL:
-		fmt_strips(d);
-		if (d->ell_codes) {
-			int rc = liship_spmv_ell_coded_f64(d->n, d->maxnzr, d->ell_codes, d->ell_dict, d->value, dx, dy, NULL, -1, NULL, NULL, lisg.stream);
-			if (rc == 0) break;
-			if (rc != LISHIP_ERR_ARG) HIPCHK(rc);
-		}
-		HIPCHK(liship_spmv_ell_f64(d->n, d->maxnzr, d->index, d->value, dx, dy, lisg.stream));
-		break;
-	case LIS_MATRIX_DIA:
-		fmt_strips(d);
-		HIPCHK(liship_spmv_dia_f64(d->n, d->np, d->nnd, d->index, d->value, dx, dy, lisg.stream));
-		break;
-	case LIS_MATRIX_JAD:
-		HIPCHK(liship_spmv_jad_f64(d->n, d->maxnzr, d->row, d->ptr, d->index, d->value, dx, dy, lisg.stream));
-		break;
-	case LIS_MATRIX_BSR:
-		HIPCHK(liship_spmv_bsr_nnz_f64(d->nr, A->bnnz, d->bnr, d->bnc, d->bptr, d->bindex, d->value, dx, dy, lisg.stream));
-		break;
-	default:
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", d->type);
-	}
-	return LIS_SUCCESS;
-}
-
 /* ------------------------------------------------------------------ reductions -> host scalars */
-/* y = A x with <w,y> (and <y,y>) formed in the product's epilogue when the kernel can (CSR row-gather);
- * otherwise the product followed by one reduction pass.  The sums land in lisg.reduce_out[0..1]. */
-LIS_INT lisd_spmv_dot_launch(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq)
-{
-	return lisd_spmv_dot_launch_to(A, dx, dy, dw, want_sumsq, lisg.reduce_out);
-}
-
-LIS_INT lisd_spmv_dot_launch_to(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq, double *result)
-{
-	lisd_mat *d = MDEV(A);
-	LISCHK(lisd_mat_ready(A));
-	d->served++;                          /* (a branch below that falls back to lisd_spmv counts the product twice: the count is a threshold, not a statistic) */
-	int nblocks = 0;
-	if (d->split_jad) {
-		LISCHK(lisd_spmv(A, dx, dy));
-		if (want_sumsq) HIPCHK(liship_dot2_f64(d->n, dy, dw, result, lisg.reduce_work, lisg.stream));
-		else HIPCHK(liship_dot_f64(d->n, dw, dy, result, lisg.reduce_work, lisg.stream));
-		return LIS_SUCCESS;
-	}
-	if (d->type == LIS_MATRIX_CSR && d->plan) (void)liship_csr_plan_info(d->plan, NULL, NULL, &nblocks);
-	/* the three parts launch at most nblocks + 2 row blocks (each cut splits one): all of them must find a slot for
-	 * their partial sums BEFORE the first part is launched -- otherwise the plain overlapped product + one dot pass */
-	const int slots_ok = (d->type == LIS_MATRIX_CSR && d->plan)
-		? (size_t)liship_csr_plan_fused_slots(d->plan) <= liship_reduce_work_bytes() / sizeof(double) / 4
-		: (size_t)nblocks + 2 <= liship_reduce_work_bytes() / sizeof(double) / 4;
-	/* a plan whose products run the team / staged kernels has no per-row-block epilogue: the plain (overlapped) product and one reduction pass */
-	const int fused = !(d->type == LIS_MATRIX_CSR && d->plan) || liship_csr_plan_fused_dots(d->plan);
-	if (d->type == LIS_MATRIX_CSR && !fused) {
-		LISCHK(lisd_spmv(A, dx, dy));
-	} else if (d->type == LIS_MATRIX_CSR && !lisg.no_fusion && lisg.nprocs > 1 && A->commtable && !lisg.no_overlap &&
-	    d->inner_end - d->inner_begin >= d->n / 2 && !slots_ok) {
-		LISCHK(lisd_spmv(A, dx, dy));
-	} else if (d->type == LIS_MATRIX_CSR && !lisg.no_fusion && lisg.nprocs > 1 && A->commtable && !lisg.no_overlap &&
-	    d->inner_end - d->inner_begin >= d->n / 2) {
-		/* as lisd_spmv: interior rows while the halo travels, boundary rows after it; every part parks its
-		 * per-block partial sums, one fold at the end */
-		int used = 0, total = 0;
-		LISCHK(lisc_halo_begin(A, dx));
-		int rc = liship_spmv_csr_rows_dot_f64(d->plan, d->inner_begin, d->inner_end, d->ptr, d->index, d->value, dx, dy, dw,
-		                                      want_sumsq, lisg.reduce_work, 0, &used, lisg.stream);
-		LISCHK(lisc_halo_end(A, dx));
-		if (rc == 0) {
-			total = used;
-			if (d->inner_begin > 0) {
-				HIPCHK(liship_spmv_csr_rows_dot_f64(d->plan, 0, d->inner_begin, d->ptr, d->index, d->value, dx, dy, dw,
-				                                    want_sumsq, lisg.reduce_work, total, &used, lisg.stream));
-				total += used;
-			}
-			if (d->inner_end < d->n) {
-				HIPCHK(liship_spmv_csr_rows_dot_f64(d->plan, d->inner_end, d->n, d->ptr, d->index, d->value, dx, dy, dw,
-				                                    want_sumsq, lisg.reduce_work, total, &used, lisg.stream));
-				total += used;
-			}
-			HIPCHK(liship_spmv_csr_dot_finish_f64(total, want_sumsq, result, lisg.reduce_work, lisg.stream));
-			return LIS_SUCCESS;
-		}
-		if (rc != LISHIP_ERR_ARG) HIPCHK(rc);
-		HIPCHK(liship_spmv_csr_f64(d->plan, d->ptr, d->index, d->value, dx, dy, lisg.stream));   /* the ghosts are in */
-	} else if (d->type == LIS_MATRIX_CSR && !lisg.no_fusion) {
-		if (lisg.nprocs > 1 && A->commtable) LISCHK(lisc_halo_device(A, dx));
-		int rc = liship_spmv_csr_dot_f64(d->plan, d->ptr, d->index, d->value, dx, dy, dw, want_sumsq,
-		                                 result, lisg.reduce_work, lisg.stream);
-		if (rc == 0) return LIS_SUCCESS;
-		if (rc != LISHIP_ERR_ARG) HIPCHK(rc);
-		HIPCHK(liship_spmv_csr_f64(d->plan, d->ptr, d->index, d->value, dx, dy, lisg.stream));
-	} else if ((d->type == LIS_MATRIX_ELL || d->type == LIS_MATRIX_DIA) && !lisg.no_fusion) {
-		if (lisg.nprocs > 1 && A->commtable) LISCHK(lisc_halo_device(A, dx));
-		fmt_strips(d);
-		int rc = (d->type == LIS_MATRIX_ELL && d->ell_codes)
-			? liship_spmv_ell_coded_f64(d->n, d->maxnzr, d->ell_codes, d->ell_dict, d->value, dx, dy, dw, want_sumsq ? 1 : 0, result, lisg.reduce_work, lisg.stream)
-			: (d->type == LIS_MATRIX_ELL)
-			? liship_spmv_ell_dot_f64(d->n, d->maxnzr, d->index, d->value, dx, dy, dw, want_sumsq, result, lisg.reduce_work, lisg.stream)
-			: liship_spmv_dia_dot_f64(d->n, d->np, d->nnd, d->index, d->value, dx, dy, dw, want_sumsq, result, lisg.reduce_work, lisg.stream);
-		if (rc == 0) return LIS_SUCCESS;
-		if (rc != LISHIP_ERR_ARG) HIPCHK(rc);
-		if (d->type == LIS_MATRIX_ELL) HIPCHK(liship_spmv_ell_f64(d->n, d->maxnzr, d->index, d->value, dx, dy, lisg.stream));
-		else HIPCHK(liship_spmv_dia_f64(d->n, d->np, d->nnd, d->index, d->value, dx, dy, lisg.stream));
-	} else if (d->type == LIS_MATRIX_BSR && d->bnr == d->bnc && !lisg.no_fusion) {
-		if (lisg.nprocs > 1 && A->commtable) LISCHK(lisc_halo_device(A, dx));
-		int rc = liship_spmv_bsr_dot_f64(d->nr, d->n, A->bnnz, d->bnr, d->bptr, d->bindex, d->value, dx, dy, dw, want_sumsq,
-		                                 result, lisg.reduce_work, lisg.stream);
-		if (rc == 0) return LIS_SUCCESS;
-		if (rc != LISHIP_ERR_ARG) HIPCHK(rc);
-		HIPCHK(liship_spmv_bsr_nnz_f64(d->nr, A->bnnz, d->bnr, d->bnc, d->bptr, d->bindex, d->value, dx, dy, lisg.stream));
-	} else LISCHK(lisd_spmv(A, dx, dy));
-	/* over A's n rows: the row form of a split BSR matrix (d->n) counts the padding rows of its last block row too, which would move the chunk borders of the reference-order sums */
-	if (want_sumsq) HIPCHK(liship_dot2_f64(A->n, dy, dw, result, lisg.reduce_work, lisg.stream));
-	else HIPCHK(liship_dot_f64(A->n, dw, dy, result, lisg.reduce_work, lisg.stream));
-	return LIS_SUCCESS;
-}
-
 LIS_INT lisd_fetch(int count, double *out)
 {
 	if (lisg.nprocs > 1 && lisg.comm_kind == 1)        /* RCCL gathers the partials straight from HBM: one sync, not two */

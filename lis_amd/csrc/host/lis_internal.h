@@ -63,7 +63,7 @@ typedef struct {
 	int *ptr, *index, *row, *bptr, *bindex;
 	double *value;
 	liship_csr_plan_t plan;
-	int xs_rows;               /* native ELL / DIA: rows per plane of the structured grid (largest offset most rows reach), 0 = none: the XCD strips of their kernels (lis_device.c fmt_strips) */
+	int xs_rows;               /* native ELL / DIA: rows per plane of the structured grid (largest offset most rows reach), 0 = none: the XCD strips of their kernels (lis_product.c fmt_strips) */
 	unsigned char *ell_codes;  /* ELL: one-byte column codes + dictionary when the matrix allows it (liship_ell_encode_indices) */
 	int *ell_dict;
 	/* A^T as a CSR in the reference's scatter order (lis_matvech.c), built on the first lis_matvech */
@@ -247,7 +247,7 @@ int     lisd_malloc(void **out, size_t bytes);                /* liship_malloc t
 int     lis_amd_trim_count(void);                             /* lis_amd_trim(), returning the number of buffers released */
 LIS_INT lisd_mat_ready_t(LIS_MATRIX A);                       /* build / upload the transposed operator */
 LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy);    /* y[0..np) = A^T x, ghost rows reduced to owners */
-LIS_INT lisd_spmv(LIS_MATRIX A, double *dx, double *dy);      /* y = A x on device pointers (halo included) */
+LIS_INT lisd_spmv(LIS_MATRIX A, double *dx, double *dy);      /* y = A x on device pointers (halo included); lis_product.c, like the two fused forms below */
 LIS_INT lisd_csr_plan(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);   /* row split + index codes */
 LIS_INT lisd_csr_plan_cols(liship_csr_plan_t *plan, int n, int ncols, const int *dptr, const int *dindex, const double *dvalue);   /* ... of a rank's local rows with ghost columns [n, ncols) */
 LIS_INT lisd_csr_plan_plain(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);    /* the same without a renumbered form (matrices no solve iterates on) */
@@ -279,6 +279,8 @@ LIS_INT lisc_allgather_host(const void *send, void *recv, size_t bytes);
 
 /* ---- matrix internals shared between files */
 LIS_INT lisi_matrix_check(LIS_MATRIX A, int level);
+int     lisi_format_served(LIS_INT type);                          /* one of the six storage formats whose products are served (lis_matvec.c) */
+void    lisi_raw_product(LIS_MATRIX A, LIS_INT fmt, LIS_SCALAR x[], LIS_SCALAR y[], int transposed);   /* lis_matvec_<fmt> / lis_matvech_<fmt> on raw host arrays (lis_matvec.c) */
 int     lisi_host_threads(void);      /* threads the host-side conversions may use: affinity mask capped by the cgroup CPU quota, at most 32 */
 /* ---- split form (lis_split.c) */
 void    lisi_sortr_ii(LIS_INT lo, LIS_INT hi, LIS_INT *key, LIS_INT *tag);    /* the reference's descending quicksort (lis_convert.c) */

@@ -10,15 +10,15 @@
 #include <stdio.h>
 #include "lis_internal.h"
 
+/* the six storage formats whose products (and timing sweep) this library serves */
+int lisi_format_served(LIS_INT type)
+{
+	return type == LIS_MATRIX_CSR || type == LIS_MATRIX_CSC || type == LIS_MATRIX_DIA || type == LIS_MATRIX_ELL || type == LIS_MATRIX_JAD || type == LIS_MATRIX_BSR;
+}
+
 LIS_INT lis_matvec(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 {
-	switch (A->matrix_type) {
-	case LIS_MATRIX_CSR: case LIS_MATRIX_CSC: case LIS_MATRIX_ELL:
-	case LIS_MATRIX_DIA: case LIS_MATRIX_JAD: case LIS_MATRIX_BSR:
-		break;
-	default:
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
-	}
+	if (!lisi_format_served(A->matrix_type)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	LISCHK(lisd_mat_ready(A));
 	/* like the reference (LIS_MATVEC_REALLOC, include/lis_matvec.h:32-43: lis_realloc of X->value to np + pad entries), X grows to hold the ghost and block
 	 * padding entries of A -- the host array too: a program that reads X->value[n ..) after a product in a multi-rank job must find memory there.  The new
@@ -44,32 +44,36 @@ LIS_INT lis_matvec(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 	return lisd_vec_done(Y);
 }
 
-static void raw_matvec(LIS_MATRIX A, LIS_INT fmt, LIS_SCALAR x[], LIS_SCALAR y[])
+/* lis_matvec_<fmt> / lis_matvech_<fmt>(A, x[], y[]) on raw HOST arrays through scratch vectors in HBM.  The forward product copies in np entries of x
+ * (a multi-rank job: the n owned ones, the halo brings the rest) and copies out n rows; the transposed one copies in n and copies out as many as the forward one reads.
+ * They cannot report errors (void), so a failing device call aborts loudly. */
+void lisi_raw_product(LIS_MATRIX A, LIS_INT fmt, LIS_SCALAR x[], LIS_SCALAR y[], int transposed)
 {
 	lisd_mat *d = MDEV(A);
-	LIS_INT err = (A->matrix_type == fmt) ? lisd_mat_ready(A) : LIS_ERR_ILL_ARG;
-	const size_t nx = (size_t)A->np + (size_t)A->pad + 16 + (fmt == LIS_MATRIX_BSR ? (size_t)A->nc * A->bnc : 0);
+	LIS_INT err = (A->matrix_type != fmt) ? LIS_ERR_ILL_ARG : transposed ? lisd_mat_ready_t(A) : lisd_mat_ready(A);
+	const size_t nx = (size_t)A->np + (size_t)A->pad + 16 + (!transposed && fmt == LIS_MATRIX_BSR ? (size_t)A->nc * A->bnc : 0);
+	const size_t cols = (size_t)(lisg.nprocs > 1 ? A->n : A->np), n_in = transposed ? (size_t)A->n : cols, n_out = transposed ? cols : (size_t)A->n;
 	if (!err && d->scap < nx) {
 		(void)liship_free(d->sx); (void)liship_free(d->sy);
 		d->sx = d->sy = NULL; d->scap = 0;
 		if (lisd_malloc((void **)&d->sx, nx * sizeof(double)) || lisd_malloc((void **)&d->sy, nx * sizeof(double))) err = LIS_ERR_OUT_OF_MEMORY;
 		else { d->scap = nx; (void)liship_memset(d->sx, 0, nx * sizeof(double), lisg.stream); }
 	}
-	if (!err) { int rc = liship_memcpy_h2d(d->sx, x, sizeof(double) * (size_t)(lisg.nprocs > 1 ? A->n : A->np), lisg.stream); if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
-	if (!err) err = lisd_spmv(A, d->sx, d->sy);
-	if (!err) { int rc = liship_memcpy_d2h(y, d->sy, sizeof(double) * (size_t)A->n, lisg.stream); if (!rc) rc = liship_stream_synchronize(lisg.stream); if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
+	if (!err) { int rc = liship_memcpy_h2d(d->sx, x, sizeof(double) * n_in, lisg.stream); if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
+	if (!err) err = transposed ? lisd_spmv_t(A, d->sx, d->sy) : lisd_spmv(A, d->sx, d->sy);
+	if (!err) { int rc = liship_memcpy_d2h(y, d->sy, sizeof(double) * n_out, lisg.stream); if (!rc) rc = liship_stream_synchronize(lisg.stream); if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
 	if (err) {
-		fprintf(stderr, "liblis_amd: lis_matvec_<fmt>(A, x[], y[]) failed (code %d) and has no error channel -- aborting\n", (int)err);
+		fprintf(stderr, "liblis_amd: lis_matvec%s_<fmt>(A, x[], y[]) failed (code %d) and has no error channel -- aborting\n", transposed ? "h" : "", (int)err);
 		abort();
 	}
 }
 
-void lis_matvec_csr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvec(A, LIS_MATRIX_CSR, x, y); }
-void lis_matvec_csc(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvec(A, LIS_MATRIX_CSC, x, y); }
-void lis_matvec_ell(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvec(A, LIS_MATRIX_ELL, x, y); }
-void lis_matvec_dia(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvec(A, LIS_MATRIX_DIA, x, y); }
-void lis_matvec_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvec(A, LIS_MATRIX_JAD, x, y); }
-void lis_matvec_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvec(A, LIS_MATRIX_BSR, x, y); }
+void lis_matvec_csr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_CSR, x, y, 0); }
+void lis_matvec_csc(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_CSC, x, y, 0); }
+void lis_matvec_ell(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_ELL, x, y, 0); }
+void lis_matvec_dia(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_DIA, x, y, 0); }
+void lis_matvec_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_JAD, x, y, 0); }
+void lis_matvec_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_BSR, x, y, 0); }
 
 /* ref src/matvec/lis_matvec.c:50-51 */
 LIS_MATVEC_FUNC LIS_MATVEC  = lis_matvec;
@@ -95,8 +99,7 @@ LIS_INT lis_matvec_optimize(LIS_MATRIX A, LIS_INT *matrix_type_maxperf)
 		printf("number of iterations = 1e7 / %d + 1 = %d\n", (int)A->nnz, (int)iter);
 	}
 	for (LIS_INT type = 1; type < 11 && !err; type++) {
-		const int served = type == LIS_MATRIX_CSR || type == LIS_MATRIX_CSC || type == LIS_MATRIX_DIA || type == LIS_MATRIX_ELL || type == LIS_MATRIX_JAD || type == LIS_MATRIX_BSR;
-		if (!served) {
+		if (!lisi_format_served(type)) {
 			if (lisg.rank == 0) printf("matrix_type = %2d (%s), not served by liblis_amd\n", (int)type, name[type - 1]);
 			continue;
 		}

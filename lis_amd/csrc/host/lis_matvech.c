@@ -245,20 +245,9 @@ LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy)
 	return LIS_SUCCESS;
 }
 
-static LIS_INT served(LIS_MATRIX A)
-{
-	switch (A->matrix_type) {
-	case LIS_MATRIX_CSR: case LIS_MATRIX_CSC: case LIS_MATRIX_ELL:
-	case LIS_MATRIX_DIA: case LIS_MATRIX_JAD: case LIS_MATRIX_BSR:
-		return LIS_SUCCESS;
-	default:
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
-	}
-}
-
 LIS_INT lis_matvech(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 {	/* ref src/matvec/lis_matvec.c:191-349; Y grows to np+pad like LIS_MATVEC_REDUCE0 (lis_matvec.h:60-72) */
-	LISCHK(served(A));
+	if (!lisi_format_served(A->matrix_type)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	LISCHK(lisd_mat_ready_t(A));
 	if (A->np + A->pad > Y->np + Y->pad) { Y->np = A->np; Y->pad = A->pad; }
 	double *dx, *dy;
@@ -270,30 +259,10 @@ LIS_INT lis_matvech(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 	return lisd_vec_done(Y);
 }
 
-/* raw HOST arrays, ref include/lis_matvec.h:92-178; void: a failing device call aborts loudly */
-static void raw_matvech(LIS_MATRIX A, LIS_INT fmt, LIS_SCALAR x[], LIS_SCALAR y[])
-{
-	lisd_mat *d = MDEV(A);
-	LIS_INT err = (A->matrix_type == fmt) ? lisd_mat_ready_t(A) : LIS_ERR_ILL_ARG;
-	const size_t nx = (size_t)A->np + (size_t)A->pad + 16;
-	if (!err && d->scap < nx) {
-		(void)liship_free(d->sx); (void)liship_free(d->sy);
-		d->sx = d->sy = NULL; d->scap = 0;
-		if (lisd_malloc((void **)&d->sx, nx * sizeof(double)) || lisd_malloc((void **)&d->sy, nx * sizeof(double))) err = LIS_ERR_OUT_OF_MEMORY;
-		else { d->scap = nx; (void)liship_memset(d->sx, 0, nx * sizeof(double), lisg.stream); }
-	}
-	if (!err) { int rc__ = liship_memcpy_h2d(d->sx, x, sizeof(double) * (size_t)A->n, lisg.stream); if (rc__) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc__); }
-	if (!err) err = lisd_spmv_t(A, d->sx, d->sy);
-	if (!err) { int rc__ = liship_memcpy_d2h(y, d->sy, sizeof(double) * (size_t)(lisg.nprocs > 1 ? A->n : A->np), lisg.stream); if (!rc__) rc__ = liship_stream_synchronize(lisg.stream); if (rc__) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc__); }
-	if (err) {
-		fprintf(stderr, "liblis_amd: lis_matvech_<fmt>(A, x[], y[]) failed (code %d) and has no error channel -- aborting\n", (int)err);
-		abort();
-	}
-}
-
-void lis_matvech_csr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvech(A, LIS_MATRIX_CSR, x, y); }
-void lis_matvech_csc(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvech(A, LIS_MATRIX_CSC, x, y); }
-void lis_matvech_ell(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvech(A, LIS_MATRIX_ELL, x, y); }
-void lis_matvech_dia(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvech(A, LIS_MATRIX_DIA, x, y); }
-void lis_matvech_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvech(A, LIS_MATRIX_JAD, x, y); }
-void lis_matvech_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { raw_matvech(A, LIS_MATRIX_BSR, x, y); }
+/* raw HOST arrays, ref include/lis_matvec.h:92-178; void: a failing device call aborts loudly (lis_matvec.c) */
+void lis_matvech_csr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_CSR, x, y, 1); }
+void lis_matvech_csc(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_CSC, x, y, 1); }
+void lis_matvech_ell(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_ELL, x, y, 1); }
+void lis_matvech_dia(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_DIA, x, y, 1); }
+void lis_matvech_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_JAD, x, y, 1); }
+void lis_matvech_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_BSR, x, y, 1); }

@@ -336,6 +336,17 @@ def device_checks(lib, name, A, ptr, idx, val, xg, yg, is_, ie, gn):
             assert lib.lis_vector_get_values(vy2, is_, n, y.ctypes.data_as(capi.P_DBL)) == 0
             assert np.array_equal(y, y_overlapped), (name, fmt, "overlap")
         lib.lis_vector_destroy(vb2); lib.lis_vector_destroy(vy2); lib.lis_matrix_destroy(B)
+    if name == "block_diagonal":
+        # a SPLIT JAD matrix on ranks without ghost columns: its HBM copy is two CSR halves and a diagonal with no row-range form, so it must not take the
+        # CSR branch that runs the interior rows under the halo (that returned L x alone).  One term per row: the bits of the single-process product
+        B = lisdrv.convert(lib, A, "jad")
+        assert lib.lis_matrix_split(B) == 0 and B.contents.is_splited and B.contents.np == B.contents.n
+        vb2, vy2 = lisdrv.new_vector(lib, B, None), lisdrv.new_vector(lib, B, None)
+        assert lib.lis_vector_set_values2(capi.LIS_INS_VALUE, is_, n, np.ascontiguousarray(xg[is_:ie]).ctypes.data_as(capi.P_DBL), vb2) == 0
+        assert lib.lis_matvec(B, vb2, vy2) == 0, (name, "split jad")
+        assert lib.lis_vector_get_values(vy2, is_, n, y.ctypes.data_as(capi.P_DBL)) == 0
+        assert np.array_equal(y, yg[is_:ie]), (name, "split jad", y[:4], yg[is_:is_ + 4])
+        lib.lis_vector_destroy(vb2); lib.lis_vector_destroy(vy2); lib.lis_matrix_destroy(B)
     if name.startswith("poisson"):
         bg = orc.spmv_csr(ptr, idx, val, np.ones(gn))
         vb, vs = lisdrv.new_vector(lib, A, None), lisdrv.new_vector(lib, A, None)
