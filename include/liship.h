@@ -534,7 +534,7 @@ int  liship_csr_transpose_f64(int nrows, int ncols, int nnz, const int *ptr, con
  * offsets that occur (used: n + ncols ints; slot: n + ncols + 1; scratch: (n + ncols) / 4096 + 4 long long) and returns their number,
  * liship_csr_to_dia writes them ascending and value[d * n + i].  BSR: distinct block columns of a block row in first-seen order, blocks
  * column-major; liship_csr_bsr_count gives bptr and the block count (-1: a block row with more than 96 distinct blocks; count: nr + 1
- * ints, scratch: nr / 4096 + 4 long long).  The *_rows forms build the CSR row form of an ELL / DIA matrix (lis_device.c): the terms of
+ * ints, scratch: nr / 4096 + 4 long long).  The *_rows forms build the CSR row form of an ELL / DIA matrix (lis_upload.c, lis_convert_hbm.c): the terms of
  * a row in the format's own order, padding and explicit zeros included. */
 int  liship_csr_row_facts(int n, const int *ptr, const int *index, int *facts, void *stream);
 int  liship_csr_to_ell(int n, int maxnzr, const int *ptr, const int *index, const double *value, int *ell_index, double *ell_value, void *stream);

@@ -497,7 +497,7 @@ static LIS_INT convert_impl(LIS_MATRIX Ain, LIS_MATRIX Aout)
 	LISCHK(lis_matrix_merge(Ain));         /* ref lis_matrix_ops.c:142: a split input is merged first */
 	if (Ain->matrix_type == want && !Ain->is_block) { LISCHK(lisp_fill_matrix(Ain)); return lisi_matrix_deep_copy(Ain, Aout); }
 	if (Ain->matrix_type == LIS_MATRIX_CSR) {
-		int done = 0;                          /* in HBM when Ain lives there (lis_device.c), else on the host arrays */
+		int done = 0;                          /* in HBM when Ain lives there (lis_convert_hbm.c), else on the host arrays */
 		LISCHK(lisd_convert_csr(Ain, Aout, &done));
 		if (done) return LIS_SUCCESS;
 		LISCHK(lisp_fill_matrix(Ain));

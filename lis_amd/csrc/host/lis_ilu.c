@@ -26,7 +26,7 @@
  * with a block where the point form has a number: the symbolic step runs unchanged on (nr, bptr, bindex) with the T row blocks of
  * LIS_GET_ISIE over the nr block rows, the schedule and the L and U layouts come from the same builders (a place holds bn*bn doubles,
  * filled by the block gather), d holds the INVERTED diagonal blocks.  The factorisation reads A's blocks in native layout: the HBM
- * copy's own arrays, or -- when the copy is held in its row form (lis_device.c try_bsr_row_form) -- a native upload kept on the entry,
+ * copy's own arrays, or -- when the copy is held in its row form (lis_upload.c lisd_try_bsr_row_form) -- a native upload kept on the entry,
  * which dies with the copy like everything else here.  psolve only: the reference's OpenMP build applies M^-1 where M^-H is meant
  * (:2098-2165 is a copy of psolve), which this library neither reproduces nor replaces, so solvers that need M^-H are refused.
  */

@@ -237,9 +237,7 @@ LIS_INT lisd_vec_done(LIS_VECTOR v);                          /* after a kernel 
 LIS_INT lisd_vec_reserve(LIS_VECTOR v, size_t doubles);       /* grow the HBM buffer (keeps data) */
 LIS_INT lisd_vec_to_host(LIS_VECTOR v);
 void    lisd_vec_free(LIS_VECTOR v);
-LIS_INT lisd_mat_ready(LIS_MATRIX A);
-void    lisd_mat_free(LIS_MATRIX A);
-LIS_INT lisd_init_quiet(void);                               /* lisd_init without the diagnostic when no device exists */
+LIS_INT lisd_init_quiet(void);                              /* lisd_init without the diagnostic when no device exists */
 void    lisd_mat_eager(LIS_MATRIX A);                         /* resident mode: upload at assemble / convert time */
 LIS_INT lisd_pool_get(size_t bytes, void **out);              /* HBM buffer of exactly `bytes`, reused across solves */
 void    lisd_pool_put(void *p, size_t bytes);
@@ -248,9 +246,6 @@ int     lis_amd_trim_count(void);                             /* lis_amd_trim(),
 LIS_INT lisd_mat_ready_t(LIS_MATRIX A);                       /* build / upload the transposed operator */
 LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy);    /* y[0..np) = A^T x, ghost rows reduced to owners */
 LIS_INT lisd_spmv(LIS_MATRIX A, double *dx, double *dy);      /* y = A x on device pointers (halo included); lis_product.c, like the two fused forms below */
-LIS_INT lisd_csr_plan(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);   /* row split + index codes */
-LIS_INT lisd_csr_plan_cols(liship_csr_plan_t *plan, int n, int ncols, const int *dptr, const int *dindex, const double *dvalue);   /* ... of a rank's local rows with ghost columns [n, ncols) */
-LIS_INT lisd_csr_plan_plain(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);    /* the same without a renumbered form (matrices no solve iterates on) */
 LIS_INT lisd_spmv_dot_launch(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq); /* sums -> reduce_out */
 LIS_INT lisd_spmv_dot_launch_to(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq, double *result); /* sums -> result (HBM) */
 LIS_INT lisd_fetch(int count, double *out);                   /* reduce_out[0..count) -> host, cross-rank fold */
@@ -258,6 +253,21 @@ LIS_INT lisd_dot(int n, const double *dx, const double *dy, double *out);
 LIS_INT lisd_nrm2(int n, const double *dx, double *out);
 LIS_INT lisd_nrm1(int n, const double *dx, double *out);
 LIS_INT lisd_dot2(int n, const double *dx, const double *dy, double *out2);
+/* ---- the HBM copy of a matrix (lis_upload.c) and what the conversion in HBM (lis_convert_hbm.c) decides with the same code */
+LIS_INT lisd_mat_ready(LIS_MATRIX A);
+void    lisd_mat_free(LIS_MATRIX A);
+LIS_INT lisd_upload_i(int **dst, const int *src, size_t count);               /* a fresh HBM array holding src[0 .. count), queued on the library's stream */
+LIS_INT lisd_upload_d(double **dst, const double *src, size_t count);         /* (src NULL: room only) */
+LIS_INT lisd_csr_plan(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);   /* row split + index codes */
+LIS_INT lisd_csr_plan_cols(liship_csr_plan_t *plan, int n, int ncols, const int *dptr, const int *dindex, const double *dvalue);   /* ... of a rank's local rows with ghost columns [n, ncols) */
+LIS_INT lisd_csr_plan_plain(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);    /* the same without a renumbered form (matrices no solve iterates on) */
+void    lisd_renum_cache_drop(void);                                          /* lis_amd_trim: the renumbering hint goes with the pool */
+int     lisd_few_distinct_values(const double *v, size_t count);              /* the screen in front of a row-form attempt */
+int     lisd_row_form_wanted(long long width, int n);                         /* the switches, 1 <= width <= 32, n * width < 2^31 */
+LIS_INT lisd_row_form_adopt(lisd_mat *d, int n, int *rptr, int *ridx, double *rval, LIS_INT nnz, int *taken);   /* takes the three HBM arrays: kept in d with their plan, or freed */
+LIS_INT lisd_try_bsr_row_form(int n, int np, int bnr, int bnc, int splited, lisd_mat *d, const int *dbptr, const int *dbindex, const double *dbvalue, LIS_INT bnnz, int values_few, int *taken);
+LIS_INT lisd_ell_index_codes(lisd_mat *d);                                    /* native ELL: one-byte column codes; out of memory keeps the 4 B indices */
+void    lisd_fmt_find_plane(lisd_mat *d, const int *host_dia_offsets);        /* native ELL / DIA: d->xs_rows */
 
 /* ---- communicator (lis_comm.c) */
 LIS_INT lisi_matrix_retype(LIS_MATRIX A, LIS_INT want, LIS_INT block);       /* convert an assembled matrix in place (lis_io.c) */
@@ -301,9 +311,7 @@ enum { SW_L, SW_U, SW_UT, SW_LT, SW_COUNT };   /* the four sweeps of a precondit
 enum { LISI_TERMS_ROWS, LISI_TERMS_T_ASC, LISI_TERMS_T_DESC };               /* lisi_sweep_terms: the rows as stored; transposed, by source row ascending / descending */
 #define SW_TERMS(w) ((w) == SW_UT ? LISI_TERMS_T_ASC : (w) == SW_LT ? LISI_TERMS_T_DESC : LISI_TERMS_ROWS)
 #define SW_DESC(w)  ((w) == SW_U || (w) == SW_LT)                            /* the sweep runs from the last row to the first */
-LIS_INT lisd_upload_i(int **dst, const int *src, size_t count);               /* a fresh HBM array holding src[0 .. count), queued on the library's stream */
-LIS_INT lisd_upload_d(double **dst, const double *src, size_t count);         /* (src NULL: room only) */
-int     lisi_sweep_blocks(void);                                             /* row blocks of the solves: 1, or the reference-order mode's T */
+int     lisi_sweep_blocks(void);                                            /* row blocks of the solves: 1, or the reference-order mode's T */
 int    *lisi_block_of(int n, int T);                                         /* block of every row among T blocks of LIS_GET_ISIE (caller frees) */
 LIS_INT lisi_sweep_terms(int n, const int *ptr, const int *idx, const int *blk, int order, int **tp, int **tc, int **tid);   /* the terms of a sweep, row by row; tid: their places in idx */
 LIS_INT lisi_sweep_build(lisi_sweep_t *s, int n, const int *tp, const int *tc, const double *tv, int desc, const int *weight, int **src_out);
@@ -341,8 +349,8 @@ void    lisi_sort_row(LIS_INT lo, LIS_INT hi, LIS_INT *idx, LIS_SCALAR *val);
 LIS_INT lisi_convert_csr_to(LIS_MATRIX Ain, LIS_MATRIX Aout);  /* Aout->matrix_type selects the target */
 LIS_INT lisi_convert_to_csr(LIS_MATRIX Ain, LIS_MATRIX Aout);
 LIS_INT lisi_jad_order(LIS_MATRIX A, LIS_INT *maxnzr, LIS_INT **perm, LIS_INT **ptr);      /* the reference's length-sorted row order + jagged-diagonal starts */
-LIS_INT lisd_convert_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done);   /* csr -> ell / dia / csc / bsr in HBM when Ain lives there (lis_device.c) */
-LIS_INT lisd_csr_home(LIS_MATRIX Ain, LIS_MATRIX *home);               /* a host copy of a CSR matrix born in HBM, for the conversions the host routines serve (lis_device.c) */
+LIS_INT lisd_convert_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done);   /* csr -> ell / dia / csc / jad / bsr in HBM when Ain lives there (lis_convert_hbm.c) */
+LIS_INT lisd_csr_home(LIS_MATRIX Ain, LIS_MATRIX *home);               /* a host copy of a CSR matrix born in HBM, for the conversions the host routines serve (lis_convert_hbm.c) */
 LIS_INT lisi_matrix_deep_copy(LIS_MATRIX Ain, LIS_MATRIX Aout);
 
 /* args (lis_initialize / lis_solver_set_option share the tokenizer) */

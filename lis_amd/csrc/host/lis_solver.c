@@ -1049,7 +1049,7 @@ static LIS_INT renumber_enter(LIS_MATRIX A, renumber_t *st)
 	 * transposed copy of the swapped-in arrays has the np local columns as its rows like any rank's A^T, and the reverse halo adds the neighbours' sums at the
 	 * renumbered export rows: lisd_spmv_t / lisc_reduce_device read the same swapped tables) */
 	const int multi = lisg.nprocs > 1 && A->commtable;
-	LISCHK(lisd_mat_lazy_reorder(A));          /* the renumbered form is built LAZILY: by the first solve that finds the plan has served lisg.reorder_after products (lis_device.c) */
+	LISCHK(lisd_mat_lazy_reorder(A));          /* the renumbered form is built LAZILY: by the first solve that finds the plan has served lisg.reorder_after products (lis_upload.c) */
 	if (!(dm->type == LIS_MATRIX_CSR && !dm->split_jad && dm->plan && (A->np == A->n || (multi && A->matrix_type == LIS_MATRIX_CSR)) && dm->n == A->n &&
 	      liship_csr_plan_reordered_form(dm->plan, &in, &rp, &ri, &rv, &st->perm) == 0)) return LIS_SUCCESS;
 	if (multi) LISCHK(lisc_halo_renumbered(A, st->perm, liship_csr_plan_reordered_inner_rows(dm->plan)));

@@ -14,7 +14,7 @@
  * One deliberate difference: the reference mallocs D->value and writes only the rows that HAVE a diagonal entry; here the
  * array starts zeroed, so a missing diagonal is 0 instead of heap contents.
  *
- * The HBM copy of a split matrix is built by lis_device.c from lisi_split_rows(): every row as ONE chain of terms in the
+ * The HBM copy of a split matrix is built by lis_upload.c from lisi_split_rows(): every row as ONE chain of terms in the
  * order the reference adds them, which the CSR kernels sum from -0.0 ("the first product initialises the sum").
  */
 #include "lis_internal.h"
@@ -317,7 +317,7 @@ LIS_INT lis_matrix_merge(LIS_MATRIX A)
  *        then the U blocks, each column by column; blocks larger than 4 take the generic routine (:70-118), which starts
  *        the sums at +0.0 instead of at the first product (*from_zero)
  * JAD is not a chain: lis_matvec_jad.c:60-140 forms (D x + sum of L) + sum of U with both partial sums started at 0 --
- * lis_device.c multiplies by L and by U separately and combines.
+ * lis_product.c multiplies by L and by U separately and combines.
  * Returns CSR arrays over `*rows` rows (BSR: nr*bnr, padding rows included); the caller frees them. */
 LIS_INT lisi_split_rows(LIS_MATRIX A, LIS_INT *rows, LIS_INT **optr, LIS_INT **oidx, LIS_SCALAR **oval, int *from_zero)
 {

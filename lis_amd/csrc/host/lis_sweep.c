@@ -10,20 +10,6 @@
 #include <stdio.h>
 #include "lis_krylov.h"
 
-
-LIS_INT lisd_upload_i(int **dst, const int *src, size_t count)
-{
-	HIPCHK(lisd_malloc((void **)dst, (count + 4) * sizeof(int)));
-	if (count) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(int), lisg.stream));
-	return LIS_SUCCESS;
-}
-LIS_INT lisd_upload_d(double **dst, const double *src, size_t count)
-{
-	HIPCHK(lisd_malloc((void **)dst, (count + 2) * sizeof(double)));
-	if (count && src) HIPCHK(liship_memcpy_h2d(*dst, src, count * sizeof(double), lisg.stream));
-	return LIS_SUCCESS;
-}
-
 int lisi_sweep_blocks(void) { return lisg.ref_reductions > 0 ? lisg.ref_reductions : 1; }
 
 /* block of row i among T blocks of LIS_GET_ISIE (ref include/lis.h:1067): the first n % T blocks hold n / T + 1 rows */

@@ -109,7 +109,7 @@ void csr_to_ell(int n, int maxnzr, const int *__restrict__ ptr, const int *__res
         eval[(size_t)j * n + i] = have ? val[s + j] : 0.0;
     }
 }
-// the row form of the same matrix (lis_device.c try_row_form): CSR rows of exactly maxnzr terms, padding included
+// the row form of the same matrix (lis_upload.c try_row_form, lis_convert_hbm.c): CSR rows of exactly maxnzr terms, padding included
 __global__ __launch_bounds__(BLOCK)
 void csr_to_ell_rows(int n, int maxnzr, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ val,
                      int *__restrict__ rptr, int *__restrict__ ridx, double *__restrict__ rval)

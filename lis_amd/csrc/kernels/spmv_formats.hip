@@ -747,7 +747,7 @@ extern "C" int liship_ell_scan_band(int n, int maxnzr, const int *idx, int *plan
 }
 
 // rows per plane of the structured grid the NEXT whole-matrix ELL / DIA launches work on (0: none -- natural workgroup order): the host layer sets it from the matrix
-// it is about to multiply (one driving thread per process, as the Lis API requires: lis_device.c)
+// it is about to multiply (one driving thread per process, as the Lis API requires: lis_product.c; the plane is found by lis_upload.c)
 extern "C" int liship_spmv_formats_set_plane(int rows) { g_fmt_plane_rows = rows > 0 ? rows : 0; return 0; }
 // what a whole-matrix launch of `grid` workgroups of `rows_per_wg` rows passes to its kernel for the plane set now: workgroups per plane, 0 when it runs in natural order
 extern "C" int liship_spmv_formats_plane_blocks(int rows_per_wg, int grid) { return rows_per_wg > 0 && grid > 0 ? fmt_plane(rows_per_wg, grid) : 0; }

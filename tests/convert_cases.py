@@ -1,13 +1,13 @@
 """Matrices for the conversion tests (tests/test_convert_cpu.py, tests/test_convert_gpu.py) and what they must turn into.
 
 Generators are deterministic and return (ptr, idx, val) as int32 / int32 / float64.  Each is built to reach one place in
-kernels/convert.hip or in lisd_convert_csr (host/lis_device.c) that a column-sorted stencil never reaches; where the case rests on a
+kernels/convert.hip or in lisd_convert_csr (host/lis_convert_hbm.c) that a column-sorted stencil never reaches; where the case rests on a
 fact about the matrix (the hub block row has exactly so many distinct blocks, `unsorted` really is unsorted), a helper below states
 the fact so that the tests can assert it.
 
 The expected arrays of the native layouts come from the plain-C oracle (oracle_arrays), which test_convert_cpu.py holds to the
 reference at these very shapes.  The ROW FORMS -- the CSR rows the library builds in HBM for constant-coefficient matrices -- have
-no oracle routine: ell_rows / dia_rows / bsr_rows restate them from the comments in convert.hip and lis_device.c, and
+no oracle routine: ell_rows / dia_rows / bsr_rows restate them from the comments in convert.hip and lis_upload.c, and
 test_convert_cpu.py holds them to orc.spmv_ell / spmv_dia / spmv_bsr of the native arrays."""
 import numpy as np
 

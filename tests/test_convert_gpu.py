@@ -1,4 +1,4 @@
-"""kernels/convert.hip and lisd_convert_csr (host/lis_device.c), entry by entry and through lis_matrix_convert, on the matrices of
+"""kernels/convert.hip and lisd_convert_csr (host/lis_convert_hbm.c), entry by entry and through lis_matrix_convert, on the matrices of
 tests/convert_cases.py: rows out of order and with repeated columns, block rows of exactly 96 and 97 distinct blocks, non-square
 blocks and every kind of padding, empty rows, one-row matrices, the borders of the scan (the 1026-tile one included), -0.0 / NaN /
 inf / subnormal values, the row forms of constant-coefficient matrices, matrices born in HBM.
@@ -409,3 +409,26 @@ def test_row_forms_of_constant_matrices(lib, case, fmt, bnr, bnc):
     B = _convert_checked(lib, A, csr, fmt, bnr, bnc, "device")
     assert lib.dll.lis_amd_matrix_value_records(B) == records
     lib.lis_matrix_destroy(B); lib.lis_matrix_destroy(A)
+
+
+@pytest.mark.parametrize("fmt,bnr,bnc", [("ell", 0, 0), ("dia", 0, 0), ("bsr", 2, 2)], ids=["ell", "dia", "bsr2x2"])
+@pytest.mark.parametrize("case", ["constant_p3d", "scan_4096"])
+def test_both_paths_decide_alike(lib, case, fmt, bnr, bnc):
+    """the conversion in HBM and the host routine followed by the upload (LIS_AMD_NO_DEVICE_CONVERT) give the new matrix the same HBM copy: the same kernel
+    family, the same value records, the same bits in the product -- constant coefficients (the row form) and values that all differ (the native arrays)"""
+    csr = csr_of(case)
+    x = _x(len(csr[0]) - 1, 7)
+    A = _resident(lib, csr)
+    B = lisdrv.convert(lib, A, fmt, bnr or 2, bnc or 2)
+    assert lib.dll.lis_amd_matrix_lazy_arrays(B) == DEVICE[fmt]
+    lib.dll.lis_amd_set_device_convert(0)
+    try:
+        H = lisdrv.convert(lib, A, fmt, bnr or 2, bnc or 2)
+    finally:
+        lib.dll.lis_amd_set_device_convert(1)
+    assert lib.dll.lis_amd_matrix_lazy_arrays(H) == HOST
+    decided = [(lib.dll.lis_amd_matrix_device_type(M), lib.dll.lis_amd_matrix_value_records(M)) for M in (B, H)]
+    assert decided[0] == decided[1], decided
+    assert decided[0][0] == (capi.LIS_MATRIX_CSR if case == "constant_p3d" else getattr(capi, "LIS_MATRIX_" + fmt.upper()))
+    assert cc.same_bits(lisdrv.matvec(lib, B, x), lisdrv.matvec(lib, H, x))
+    lib.lis_matrix_destroy(B); lib.lis_matrix_destroy(H); lib.lis_matrix_destroy(A)
