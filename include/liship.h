@@ -199,6 +199,13 @@ int  liship_csr_plan_reorder(liship_csr_plan_t plan, const int *ptr, const int *
  * liship_csr_plan_reorder_permutation: the permutation of the reordered form to the host (LISHIP_ERR_ARG when the plan has none). */
 int  liship_csr_plan_reorder_with(liship_csr_plan_t plan, const int *ptr, const int *index, const double *value, int min_items_per_listed, const int *perm_hint, void *stream);
 int  liship_csr_plan_reorder_permutation(liship_csr_plan_t plan, int *perm_host);
+/* The numbering alone, for tests and tools: what liship_csr_plan_reorder would find for the device arrays ptr / index (n rows; columns [n, ncols) are ghost columns,
+ * ncols <= n: none) with `landmarks` landmarks (clamped to 3..6), WITHOUT its size gate and its keep rule -- no plan, no P A P^T.  order_host[new position] = row
+ * (HOST, n entries); *inner_rows_host = rows that have a component and read no ghost column (n - loose rows when there are no ghost columns).  *found = 0 and 0 returned: the
+ * ordering declined (the graph is too deep for its level budget) and the outputs are not to be read; a HIP code: a runtime error; LISHIP_ERR_ARG: a null pointer
+ * with n > 0 (or found itself); n = 0 is fine.  The numbering is a function of its inputs alone (distances, ties to the smallest index, a stable sort):
+ * tests/order_model.py predicts it index by index. */
+int  liship_csr_order(int n, int ncols, const int *ptr, const int *index, int landmarks, int *order_host, int *inner_rows_host, int *found, void *stream);
 /* A rank's local matrix of a multi-rank job (columns [n, ncols) are ghost columns, lis_matrix_mpi.c:274-306): said before liship_csr_plan_reorder, the numbering is found on
  * the owned columns alone, ghost columns keep their numbers in P A P^T and the rows that read one are placed behind all the others --
  * rows [0, liship_csr_plan_reordered_inner_rows) of the reordered form touch no ghost column (they can run while the halo travels). */

@@ -112,6 +112,7 @@ _LISHIP = {
     "liship_csr_plan_reordered": (C.c_longlong, [_vp]),
     "liship_csr_plan_reorder_with": (_ci, [_vp, _vp, _vp, _vp, _ci, _vp, _vp]),
     "liship_csr_plan_reorder_permutation": (_ci, [_vp, _vp]),
+    "liship_csr_order": (_ci, [_ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "liship_spmv_csr_set_reorder": (_ci, [_ci]),
     "liship_csr_plan_reordered_form": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_csr_plan_set_ghost_columns": (_ci, [_vp, _ci]),

@@ -23,6 +23,8 @@ namespace order_dev {
 constexpr int MAX_COMP = 8, MAX_LEVEL = (1 << 15) - 1, LEVEL_BATCH = 32, SORT_TILE = 2048, MAX_FIELDS = 6;
 struct Fields { const int *l[MAX_FIELDS]; };      // the landmark distance fields, by value into the kernels
 constexpr int LEVEL_BUDGET = 16384;     // levels over ALL searches of one ordering: a graph of huge diameter (a chain) is not worth ~10 us per level -- no candidate then
+// (MAX_LEVEL cannot be reached: a search pays LEVEL_BATCH levels of the budget per batch, so the budget -- half of MAX_LEVEL -- ends every search first; bfs()'s
+//  `return MAX_LEVEL` is dead code that keeps the loop bounded on its own terms.  tests/order_model.py states the budget as 512 batches.)
 
 // one level of a top-down breadth-first search: every vertex of level `cur` gives its unvisited neighbours level cur + 1
 __global__ void bfs_level(int n, const int *__restrict__ ptr, const int *__restrict__ idx, int *__restrict__ level, int cur, int *__restrict__ grew)

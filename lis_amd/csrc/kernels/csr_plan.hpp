@@ -1858,6 +1858,24 @@ extern "C" int liship_csr_plan_reorder_permutation(liship_csr_plan_t p, int *out
     HIP_TRY(hipMemcpy(out_host, p->r_perm, sizeof(int) * (size_t)p->n, hipMemcpyDeviceToHost));
     return 0;
 }
+// The numbering alone, for tests and tools: order_dev::device_order on device arrays, without the size gate and the keep rule of reorder_impl.  *found = 0 (and 0
+// returned): the ordering declined (a graph too deep for its level budget); a HIP code: a runtime error.
+extern "C" int liship_csr_order(int n, int ncols, const int *ptr, const int *idx, int landmarks, int *order_host, int *inner_rows_host, int *found, void *stream)
+{
+    if (n < 0 || !found || (n > 0 && (!ptr || !idx || !order_host || !inner_rows_host))) return LISHIP_ERR_ARG;
+    *found = 0;
+    if (inner_rows_host) *inner_rows_host = 0;
+    (void)hipGetLastError();
+    const bool ok = order_dev::device_order(n, ncols > n ? ncols : n, ptr, idx, landmarks, order_host, inner_rows_host, as_stream(stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (!ok) {                                                     // declined, or a runtime error the calls have reported and cleared: the device says which
+        const hipError_t s = hipStreamSynchronize(as_stream(stream));
+        if (s != hipSuccess) return (int)s;
+    }
+    *found = ok ? 1 : 0;
+    return 0;
+}
 static int reorder_impl(liship_csr_plan_t p, const int *ptr, const int *idx, const double *val, int min_items_per_listed, const int *hint, void *stream)
 {
     if (!p || (p->n > 0 && (!ptr || !idx || !val))) return LISHIP_ERR_ARG;

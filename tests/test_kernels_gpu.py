@@ -12,6 +12,7 @@ import pytest
 
 import orc
 import lis_amd
+import order_model
 from lis_amd import DeviceArray as DA, check
 
 pytestmark = pytest.mark.gpu
@@ -818,6 +819,27 @@ def _scrambled_poisson(scramble, vary=True):
     return permute_csr(ptr, idx, val, np.random.default_rng(9).permutation(n)) if scramble else (ptr, idx, val)
 
 
+def _order_door(lib, n, ncols, dptr, didx, landmarks):
+    """liship_csr_order: the numbering alone, as the plan would find it"""
+    order, inner, found = np.full(n, -7, np.int32), C.c_int(-7), C.c_int(-7)
+    check(lib.liship_csr_order(n, ncols, dptr.ptr, didx.ptr, landmarks, order.ctypes.data, C.addressof(inner), C.addressof(found), None))
+    assert found.value == 1
+    return order, inner.value
+
+
+def _reordered_arrays(lib, plan, n):
+    """P A P^T as the plan keeps it in HBM: its plan, the device pointers, and ptr / index / value / perm on the host"""
+    inner, rp, ri, rv, pm = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    check(lib.liship_csr_plan_reordered_form(plan, C.byref(inner), C.byref(rp), C.byref(ri), C.byref(rv), C.byref(pm)))
+    hp, hperm = np.empty(n + 1, np.int32), np.empty(n, np.int32)
+    check(lib.liship_memcpy_d2h(hp.ctypes.data, rp, hp.nbytes, None)); check(lib.liship_memcpy_d2h(hperm.ctypes.data, pm, hperm.nbytes, None))
+    check(lib.liship_device_synchronize())
+    hi, hv = np.empty(hp[-1], np.int32), np.empty(hp[-1], np.float64)
+    check(lib.liship_memcpy_d2h(hi.ctypes.data, ri, hi.nbytes, None)); check(lib.liship_memcpy_d2h(hv.ctypes.data, rv, hv.nbytes, None))
+    check(lib.liship_device_synchronize())
+    return (inner, rp, ri, rv, pm), hp, hi, hv, hperm
+
+
 @pytest.mark.parametrize("kind", ["nodes", "rows", "two_meshes_and_loose_rows", "natural", "short_rows", "short_rows_natural"])
 def test_reordered_plan_bit_exact(lib, kind):
     """liship_csr_plan_reorder: a matrix numbered without locality is renumbered inside the plan (Cuthill-McKee, P A P^T in HBM); y keeps the oracle's bits
@@ -861,6 +883,20 @@ def test_reordered_plan_bit_exact(lib, kind):
         check(lib.liship_spmv_csr_f64(inner, rp, ri, rv, xp.ptr, yp.ptr, None))
         check(lib.liship_permute_scatter_f64(n, pm, yp.ptr, yb.ptr, None))
         assert np.array_equal(yb.to_host(), yref, equal_nan=True)
+        # WHICH permutation: the one liship_csr_order finds with the landmark count reorder_impl derives (six for 12 entries per row or more, else three), which is
+        # the one tests/order_model.py predicts, index by index -- the product's bits cannot tell a good numbering from a valid one
+        landmarks = 6 if len(idx) >= 12 * n else 3
+        perm = np.empty(n, np.int32)
+        check(lib.liship_csr_plan_reorder_permutation(plan, perm.ctypes.data))
+        assert np.array_equal(perm, _order_door(lib, n, n, dptr, didx, landmarks)[0])
+        model = order_model.order(n, n, ptr, idx, landmarks)
+        assert model.found and (model.components, model.loose) == ((2, 1200) if kind == "two_meshes_and_loose_rows" else (1, 0))
+        assert np.array_equal(perm, model.order)
+        # ... and P A P^T itself, array by array: csr_reorder_rows against permute_csr (81-entry rows: its 64-lane stride), values bit for bit
+        _, hp, hi, hv, hperm = _reordered_arrays(lib, plan, n)
+        ep, ei, ev = permute_csr(ptr, idx, val, perm)
+        assert np.array_equal(hperm, perm) and np.array_equal(hp, ep) and np.array_equal(hi, ei)
+        assert np.array_equal(hv.view(np.uint64), ev.view(np.uint64))
     ys = {}
     for on in (2, 0, 1, 2):                              # 2: whole-matrix products of long-row plans take the reordered form (opt-in); 1: the default, products in the caller's numbering
         lib.liship_spmv_csr_set_reorder(on)
@@ -926,6 +962,15 @@ def test_reordered_plan_bit_exact(lib, kind):
         check(lib.liship_memcpy_d2h(hi.ctypes.data, ri, hi.nbytes, None)); check(lib.liship_device_synchronize())
         assert np.array_equal(np.sort(hperm), np.arange(n)) and np.array_equal(has_ghost[hperm], np.arange(n) >= inner_rows)
         assert hi[:hp[inner_rows]].max() < n and np.array_equal(np.sort(hi[hi >= n]), np.sort(idx_g[idx_g >= n]))
+        # entry by entry: ghost columns keep their numbers where they stand, the others are renumbered; the permutation is the door's, inner_rows the model's
+        door, door_inner = _order_door(lib, n, n + 8, dptr, didx_g, 6)
+        assert np.array_equal(hperm, door) and inner_rows == door_inner == order_model.inner_rows(n, n + 8, ptr, idx_g)
+        ep, ei, src = permute_csr(ptr, np.where(idx_g >= n, 0, idx_g), np.arange(len(idx), dtype=np.float64), hperm)
+        src = src.astype(np.int64)
+        hv = np.empty(hp[-1], np.float64)
+        check(lib.liship_memcpy_d2h(hv.ctypes.data, rv, hv.nbytes, None)); check(lib.liship_device_synchronize())
+        assert np.array_equal(hp, ep) and np.array_equal(hi, np.where(idx_g[src] >= n, idx_g[src], ei))
+        assert np.array_equal(hv.view(np.uint64), val[src].view(np.uint64))
         xp, yp, yb = DA.from_host(np.zeros(n + 8), np.float64), DA.from_host(np.full(n, np.nan), np.float64), DA.from_host(np.full(n, np.nan), np.float64)
         dxg = DA.from_host(xg, np.float64)
         check(lib.liship_permute_gather_f64(n, pm, dxg.ptr, xp.ptr, None))
@@ -958,18 +1003,72 @@ def test_reordered_plan_bit_exact(lib, kind):
         val2 = val * rng.uniform(0.5, 1.5, len(val))
         dval2 = DA.from_host(val2, np.float64)
         yref2 = orc.spmv_csr(ptr, idx, val2, x)
-        for hint in (perm, np.zeros(n, np.int32), np.arange(n, dtype=np.int32)[::-1].copy()):        # the walk's own; not a permutation; a permutation that is no better
+        def broken(at, value):
+            h = perm.copy(); h[at] = value
+            return h
+        for hint in (perm, np.zeros(n, np.int32), np.arange(n, dtype=np.int32)[::-1].copy(),         # the walk's own; not a permutation; a permutation that is no better;
+                     broken(n // 2, n), broken(5, -1), broken(n - 1, perm[0])):                      # an entry equal to n; an entry of -1; a duplicate in the last position only
             plan2 = C.c_void_p()
             check(lib.liship_csr_plan_create(C.byref(plan2), n, dptr.ptr, None))
             check(lib.liship_csr_plan_localize_columns(plan2, dptr.ptr, didx.ptr, None))
             check(lib.liship_csr_plan_reorder_with(plan2, dptr.ptr, didx.ptr, dval2.ptr, 0, hint.ctypes.data, None))
             assert lib.liship_csr_plan_reordered(plan2) == re             # the same lists either way (the walk is deterministic)
+            perm2 = np.full(n, -7, np.int32)
+            check(lib.liship_csr_plan_reorder_permutation(plan2, perm2.ctypes.data))
+            assert np.array_equal(perm2, perm)                            # ... because every refused hint falls back to the walk, and the walk finds what it found
             dy = DA.from_host(np.full(n, np.nan), np.float64)
             check(lib.liship_spmv_csr_f64(plan2, dptr.ptr, didx.ptr, dval2.ptr, dx.ptr, dy.ptr, None))
             assert np.array_equal(dy.to_host(), yref2, equal_nan=True)
             check(lib.liship_csr_plan_destroy(plan2))
     lib.liship_spmv_csr_set_reorder(1)
     check(lib.liship_csr_plan_destroy(plan))
+
+
+_SPECIALS = np.array([-0.0, 0.0, np.inf, -np.inf, np.nan, 5e-324, -5e-324, 1e308, -1e308, 2.2250738585072014e-308])
+_SENTINEL = np.uint64(0x7FF8DEAD0000BEEF)                   # a quiet NaN nobody computes: memory no kernel may write
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 4, 5, 767, 768, 769, 3 * 256 * 2 + 1])
+def test_permute_gather_scatter_bits(lib, n):
+    """liship_permute_gather_f64 / _scatter_f64 work in triples per lane (csr_reorder_gather_kernel: i + 2 < n, then a tail loop): every n around a triple, a
+    workgroup of 256 triples and two of them, against numpy, by bits, special values among the data, and nothing written behind the n entries"""
+    rng = np.random.default_rng(400 + n)
+    perm = rng.permutation(n).astype(np.int32)
+    x = rng.uniform(-1, 1, n)
+    if n:
+        x[rng.choice(n, min(n, 40), replace=False)] = np.resize(_SPECIALS, min(n, 40))
+    pad = 4
+    dperm, dx = DA.from_host(np.concatenate([perm, np.zeros(pad, np.int32)]), np.int32), DA.from_host(np.concatenate([x, np.zeros(pad)]), np.float64)
+    for fn, want in ((lib.liship_permute_gather_f64, x[perm]), (lib.liship_permute_scatter_f64, x[np.argsort(perm)])):
+        out = DA.from_host(np.full(n + pad, _SENTINEL, np.uint64), np.uint64)
+        check(fn(n, dperm.ptr, dx.ptr, out.ptr, None))
+        got = out.to_host()
+        assert np.array_equal(got[:n], want.view(np.uint64)), fn.__name__
+        assert np.all(got[n:] == _SENTINEL), fn.__name__
+    if n:
+        assert lib.liship_permute_gather_f64(n, dperm.ptr, dx.ptr, dx.ptr, None) == -1          # x and xp distinct
+        assert lib.liship_permute_scatter_f64(n, None, dx.ptr, dx.ptr + 8, None) == -1
+    assert lib.liship_permute_gather_f64(-1, dperm.ptr, dx.ptr, dx.ptr, None) == -1
+
+
+@pytest.mark.parametrize("count", [0, 1, 255, 256, 257])
+def test_permute_rows_of_list(lib, count):
+    """liship_permute_rows_of_list: out[k] = the position of row index[k] under perm, around one 256-thread workgroup; rows may repeat; nothing behind the list"""
+    n = 1000
+    rng = np.random.default_rng(500 + count)
+    perm = rng.permutation(n).astype(np.int32)
+    inv = np.empty(n, np.int32); inv[perm] = np.arange(n)
+    rows = rng.integers(0, n, count).astype(np.int32)
+    if count > 2:
+        rows[:3] = (0, n - 1, n - 1)
+    dperm, drows = DA.from_host(perm, np.int32), DA.from_host(rows, np.int32)
+    out = DA.from_host(np.full(count + 4, -7, np.int32), np.int32)
+    check(lib.liship_permute_rows_of_list(n, dperm.ptr, count, drows.ptr, out.ptr, None))
+    got = out.to_host()
+    assert np.array_equal(got[:count], inv[rows]) and np.all(got[count:] == -7)
+    if count:
+        assert lib.liship_permute_rows_of_list(n, dperm.ptr, count, None, out.ptr, None) == -1
+        assert lib.liship_permute_rows_of_list(n, None, count, drows.ptr, out.ptr, None) == -1
 
 
 @pytest.mark.parametrize("L", [21, 22, 23, 25, 26, 41, 42, 43, 62, 63, 81, 85, 101, 127])
