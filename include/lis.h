@@ -99,6 +99,51 @@ typedef LIS_INT      LIS_Comm;         /* ref:485 */
 #define LIS_PARAMS_RESID_WEIGHT (LIS_OPTIONS_LEN+13)
 #define LIS_PARAMS_SAAMG_THETA  (LIS_OPTIONS_LEN+14)
 
+/* ---- eigensolver option slots, ref:99-134 ----------------------------------------------------- */
+#define LIS_EOPTIONS_LEN 13           /* ref:99 */
+#define LIS_EOPTIONS_ESOLVER 0        /* ref:100 */
+#define LIS_EOPTIONS_MAXITER 1        /* ref:101 */
+#define LIS_EOPTIONS_SUBSPACE 2       /* ref:102 */
+#define LIS_EOPTIONS_MODE 3           /* ref:103 */
+#define LIS_EOPTIONS_OUTPUT 4         /* ref:104 */
+#define LIS_EOPTIONS_INITGUESS_ONES 5 /* ref:105 */
+#define LIS_EOPTIONS_INNER_ESOLVER 6  /* ref:106 */
+#define LIS_EOPTIONS_INNER_GENERALIZED_ESOLVER 7   /* ref:107 */
+#define LIS_EOPTIONS_STORAGE 8        /* ref:108 */
+#define LIS_EOPTIONS_STORAGE_BLOCK 9  /* ref:109 */
+#define LIS_EOPTIONS_PRECISION 10     /* ref:110 */
+#define LIS_EOPTIONS_SWITCH_MAXITER 11 /* ref:111 */
+#define LIS_EOPTIONS_RVAL 12          /* ref:112 */
+
+#define LIS_EPARAMS_LEN 3             /* ref:131 */
+#define LIS_EPARAMS_RESID    (LIS_EOPTIONS_LEN+0)   /* ref:132 */
+#define LIS_EPARAMS_SHIFT    (LIS_EOPTIONS_LEN+1)   /* ref:133 */
+#define LIS_EPARAMS_SHIFT_IM (LIS_EOPTIONS_LEN+2)   /* ref:134 */
+
+#define LIS_EPRINT_NONE 0             /* ref:146 */
+#define LIS_EPRINT_MEM 1              /* ref:147 */
+#define LIS_EPRINT_OUT 2              /* ref:148 */
+#define LIS_EPRINT_ALL 3              /* ref:149 */
+
+/* eigensolver ids, ref:188-204 (served: PI, II, RQI, CG, CR) */
+#define LIS_ESOLVER_LEN 16            /* ref:188 */
+#define LIS_ESOLVER_PI 1              /* ref:189 */
+#define LIS_ESOLVER_II 2              /* ref:190 */
+#define LIS_ESOLVER_RQI 3             /* ref:191 */
+#define LIS_ESOLVER_CG 4              /* ref:192 */
+#define LIS_ESOLVER_CR 5              /* ref:193 */
+#define LIS_ESOLVER_SI 6              /* ref:194 */
+#define LIS_ESOLVER_LI 7              /* ref:195 */
+#define LIS_ESOLVER_AI 8              /* ref:196 */
+#define LIS_ESOLVER_GPI 9             /* ref:197 */
+#define LIS_ESOLVER_GII 10            /* ref:198 */
+#define LIS_ESOLVER_GRQI 11           /* ref:199 */
+#define LIS_ESOLVER_GCG 12            /* ref:200 */
+#define LIS_ESOLVER_GCR 13            /* ref:201 */
+#define LIS_ESOLVER_GSI 14            /* ref:202 */
+#define LIS_ESOLVER_GLI 15            /* ref:203 */
+#define LIS_ESOLVER_GAI 16            /* ref:204 */
+
 #define LIS_PRINT_NONE 0              /* ref:142-145 */
 #define LIS_PRINT_MEM 1
 #define LIS_PRINT_OUT 2
@@ -425,6 +470,35 @@ struct LIS_SOLVER_STRUCT
 };
 typedef struct LIS_SOLVER_STRUCT *LIS_SOLVER;
 
+/* ref:760-786 */
+struct LIS_ESOLVER_STRUCT
+{
+	LIS_MATRIX A,B;
+	LIS_VECTOR x,xx,d;
+	LIS_SCALAR *evalue;
+	LIS_VECTOR *evector;
+	LIS_REAL *resid;
+	LIS_VECTOR *work;
+	LIS_REAL *rhistory;
+	LIS_INT worklen;
+	LIS_INT options[LIS_EOPTIONS_LEN];
+	LIS_SCALAR params[LIS_EPARAMS_LEN];
+	LIS_INT retcode;
+	LIS_INT *iter;
+	LIS_INT *iter2;
+	double time;
+	LIS_INT *nesol;
+	double itime;
+	double ptime;
+	double p_c_time;
+	double p_i_time;
+	LIS_INT eprecision;
+	LIS_SCALAR ishift;
+	LIS_REAL nrm2;
+	LIS_REAL tol;
+};
+typedef struct LIS_ESOLVER_STRUCT *LIS_ESOLVER;
+
 /* kernel-level SpMV entry points, ref include/lis_matvec.h:76,91-181: raw HOST arrays in, raw host
  * array out; the matrix is the (cached) device copy of A */
 typedef void (*LIS_MATVEC_XXX)(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);
@@ -503,6 +577,10 @@ LIS_INT lis_matrix_set_values(LIS_INT flag, LIS_INT n, LIS_SCALAR value[], LIS_M
 LIS_INT lis_matrix_malloc(LIS_MATRIX A, LIS_INT nnz_row, LIS_INT nnz[]);                  /* ref:880, lis_matrix.c:592 (row capacity hint) */
 LIS_INT lis_matrix_get_diagonal(LIS_MATRIX A, LIS_VECTOR d);
 LIS_INT lis_matrix_scale(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR D, LIS_INT action);   /* ref:882, src/matrix/lis_matrix_ops.c:579 (-scale) */
+/* A <- A - sigma I: the first stored diagonal entry of every row (a split matrix: A->D); a matrix whose copy lives in HBM in CSR storage is
+ * edited there by a kernel, its host arrays on the host, and nothing crosses the bus (host/lis_shift.c).  The reference keeps this one in its
+ * internal header too (src/matrix lis_matrix.h; lis_matrix_ops.c:781) */
+LIS_INT lis_matrix_shift_diagonal(LIS_MATRIX A, LIS_SCALAR sigma);
 LIS_INT lis_matrix_convert(LIS_MATRIX Ain, LIS_MATRIX Aout);
 /* A = L + D + U in A->L / A->D / A->U (is_splited): lis_matvec then adds D x first, the L entries, the U entries.  The
  * reference keeps these two in its internal header (src/matrix lis_matrix.h; lis_matrix_ops.c:860, :1052) */
@@ -559,6 +637,34 @@ LIS_INT lis_precon_destroy(LIS_PRECON precon);
 LIS_INT lis_solver_get_solvername(LIS_INT solver, char *solvername);
 LIS_INT lis_solver_get_preconname(LIS_INT precon_type, char *preconname);
 LIS_INT lis_solver_output_rhistory(LIS_SOLVER solver, char *filename);  /* ref:1022, src/system/lis_output.c:586 */
+/* ---- eigensolvers, ref:990-1013, 1026 (src/esolver/lis_esolver.c, _pi.c, _ii.c, _rqi.c, _cg.c) ----------------
+ * Served: one eigenpair by power (-e pi), inverse (-e ii), Rayleigh quotient (-e rqi), CG (-e cg) and CR (-e cr, the default) iteration, on one rank,
+ * in double precision.  -e si | li | ai, the generalized solvers (and lis_gesolve with a B), and the getters only those fill answer
+ * LIS_ERR_NOT_IMPLEMENTED before A or x is touched.  -estorage converts A for good, as -storage does in lis_solve. */
+LIS_INT lis_esolver_create(LIS_ESOLVER *esolver);                        /* ref:990 */
+LIS_INT lis_esolver_destroy(LIS_ESOLVER esolver);                        /* ref:991 */
+LIS_INT lis_esolver_set_option(char *text, LIS_ESOLVER esolver);         /* ref:993 */
+LIS_INT lis_esolver_set_optionC(LIS_ESOLVER esolver);                    /* ref:994 */
+LIS_INT lis_esolve(LIS_MATRIX A, LIS_VECTOR x, LIS_SCALAR *evalue0, LIS_ESOLVER esolver);                 /* ref:995 */
+LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue0, LIS_ESOLVER esolver);  /* ref:996; B == NULL is lis_esolve */
+LIS_INT lis_esolver_get_iter(LIS_ESOLVER esolver, LIS_INT *iter);        /* ref:997 */
+LIS_INT lis_esolver_get_iterex(LIS_ESOLVER esolver, LIS_INT *iter, LIS_INT *iter_double, LIS_INT *iter_quad);   /* ref:998 */
+LIS_INT lis_esolver_get_time(LIS_ESOLVER esolver, double *time);         /* ref:999 */
+LIS_INT lis_esolver_get_timeex(LIS_ESOLVER esolver, double *time, double *itime, double *ptime, double *p_c_time, double *p_i_time);   /* ref:1000 */
+LIS_INT lis_esolver_get_residualnorm(LIS_ESOLVER esolver, LIS_REAL *residual);   /* ref:1001 */
+LIS_INT lis_esolver_get_status(LIS_ESOLVER esolver, LIS_INT *status);    /* ref:1002 */
+LIS_INT lis_esolver_get_rhistory(LIS_ESOLVER esolver, LIS_VECTOR v);     /* ref:1003 */
+LIS_INT lis_esolver_get_evalues(LIS_ESOLVER esolver, LIS_VECTOR v);      /* ref:1004; as there LIS_ERR_ILL_ARG unless -e is a subspace / Lanczos / Arnoldi solver */
+LIS_INT lis_esolver_get_specific_evalue(LIS_ESOLVER esolver, LIS_INT mode, LIS_SCALAR *evalue);      /* ref:1005; refused */
+LIS_INT lis_esolver_get_evectors(LIS_ESOLVER esolver, LIS_MATRIX M);     /* ref:1006; refused */
+LIS_INT lis_esolver_get_specific_evector(LIS_ESOLVER esolver, LIS_INT mode, LIS_VECTOR x);           /* ref:1007; refused */
+LIS_INT lis_esolver_get_residualnorms(LIS_ESOLVER esolver, LIS_VECTOR v);                            /* ref:1008; as get_evalues */
+LIS_INT lis_esolver_get_specific_residualnorm(LIS_ESOLVER esolver, LIS_INT mode, LIS_REAL *residual); /* ref:1009; refused */
+LIS_INT lis_esolver_get_iters(LIS_ESOLVER esolver, LIS_VECTOR v);        /* ref:1010; as get_evalues */
+LIS_INT lis_esolver_get_specific_iter(LIS_ESOLVER esolver, LIS_INT mode, LIS_INT *iter);             /* ref:1011; refused */
+LIS_INT lis_esolver_get_esolver(LIS_ESOLVER esolver, LIS_INT *nesol);    /* ref:1012 */
+LIS_INT lis_esolver_get_esolvername(LIS_INT esolver, char *esolvername); /* ref:1013 */
+LIS_INT lis_esolver_output_rhistory(LIS_ESOLVER esolver, char *filename); /* ref:1026, src/system/lis_output.c:659 */
 /* ---- file I/O, ref:1019-1024 (src/system/lis_input.c, lis_input_mm.c, lis_output.c, lis_output_mm.c) ----
  * Matrix Market coordinate real general|symmetric, with Lis's size-line extension "nr nc nnz isb isx [isbin]"
  * (right-hand side / initial guess appended, optional binary records).  The reader fixes the in-row entry

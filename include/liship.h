@@ -396,6 +396,20 @@ int  liship_axpy_sumsq_dot_f64(int n, double a, const double *x, double *y, cons
  * result[], so a Hessenberg column needs no host synchronisation between its steps. */
 int  liship_mgs_step_f64(int n, const double *hprev, const double *vprev, double *w, const double *vnext,
                          double *result, void *work, void *stream);
+/* K inner products result[k] = <vecs[pairs[k][0]], vecs[pairs[k][1]]> over nvec <= LISHIP_MULTIDOT_MAX_VECS vectors of n elements in ONE pass: a
+ * workgroup reads its tile of every vector once (kernels/eigen.hip).  vecs and pairs are HOST arrays (of device pointers / of indices into vecs); a pair may
+ * name one vector twice, and two results may name the same pair.  Every sum is formed EXACTLY as liship_dot_f64 forms that pair alone -- the tree above, the
+ * 16 B or the 8 B lane mapping chosen from that pair's own two arrays, or the T chunks of liship_set_reference_reductions(T) -- so a loop may take its
+ * Gram block here or as K separate dots and find the same bits (the eigensolvers' CG and CR, host/lis_esolver.c; tests/test_multidot_gpu.py).  When some vector
+ * is only 8 B aligned, the tiles are swept a second time for the pairs that involve one (the second sweep reads from cache).  In the reference-order mode
+ * the K sums are K passes (one lane adds a chunk there: nothing to share).  Announce no liship_krylov_chain step before this call: the one pass
+ * leaves it pending, where liship_dot_f64 would run it. */
+#define LISHIP_MULTIDOT_MAX_VECS 8
+#define LISHIP_MULTIDOT_MAX_PAIRS 36
+int  liship_multidot_f64(int n, int nvec, const double *const *vecs, int K, const int (*pairs)[2], double *result, void *work, void *stream);
+/* value[k] -= sigma for the FIRST stored entry k of each row whose column is the row; a row without one is left alone (lis_matrix_shift_diagonal_csr,
+ * src/matrix/lis_matrix_csr.c:566-603, on arrays in HBM; a split matrix's chain rows start with their diagonal term, host/lis_split.c) */
+int  liship_csr_shift_diagonal_f64(int n, const int *ptr, const int *index, double *value, double sigma, void *stream);
 /* x *= 1/sqrt(*sumsq) with sumsq in HBM  (lis_vector_nrm2 + lis_vector_scale, lis_solver_gmres.c:229-232) */
 int  liship_scale_inv_norm_f64(int n, const double *sumsq, double *x, void *stream);
 
@@ -532,6 +546,10 @@ int  liship_gather_f64(int count, const int *export_index, const double *x, doub
  * 207-236).  The reference-order mode's A^T x for T > 1 (T = 1 is the plain row sum). */
 int  liship_spmv_csr_transposed_chunked_f64(int rows, int nsrc, int T, const int *tptr, const int *tidx, const double *tval,
                                             const double *x, double *y, void *stream);
+/* the same sums for transposed rows whose entries are NOT in ascending source row (the entry point above relies on that order): each thread chunk's terms in
+ * stored order.  What lis_matvech_ell's T threads form (src/matvec/lis_matvec_ell.c:182-222: the scatter walks slot after slot); T sweeps over a row. */
+int  liship_spmv_csr_transposed_chunked_unordered_f64(int rows, int nsrc, int T, const int *tptr, const int *tidx, const double *tval,
+                                                      const double *x, double *y, void *stream);
 int  liship_csr_transpose_f64(int nrows, int ncols, int nnz, const int *ptr, const int *index, const double *value,
                               int *tptr, int *tindex, double *tvalue, int *work, void *stream);
 /* ---- storage-format conversions of a CSR matrix that lives in HBM (kernels/convert.hip): the arrays the reference's host routines

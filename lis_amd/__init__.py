@@ -193,6 +193,8 @@ _LISHIP = {
     "liship_nrm1_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_sum_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_dot2_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
+    "liship_multidot_f64": (_ci, [_ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "liship_csr_shift_diagonal_f64": (_ci, [_ci, _vp, _vp, _vp, _cd, _vp]),
     "liship_csr_diagonal_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
     "liship_ell_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
     "liship_dia_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
@@ -200,6 +202,7 @@ _LISHIP = {
     "liship_spmv_formats_plane_blocks": (_ci, [_ci, _ci]),
     "liship_ell_scan_band": (_ci, [_ci, _ci, _vp, _vp, _vp]),
     "liship_spmv_csr_transposed_chunked_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_spmv_csr_transposed_chunked_unordered_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_bsr_to_rows": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_csr_transpose_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_gather_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),

@@ -106,6 +106,25 @@ PV = C.POINTER(Vector)
 PM = C.POINTER(Matrix)
 PS = C.POINTER(Solver)
 
+LIS_EOPTIONS_LEN, LIS_EPARAMS_LEN = 13, 3
+LIS_ESOLVER_PI, LIS_ESOLVER_II, LIS_ESOLVER_RQI, LIS_ESOLVER_CG, LIS_ESOLVER_CR = 1, 2, 3, 4, 5
+
+
+class ESolver(C.Structure):
+    """LIS_ESOLVER_STRUCT (lis.h:760-786)."""
+    _fields_ = [
+        ("A", PM), ("B", PM), ("x", PV), ("xx", PV), ("d", PV),
+        ("evalue", P_DBL), ("evector", C.c_void_p), ("resid", P_DBL), ("work", C.c_void_p),
+        ("rhistory", P_DBL), ("worklen", LIS_INT),
+        ("options", LIS_INT * LIS_EOPTIONS_LEN), ("params", LIS_SCALAR * LIS_EPARAMS_LEN),
+        ("retcode", LIS_INT), ("iter", P_INT), ("iter2", P_INT), ("time", C.c_double), ("nesol", P_INT),
+        ("itime", C.c_double), ("ptime", C.c_double), ("p_c_time", C.c_double), ("p_i_time", C.c_double),
+        ("eprecision", LIS_INT), ("ishift", LIS_SCALAR), ("nrm2", LIS_REAL), ("tol", LIS_REAL),
+    ]
+
+
+PE = C.POINTER(ESolver)
+
 _PROTOS = {
     # utilities (lis.h:1030-1045)
     "lis_initialize": (LIS_INT, [C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p))]),
@@ -209,6 +228,32 @@ _PROTOS = {
     "lis_solver_output_rhistory": (LIS_INT, [PS, C.c_char_p]),
     "lis_solver_get_solvername": (LIS_INT, [LIS_INT, C.c_char_p]),
     "lis_solver_get_preconname": (LIS_INT, [LIS_INT, C.c_char_p]),
+    # eigensolvers (lis.h:990-1013, 1026) and the shift they are made of (lis_matrix.h of the reference)
+    "lis_esolver_create": (LIS_INT, [C.POINTER(PE)]),
+    "lis_esolver_destroy": (LIS_INT, [PE]),
+    "lis_esolver_set_option": (LIS_INT, [C.c_char_p, PE]),
+    "lis_esolver_set_optionC": (LIS_INT, [PE]),
+    "lis_esolve": (LIS_INT, [PM, PV, P_DBL, PE]),
+    "lis_gesolve": (LIS_INT, [PM, PM, PV, P_DBL, PE]),
+    "lis_esolver_get_iter": (LIS_INT, [PE, P_INT]),
+    "lis_esolver_get_iterex": (LIS_INT, [PE, P_INT, P_INT, P_INT]),
+    "lis_esolver_get_time": (LIS_INT, [PE, P_DBL]),
+    "lis_esolver_get_timeex": (LIS_INT, [PE, P_DBL, P_DBL, P_DBL, P_DBL, P_DBL]),
+    "lis_esolver_get_residualnorm": (LIS_INT, [PE, P_DBL]),
+    "lis_esolver_get_status": (LIS_INT, [PE, P_INT]),
+    "lis_esolver_get_rhistory": (LIS_INT, [PE, PV]),
+    "lis_esolver_get_evalues": (LIS_INT, [PE, PV]),
+    "lis_esolver_get_specific_evalue": (LIS_INT, [PE, LIS_INT, P_DBL]),
+    "lis_esolver_get_evectors": (LIS_INT, [PE, PM]),
+    "lis_esolver_get_specific_evector": (LIS_INT, [PE, LIS_INT, PV]),
+    "lis_esolver_get_residualnorms": (LIS_INT, [PE, PV]),
+    "lis_esolver_get_specific_residualnorm": (LIS_INT, [PE, LIS_INT, P_DBL]),
+    "lis_esolver_get_iters": (LIS_INT, [PE, PV]),
+    "lis_esolver_get_specific_iter": (LIS_INT, [PE, LIS_INT, P_INT]),
+    "lis_esolver_get_esolver": (LIS_INT, [PE, P_INT]),
+    "lis_esolver_get_esolvername": (LIS_INT, [LIS_INT, C.c_char_p]),
+    "lis_esolver_output_rhistory": (LIS_INT, [PE, C.c_char_p]),
+    "lis_matrix_shift_diagonal": (LIS_INT, [PM, LIS_SCALAR]),
     # memory (lis.h:1037-1042)
     "lis_malloc": (C.c_void_p, [C.c_size_t, C.c_char_p]),
     "lis_free": (None, [C.c_void_p]),

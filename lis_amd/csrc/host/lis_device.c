@@ -49,7 +49,7 @@ LIS_INT lisd_init(void)
 	HIPCHK(liship_set_device(lisg.device));
 	HIPCHK(liship_stream_create(&lisg.stream));
 	HIPCHK(lisd_malloc(&lisg.reduce_work, liship_reduce_work_bytes()));
-	HIPCHK(lisd_malloc((void **)&lisg.reduce_out, 4 * sizeof(double)));
+	HIPCHK(lisd_malloc((void **)&lisg.reduce_out, 64 * sizeof(double)));      /* (4 for the Krylov passes, LISHIP_MULTIDOT_MAX_PAIRS for lisd_multidot) */
 	HIPCHK(liship_malloc_host((void **)&lisg.host_out, 4 * 64 * sizeof(double)));
 	HIPCHK(liship_spmv_csr_set_long_row_tree((lisg.long_row_chain || lisg.ref_reductions) ? 0 : 1));     /* parity modes take the chain */
 	if (lisg.reference_layout) LISCHK(lis_amd_set_reference_layout(1));
@@ -478,6 +478,18 @@ LIS_INT lisd_dot2(int n, const double *dx, const double *dy, double *out2)
 {
 	HIPCHK(liship_dot2_f64(n, dx, dy, lisg.reduce_out, lisg.reduce_work, lisg.stream));
 	return lisd_fetch(2, out2);
+}
+
+/* out[k] = <dv[pairs[k][0]], dv[pairs[k][1]]>, k < K <= LISHIP_MULTIDOT_MAX_PAIRS: one pass over the vectors and one read-back (liship_multidot_f64), or -- with
+ * LIS_AMD_NO_FUSION=1 / the UNFUSED loop mode, and in a multi-rank job, whose fold takes 4 sums at a time -- K dots.  The same bits either way. */
+LIS_INT lisd_multidot(int n, int nvec, const double *const *dv, int K, const int (*pairs)[2], double *out)
+{
+	if (lisg.no_fusion || lisg.nprocs > 1) {
+		for (int k = 0; k < K; k++) LISCHK(lisd_dot(n, dv[pairs[k][0]], dv[pairs[k][1]], &out[k]));
+		return LIS_SUCCESS;
+	}
+	HIPCHK(liship_multidot_f64(n, nvec, dv, K, pairs, lisg.reduce_out, lisg.reduce_work, lisg.stream));
+	return lisd_fetch(K, out);
 }
 
 /* ------------------------------------------------------------------ matrices born in HBM */

@@ -155,7 +155,7 @@ typedef struct {
 	int device;
 	void *stream;
 	void *reduce_work;         /* HBM scratch of the two-stage reductions */
-	double *reduce_out;        /* HBM: up to 4 results */
+	double *reduce_out;        /* HBM: up to 4 results of a Krylov pass, up to LISHIP_MULTIDOT_MAX_PAIRS of lisd_multidot (room for 64) */
 	double *gather_out;        /* HBM: nprocs * 4 doubles (cross-rank fold) */
 	double *host_out;          /* page-locked: 4 results, and up to 4 x 64 gathered partials */
 	/* communicator */
@@ -256,6 +256,10 @@ LIS_INT lisd_dot2(int n, const double *dx, const double *dy, double *out2);
 /* ---- the HBM copy of a matrix (lis_upload.c) and what the conversion in HBM (lis_convert_hbm.c) decides with the same code */
 LIS_INT lisd_mat_ready(LIS_MATRIX A);
 void    lisd_mat_free(LIS_MATRIX A);
+LIS_INT lisd_mat_values_changed(LIS_MATRIX A);                                /* a kernel edited d->value of a CSR copy in place: derived data dropped, the plan made again from the HBM arrays */
+void    lisd_mat_host_edit_begin(LIS_MATRIX A);                               /* the library itself edits the watched host arrays (the copy carries the edit already) ... */
+void    lisd_mat_host_edit_end(LIS_MATRIX A);                                 /* ... watched again, host_written untouched */
+LIS_INT lisd_multidot(int n, int nvec, const double *const *dv, int K, const int (*pairs)[2], double *out);   /* K inner products -> host; one pass, or K dots under LIS_AMD_NO_FUSION (same bits) */
 LIS_INT lisd_upload_i(int **dst, const int *src, size_t count);               /* a fresh HBM array holding src[0 .. count), queued on the library's stream */
 LIS_INT lisd_upload_d(double **dst, const double *src, size_t count);         /* (src NULL: room only) */
 LIS_INT lisd_csr_plan(liship_csr_plan_t *plan, int n, const int *dptr, const int *dindex, const double *dvalue);   /* row split + index codes */

@@ -235,8 +235,12 @@ LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy)
 	LISCHK(lisd_mat_ready_t(A));
 	if (lisg.ref_reductions > 1 && A->matrix_type == LIS_MATRIX_CSR)
 		/* reference-order mode at T > 1: the OpenMP build's per-thread scatter buffers group a column's terms by row chunk (lis_matvec_csr.c:207-236).
-		 * CSR only: the other formats' threaded walks group differently again and keep the one-thread order */
+		 * CSR here, ELL below; DIA, JAD and BSR keep the one-thread order (their threaded walks group differently again) */
 		HIPCHK(liship_spmv_csr_transposed_chunked_f64(d->t_rows, A->n, lisg.ref_reductions, d->t_ptr, d->t_index, d->t_value, dx, dy, lisg.stream));
+	else if (lisg.ref_reductions > 1 && A->matrix_type == LIS_MATRIX_ELL && !A->is_splited)
+		/* ... and ELL: its threads own the same row chunks and walk them slot after slot (lis_matvec_ell.c:182-222) -- the transposed rows list that walk, a chunk's
+		 * terms are not contiguous in them.  What the BiCG inside `lis_esolve -e ii -estorage ell` needs to carry the reference's bits at T > 1 */
+		HIPCHK(liship_spmv_csr_transposed_chunked_unordered_f64(d->t_rows, A->n, lisg.ref_reductions, d->t_ptr, d->t_index, d->t_value, dx, dy, lisg.stream));
 	else
 		HIPCHK(liship_spmv_csr_f64(d->t_plan, d->t_ptr, d->t_index, d->t_value, dx, dy, lisg.stream));
 	if (d->t_diag)          /* split CSR: y = D.*x + 1*w, w the off-diagonal sums just formed (1*w is w; lis_matvec_csr.c:152-159) */

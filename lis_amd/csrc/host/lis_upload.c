@@ -590,6 +590,41 @@ void lisd_mat_free(LIS_MATRIX A)
 	lisp_matrix_release(A, 0);         /* no copy left that a host write could leave stale: the watched arrays are plain memory again */
 }
 
+/* ------------------------------------------------------------------ values edited in place (lis_matrix_shift_diagonal, lis_shift.c)
+ * A kernel changed d->value of a CSR copy where it lies: everything derived from the old values goes -- the plan with its value records and its renumbered
+ * form, the transposed copies in both numberings, what the preconditioners cached on the copy -- and the plan is made again from the HBM arrays, by the
+ * call that made it at upload time (mat_upload / upload_split / lis_amd_matrix_set_csr_device).  The transposed copy and the caches come back on their
+ * next use.  No matrix array crosses the bus. */
+LIS_INT lisd_mat_values_changed(LIS_MATRIX A)
+{
+	lisd_mat *d = MDEV(A);
+	if (d->plan) { (void)liship_csr_plan_destroy(d->plan); d->plan = NULL; }
+	if (d->t_plan) { (void)liship_csr_plan_destroy(d->t_plan); d->t_plan = NULL; }
+	(void)liship_free(d->t_ptr); (void)liship_free(d->t_index); (void)liship_free(d->t_value); (void)liship_free(d->t_diag);
+	d->t_ptr = NULL; d->t_index = NULL; d->t_value = NULL; d->t_diag = NULL; d->t_ready = 0; d->t_nnz = 0;
+	if (d->rt_plan) { (void)liship_csr_plan_destroy(d->rt_plan); d->rt_plan = NULL; }
+	(void)liship_free(d->rt_ptr); (void)liship_free(d->rt_index); (void)liship_free(d->rt_value);
+	d->rt_ptr = NULL; d->rt_index = NULL; d->rt_value = NULL; d->rt_ready = 0; d->rt_nnz = 0;
+	lisi_precon_release(d, NULL, NULL);
+	d->reorder_tried = 0; d->served = 0;
+	if (A->is_splited) {
+		LISCHK(lisd_csr_plan(&d->plan, d->n, d->ptr, d->index, d->value));
+		HIPCHK(liship_csr_plan_set_first_term_initialises(d->plan, 1));      /* (CSR chain rows: upload_rows, from_zero = 0) */
+	} else LISCHK(lisd_csr_plan_cols(&d->plan, A->n, d->device_only ? d->np : A->np, d->ptr, d->index, d->value));
+	HIPCHK(liship_stream_synchronize(lisg.stream));
+	return LIS_SUCCESS;
+}
+
+/* ... and the same edit made by the library on the watched host arrays: they open for it without the write being taken for the program's (host_written
+ * stays as it is, the copy is kept), then close again; LIS_AMD_MATRIX_CHECK's hash is taken anew */
+void lisd_mat_host_edit_begin(LIS_MATRIX A) { lisp_matrix_release(A, 0); }
+void lisd_mat_host_edit_end(LIS_MATRIX A)
+{
+	lisd_mat *d = MDEV(A);
+	(void)lisp_matrix_protect(A);
+	if (lisg.matrix_check && d->checked) d->host_hash = host_arrays_hash(A);
+}
+
 /* ------------------------------------------------------------------ what the copy looks like (tests, drivers) */
 LIS_INT lis_amd_matrix_upload(LIS_MATRIX A) { return lisd_mat_ready(A); }
 /* a fact of the plan of A's copy, 0 where there is no copy or no plan */

@@ -235,7 +235,42 @@ void spmv_t_chunked_kernel(int rows, int nsrc, int T, const int *__restrict__ tp
     total += part;
     y[c] = total;
 }
+// The same sums when the entries of a transposed row are NOT in ascending source row -- the scatter order of lis_matvech_ell is slot after slot, and within
+// a slot row after row (src/matvec/lis_matvec_ell.c:182-222): thread k still owns the source rows of chunk k and adds its own terms in the order its walk
+// meets them, which is the stored order restricted to the chunk.  One sweep over the row per chunk: T times the row's length, rows of an ELL matrix are short.
+__global__ __launch_bounds__(BLOCK)
+void spmv_t_chunked_unordered_kernel(int rows, int nsrc, int T, const int *__restrict__ tptr, const int *__restrict__ tidx,
+                                     const double *__restrict__ tval, const double *__restrict__ x, double *__restrict__ y, const double *skip)
+{
+    if (skip && skip[0] != 0.0) return;
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= rows) return;
+    const int q = nsrc / T, rem = nsrc % T;
+    const long long big = (long long)rem * (q + 1);
+    const int b = tptr[c], e = tptr[c + 1];
+    double total = 0.0;
+    for (int chunk = 0; chunk < T; chunk++) {
+        double part = 0.0;
+        for (int k = b; k < e; k++) {
+            const int j = tidx[k];
+            const int kc = j < big ? j / (q + 1) : rem + (int)((j - big) / q);
+            if (kc == chunk) part += tval[k] * x[j];
+        }
+        total += part;
+    }
+    y[c] = total;
+}
 } // namespace
+
+extern "C" int liship_spmv_csr_transposed_chunked_unordered_f64(int rows, int nsrc, int T, const int *tptr, const int *tidx, const double *tval,
+                                                                const double *x, double *y, void *stream)
+{
+    if (rows < 0 || nsrc < 0 || T < 1) return LISHIP_ERR_ARG;
+    if (rows == 0) return 0;
+    spmv_t_chunked_unordered_kernel<<<(rows + BLOCK - 1) / BLOCK, BLOCK, 0, as_stream(stream)>>>(rows, nsrc, T, tptr, tidx, tval, x, y, liship_internal_guard());
+    LAUNCH_CHECK();
+    return 0;
+}
 
 // y[0..rows) = A^T x from the transposed CSR (rows = columns of A, nsrc = rows of A), summed as the reference's T threads do
 extern "C" int liship_spmv_csr_transposed_chunked_f64(int rows, int nsrc, int T, const int *tptr, const int *tidx, const double *tval,
