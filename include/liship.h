@@ -315,7 +315,19 @@ int  liship_spmv_bsr_f64(int nr, int bnr, int bnc, const int *bptr, const int *b
  * per block row (short block rows) and a lane per block (long ones) */
 int  liship_spmv_bsr_nnz_f64(int nr, int bnnz, int bnr, int bnc, const int *bptr, const int *bindex,
                              const double *value, const double *x, double *y, void *stream);
-/* block rows [brb, bre) only (the array layout is that of all nr block rows): the parts of a multi-rank product around its halo exchange -- same bits */
+/* which kernel liship_spmv_bsr_nnz_f64 launches for these arguments (no launch; LISHIP_ERR_ARG for nr < 0 or a block size below 1).  The choice rests on the
+ * block size, bnnz / nr, liship_spmv_bsr_set_team and on whether bindex, value, x and y are 16 B aligned; every kind writes the same bits. */
+#define LISHIP_BSR_GENERIC 0   /* any bnr x bnc: one lane per scalar row */
+#define LISHIP_BSR_TILE    1   /* square 1..4: two phases, products through LDS */
+#define LISHIP_BSR_PAIR22  2   /* 2x2: the same with a lane per block */
+#define LISHIP_BSR_ROWS    3   /* square 2..4, short block rows: a lane per block row */
+#define LISHIP_BSR_TEAM    4   /* square 2..4, long block rows: eight lanes per block row */
+int  liship_spmv_bsr_kind(int nr, int bnnz, int bnr, int bnc, const int *bindex, const double *value, const double *x, const double *y);
+/* the kind of the kernel the last liship_spmv_bsr_f64 / _nnz_f64 / _rows_f64 call of this process launched (-1: none yet; a call that launches nothing --
+ * nr = 0, an empty range, a refusal -- leaves it; liship_spmv_bsr_dot_f64 does not go through the choice and leaves it too) */
+int  liship_spmv_bsr_last_kind(void);
+/* block rows [brb, bre) only (the array layout is that of all nr block rows): the parts of a multi-rank product around its halo exchange -- same bits, and
+ * the kernel liship_spmv_bsr_kind names for the whole matrix's nr and bnnz with y + brb * bnr */
 int  liship_spmv_bsr_rows_f64(int nr, int bnnz, int bnr, int bnc, const int *bptr, const int *bindex, const double *value,
                               const double *x, double *y, int brb, int bre, void *stream);
 /* A/B switch: 0 keeps square blocks with long block rows (mean > 12 / 16 / 12 stored blocks per block row at 2x2 / 3x3 / 4x4) on the two-phase tile

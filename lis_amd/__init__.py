@@ -89,6 +89,8 @@ _LISHIP = {
     "liship_spmv_csr_set_block_rows": (_ci, [_ci]),
     "liship_spmv_bsr_rows_f64": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp]),
     "liship_spmv_bsr_set_team": (_ci, [_ci]),
+    "liship_spmv_bsr_kind": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "liship_spmv_bsr_last_kind": (_ci, []),
     "liship_csr_plan_encode_row_values": (_ci, [_vp, _vp, _vp, _vp]),
     "liship_csr_plan_value_records": (_ci, [_vp]),
     "liship_csr_plan_dominant_pattern": (_ci, [_vp]),

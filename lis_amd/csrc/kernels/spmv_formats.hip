@@ -960,17 +960,82 @@ extern "C" int liship_spmv_jad_f64(int n, int maxnzr, const int *perm, const int
     return 0;
 }
 
+// The ONE place that chooses the BSR kernel (LISHIP_BSR_*): the launches below switch on it and on nothing else, and liship_spmv_bsr_kind answers it
+// without a launch.  nr / bnnz are those of the WHOLE matrix (bnnz < 0: unknown), the pointers those the kernel will be given.  Square blocks up to 4x4
+// with 16 B aligned values take a native kernel: long block rows (mean > 12 / 16 / 12 stored blocks at 2x2 / 3x3 / 4x4) the team kernel where
+// g_bsr_team allows it, short ones the lane-per-block-row kernel where its 16 B accesses are aligned, everything else the two-phase kernels.
+static int bsr_kind(int nr, int bnnz, int bnr, int bnc, const int *bidx, const double *val, const double *x, const double *y)
+{
+    if (bnr != bnc || bnr > 4 || !aligned16(val)) return LISHIP_BSR_GENERIC;
+    const double mean = bnnz >= 0 && nr > 0 ? (double)bnnz / nr : 0.0;     // stored blocks per block row
+    switch (bnr) {
+    case 1: return LISHIP_BSR_TILE;
+    case 2:
+        if (g_bsr_team && bnnz >= 0 && mean > 12.0) return LISHIP_BSR_TEAM;
+        if (aligned16(x) && aligned16(y) && aligned16(bidx) && (bnnz < 0 || mean <= 12.0)) return LISHIP_BSR_ROWS;
+        return aligned16(x) ? LISHIP_BSR_PAIR22 : LISHIP_BSR_TILE;
+    case 3:
+        if (g_bsr_team && bnnz >= 0 && mean > 16.0) return LISHIP_BSR_TEAM;
+        return aligned16(bidx) && bnnz >= 0 && mean <= 16.0 ? LISHIP_BSR_ROWS : LISHIP_BSR_TILE;
+    default:
+        // (4x4 long block rows stay with the tile kernel: a team's T rounds cost T x the additions, and at 16 per block that is what binds --
+        //  <4, 16, 2> 62.6 %, <4, 8, 4> 62.0-63.8 % against 65.8-68.4 %, profiles/r03_bsr_team_kernel.txt; g_bsr_team = 2 selects it for A/B)
+        if (g_bsr_team == 2 && bnnz >= 0 && mean > 12.0) return LISHIP_BSR_TEAM;
+        return aligned16(x) && aligned16(y) && aligned16(bidx) && bnnz >= 0 && mean <= 12.0 ? LISHIP_BSR_ROWS : LISHIP_BSR_TILE;
+    }
+}
+
+extern "C" int liship_spmv_bsr_kind(int nr, int bnnz, int bnr, int bnc, const int *bidx, const double *val, const double *x, const double *y)
+{
+    if (nr < 0 || bnr < 1 || bnc < 1) return LISHIP_ERR_ARG;
+    return bsr_kind(nr, bnnz, bnr, bnc, bidx, val, x, y);
+}
+
+// kernel `kind` on the nr block rows behind bptr (a whole matrix, or a block-row range of one: see liship_spmv_bsr_rows_f64).
+// g_bsr_launched is the kind of the last kernel that went out through here (liship_spmv_bsr_last_kind: a test can tell which one a range was given)
+static int g_bsr_launched = -1;
+extern "C" int liship_spmv_bsr_last_kind(void) { return g_bsr_launched; }
+
+static int bsr_launch(int kind, int nr, int bnr, int bnc, const int *bptr, const int *bidx, const double *val, const double *x, double *y, void *stream)
+{
+    if (nr == 0) return 0;
+    const long long rows = (long long)nr * bnr;
+    if (rows > 0x7fffffffLL) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    const int brw = BLOCK / (bnr <= 4 ? bnr : 4), grid = (nr + brw - 1) / brw;       // (the two-phase kernels: square blocks up to 4x4 only)
+    const int lanes = (nr + BSR_LANES - 1) / BSR_LANES, teams = (nr + 7) / 8;
+    switch (kind * 8 + (kind == LISHIP_BSR_GENERIC ? 0 : bnr)) {
+    case LISHIP_BSR_TILE * 8 + 1: spmv_bsr_tile_kernel<1, 1><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_TILE * 8 + 2: spmv_bsr_tile_kernel<2, 2><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_TILE * 8 + 3: spmv_bsr_tile_kernel<3, 3><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_TILE * 8 + 4: spmv_bsr_tile_kernel<4, 4><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_PAIR22 * 8 + 2: spmv_bsr22_kernel<<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_ROWS * 8 + 2: spmv_bsr_rows_kernel<2, 512, 8><<<lanes, BSR_LANES, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_ROWS * 8 + 3: spmv_bsr_rows_kernel<3, 352, 12><<<lanes, BSR_LANES, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_ROWS * 8 + 4: spmv_bsr_rows_kernel<4, 160, 8><<<lanes, BSR_LANES, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_TEAM * 8 + 2: spmv_bsr_team_kernel<2, 8, 4><<<teams, WAVE, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_TEAM * 8 + 3: spmv_bsr_team_kernel<3, 8, 4><<<teams, WAVE, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_TEAM * 8 + 4: spmv_bsr_team_kernel<4, 8, 4><<<teams, WAVE, 0, st>>>(nr, bptr, bidx, val, x, y); break;
+    case LISHIP_BSR_GENERIC * 8: spmv_bsr_kernel<<<grid_for((int)rows), BLOCK, 0, st>>>((int)rows, bnr, bnc, bptr, bidx, val, x, y); break;
+    default: return LISHIP_ERR_ARG;                     // (a kind bsr_kind never gives for this block size)
+    }
+    g_bsr_launched = kind;
+    LAUNCH_CHECK();
+    return 0;
+}
+
 // Block rows [brb, bre) only: a multi-rank product runs the block rows that reference no ghost block column while the halo is in flight and the boundary block
 // rows after it.  A block-row range of a BSR matrix IS a BSR matrix -- bptr + brb still indexes the whole bindex / value arrays, y moves by brb * bnr -- so
-// the kernels above serve it unchanged (the same kind of kernel as the whole matrix takes: the mean block-row length is the matrix's); rows are independent,
-// so the parts write the bits of the whole launch.
+// the kernels above serve it unchanged.  The kind is the one bsr_kind gives the WHOLE matrix's nr and bnnz with the pointers of this launch (y + brb * bnr):
+// every part runs the kernel that was chosen for the matrix, whatever its own share of the blocks; rows are independent, so the parts write the bits of
+// the whole launch.
 extern "C" int liship_spmv_bsr_rows_f64(int nr, int bnnz, int bnr, int bnc, const int *bptr, const int *bidx, const double *val,
                                         const double *x, double *y, int brb, int bre, void *stream)
 {
     if (nr < 0 || bnr < 1 || bnc < 1 || brb < 0 || bre > nr) return LISHIP_ERR_ARG;
     if (brb >= bre) return 0;
-    const long long part = nr > 0 && bnnz >= 0 ? (long long)bnnz * (bre - brb) / nr : -1;
-    return liship_spmv_bsr_nnz_f64(bre - brb, (int)part, bnr, bnc, bptr + brb, bidx, val, x, y + (size_t)brb * bnr, stream);
+    double *yp = y + (size_t)brb * bnr;
+    return bsr_launch(bsr_kind(nr, bnnz, bnr, bnc, bidx, val, x, yp), bre - brb, bnr, bnc, bptr + brb, bidx, val, x, yp, stream);
 }
 
 extern "C" int liship_spmv_bsr_set_team(int on) { g_bsr_team = on; return 0; }
@@ -1007,44 +1072,10 @@ extern "C" int liship_spmv_bsr_dot_f64(int nr, int n, int bnnz, int bs, const in
 }
 
 // the same with the number of stored blocks known (the host layer knows it): block rows that are short on average
-// take the lane-per-block-row kernel, long ones keep the lane-per-block(-column) kernels (as CSR's two kernels)
+// take the lane-per-block-row kernel, long ones keep the lane-per-block(-column) kernels (as CSR's two kernels) -- bsr_kind
 extern "C" int liship_spmv_bsr_nnz_f64(int nr, int bnnz, int bnr, int bnc, const int *bptr, const int *bidx,
                                        const double *val, const double *x, double *y, void *stream)
 {
     if (nr < 0 || bnr < 1 || bnc < 1) return LISHIP_ERR_ARG;
-    if (nr == 0) return 0;
-    const long long rows = (long long)nr * bnr;
-    if (rows > 0x7fffffffLL) return LISHIP_ERR_ARG;
-    hipStream_t st = as_stream(stream);
-    const double mean = bnnz >= 0 ? (double)bnnz / nr : 0.0;            // stored blocks per block row
-    if (bnr == bnc && bnr <= 4 && aligned16(val)) {
-        const int brw = BLOCK / bnr, grid = (nr + brw - 1) / brw;
-        switch (bnr) {
-        case 1: spmv_bsr_tile_kernel<1, 1><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y); break;
-        case 2:
-            if (g_bsr_team && bnnz >= 0 && mean > 12.0) { spmv_bsr_team_kernel<2, 8, 4><<<(nr + 7) / 8, WAVE, 0, st>>>(nr, bptr, bidx, val, x, y); break; }
-            if (aligned16(x) && aligned16(y) && aligned16(bidx) && (bnnz < 0 || mean <= 12.0))
-                spmv_bsr_rows_kernel<2, 512, 8><<<(nr + BSR_LANES - 1) / BSR_LANES, BSR_LANES, 0, st>>>(nr, bptr, bidx, val, x, y);
-            else if (aligned16(x)) spmv_bsr22_kernel<<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y);
-            else              spmv_bsr_tile_kernel<2, 2><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y);
-            break;
-        case 3:
-            if (g_bsr_team && bnnz >= 0 && mean > 16.0) { spmv_bsr_team_kernel<3, 8, 4><<<(nr + 7) / 8, WAVE, 0, st>>>(nr, bptr, bidx, val, x, y); break; }
-            if (aligned16(bidx) && bnnz >= 0 && mean <= 16.0) spmv_bsr_rows_kernel<3, 352, 12><<<(nr + BSR_LANES - 1) / BSR_LANES, BSR_LANES, 0, st>>>(nr, bptr, bidx, val, x, y);
-            else                 spmv_bsr_tile_kernel<3, 3><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y);
-            break;
-        default:
-            // (4x4 long block rows stay with the tile kernel: a team's T rounds cost T x the additions, and at 16 per block that is what binds --
-            //  <4, 16, 2> 62.6 %, <4, 8, 4> 62.0-63.8 % against 65.8-68.4 %, profiles/r03_bsr_team_kernel.txt; g_bsr_team = 2 selects it for A/B)
-            if (g_bsr_team == 2 && bnnz >= 0 && mean > 12.0) { spmv_bsr_team_kernel<4, 8, 4><<<(nr + 7) / 8, WAVE, 0, st>>>(nr, bptr, bidx, val, x, y); break; }
-            if (aligned16(x) && aligned16(y) && aligned16(bidx) && bnnz >= 0 && mean <= 12.0)
-                spmv_bsr_rows_kernel<4, 160, 8><<<(nr + BSR_LANES - 1) / BSR_LANES, BSR_LANES, 0, st>>>(nr, bptr, bidx, val, x, y);
-            else
-                spmv_bsr_tile_kernel<4, 4><<<grid, BLOCK, 0, st>>>(nr, bptr, bidx, val, x, y);
-            break;
-        }
-    } else
-        spmv_bsr_kernel<<<grid_for((int)rows), BLOCK, 0, st>>>((int)rows, bnr, bnc, bptr, bidx, val, x, y);
-    LAUNCH_CHECK();
-    return 0;
+    return bsr_launch(bsr_kind(nr, bnnz, bnr, bnc, bidx, val, x, y), nr, bnr, bnc, bptr, bidx, val, x, y, stream);
 }
