@@ -91,8 +91,13 @@ LIS_INT lis_amd_last_solve_renumbered(void);           /* 1: the last lis_solve 
 /* 1 when the last lis_solve ran -p ssor (else 0, and 0 in every field): its row blocks (1, or T of lis_amd_set_reference_reductions(T)),
  * the levels of its forward and backward sweeps, and the kernel launches of one psolve (runs of small levels share one launch) */
 LIS_INT lis_amd_last_solve_ssor(LIS_INT *blocks, LIS_INT *levels_fwd, LIS_INT *levels_bwd, LIS_INT *launches_per_psolve);
-/* SSOR schedule of a split CSR matrix with WD at the current block count: info = {host seconds spent building schedules for A,
- * bytes one psolve streams (level-ordered layout), launches per psolve, forward levels} (tools/ssor_probe.py) */
+/* 0 when the last lis_solve ran no -p ssor, 1 when it ran the point form (CSR storage), bn when it ran the block sweeps on a BSR matrix of
+ * bn x bn blocks.  There lis_amd_last_solve_ssor reports blocks = 1 at every T (the reference's block sweeps are serial) and counts
+ * levels over block rows. */
+LIS_INT lis_amd_last_solve_ssor_block(void);
+/* SSOR schedule of a split CSR matrix -- or split BSR matrix with square blocks of 1 .. 8: block rows and block terms -- with WD at the
+ * current block count: info = {host seconds spent building schedules for A,
+ * bytes one psolve streams (level-ordered layout), launches per psolve, forward levels} (tools/ssor_probe.py, tools/bssor_probe.py) */
 LIS_INT lis_amd_ssor_schedule_info(LIS_MATRIX A, double info[4]);
 /* One sweep of that schedule, read-only: sweep = 0 forward on L, 1 backward on U, 2 forward on U^T, 3 backward on L^T (the two of
  * lis_matrix_solveh); info = {levels, launches, levels on a launch of their own (more than LISHIP_SWEEP_SMALL_LEVEL rows), long rows

@@ -671,6 +671,23 @@ int  liship_bilu_sweep_f64(const liship_sweep_t *sweep, int n, int bn, const dou
 /* dst block p = src block perm[p], blocks of bs doubles: liship_permute_gather_f64 for the values of a block layout */
 int  liship_block_gather_f64(int nblocks, int bs, const int *perm, const double *src, double *dst, void *stream);
 
+/* ------------------------------------------------------------------ block SSOR sweeps (kernels/bsptrsv.hip on kernels/level_schedule.hpp, -p ssor on BSR storage)
+ * One sweep of lis_matrix_solve_bsr / lis_matrix_solveh_bsr over a layout of ceil(n / bn) block rows whose val holds bn*bn doubles per
+ * place in native column-major order; wd: the inverted blocks of omega D, one per block row.  Every scalar row is one ordered chain:
+ *   transposed == 0, LISHIP_SWEEP_MUL   t = b_i; per term, c ascending: t[r] -= a(r,c) x_j[c];  x_i = wd_i t
+ *                    LISHIP_SWEEP_SUB   t = +0.0; t[r] += a(r,c) x_j[c];                        x_i -= wd_i t        (b is not read)
+ *   transposed != 0, LISHIP_SWEEP_MUL   t = b_i; per term: t[c] -= (sum_r a(r,c) x_j[r]);       x_i = wd_i^T t
+ *                    LISHIP_SWEEP_SCAT  t = b_i; per term: t[c] -= (sum_r a(r,c) work_j[r]);    x_i = t, work_i = wd_i^T t
+ * the sums over r and the products with wd_i summed left to right, from the first product for bn <= 3 and from +0.0 for bn >= 4.
+ * b and x read as +0.0 from n on and x is never written there; b may equal x.  work (SCAT, bn >= 2): bn * ceil(n / bn) doubles, all
+ * written.  Any other mode, bn outside 1 .. 8 or a layout of another size: LISHIP_ERR_ARG.  bn = 1: liship_sweep_f64 after this entry's
+ * own argument checks -- the same roundings in the same order.  liship_bsweep_chunk(bn): the terms of a long block row whose products
+ * lie in LDS at once (0: bn is not served; bn = 1: 256, the workgroup of the point sweep's level kernel, whose long rows take a product
+ * per thread). */
+int  liship_bsweep_f64(const liship_sweep_t *sweep, int n, int bn, int mode, int transposed, const double *b, double *x,
+                       const double *wd, double *work, void *stream);
+int  liship_bsweep_chunk(int bn);
+
 /* ------------------------------------------------------------------ block diagonal (kernels/bdiag.hip, -p bjacobi)
  * d: nr = ceil(n / bn) blocks of bn x bn doubles, block b at d[b*bn*bn], entry (i, j) at i + j*bn (LIS_MATRIX_DIAG).
  * inverse: every block replaced by its inverse, by the reference's lis_array_ge (LU without pivoting, no pivot check: 1 / 0 = inf goes on), after the

@@ -263,6 +263,7 @@ _PROTOS = {
 # the SSOR, ILU(k) and block Jacobi extensions of include/lis_amd.h: set where the library has them (liblis_amd.so), absent from the reference build
 _AMD_PROTOS = {
     "lis_amd_last_solve_ssor": (LIS_INT, [P_INT, P_INT, P_INT, P_INT]),
+    "lis_amd_last_solve_ssor_block": (LIS_INT, []),
     "lis_amd_ssor_schedule_info": (LIS_INT, [PM, P_DBL]),
     "lis_amd_ssor_sweep_info": (LIS_INT, [PM, LIS_INT, P_INT]),
     "lis_amd_ssor_psolve_times": (LIS_INT, [PM, PV, PV, LIS_INT, P_DBL]),

@@ -86,6 +86,28 @@ void lisi_bjacobi_wd_free(LIS_PRECON precon)
 	precon->WD = NULL;
 }
 
+/* What lis_matrix_convert_self (ref lis_matrix_ops.c:326-368) makes of A under -storage / -storage_block, shared by the preconditioners
+ * that work on blocks (-p bjacobi, -p ssor): the type, and for BSR the blocks A has, or the ones the conversion makes -- -storage_block b
+ * gives b x b, none the sizes of lis_matrix_set_blocksize; a BSR matrix keeps its blocks whatever -storage_block says.  Nothing is touched. */
+LIS_INT lisi_storage_result(LIS_MATRIX A, LIS_INT storage, LIS_INT block, LIS_INT *bnr, LIS_INT *bnc)
+{
+	const LIS_INT result = storage ? storage : A->matrix_type;
+	*bnr = *bnc = 1;
+	if (result == LIS_MATRIX_BSR) {
+		const int converts = A->matrix_type != LIS_MATRIX_BSR;
+		if (converts && block > 0) *bnr = *bnc = block;
+		else { *bnr = converts ? A->conv_bnr : A->bnr; *bnc = converts ? A->conv_bnc : A->bnc; }
+	}
+	return result;
+}
+
+/* ... and the conversion itself, only when -storage names another type than A has */
+LIS_INT lisi_convert_self(LIS_MATRIX A, LIS_INT result, LIS_INT block)
+{
+	if (result != A->matrix_type) LISCHK(lisi_matrix_retype(A, result, result == LIS_MATRIX_BSR ? block : 0));
+	return LIS_SUCCESS;
+}
+
 LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon)
 {
 	LIS_MATRIX A = solver->A;
@@ -93,23 +115,20 @@ LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon)
 	PPRIV(precon)->from_bjacobi = 1;             /* (stays set when the type below becomes Jacobi: the fallback's mark) */
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisd_init());                         /* no device: the no-device code, before anything that could succeed */
-	const LIS_INT result = storage ? storage : A->matrix_type;       /* what A is after lis_matrix_convert_self */
+	LIS_INT bnr, bnc;
+	const LIS_INT result = lisi_storage_result(A, storage, block, &bnr, &bnc);       /* what A is after lis_matrix_convert_self */
 	/* refusals first: A is left as it was */
 	if (lisg.nprocs > 1) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi is served on one rank only (A is untouched)\n");
 	if (solver->options[LIS_OPTIONS_SCALE] != LIS_SCALE_NONE) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi together with -scale is not served (A is untouched)\n");
 	if (solver->options[LIS_OPTIONS_ADDS]) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi with -adds true is not served (A is untouched)\n");
 	if (result == LIS_MATRIX_VBR) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on VBR storage is not served (A is untouched)\n");
-	if (result == LIS_MATRIX_BSR) {              /* the blocks A has, or the ones the conversion makes: -storage_block b gives b x b, none the sizes of lis_matrix_set_blocksize */
-		const int converts = A->matrix_type != LIS_MATRIX_BSR;
-		const LIS_INT bnr = converts ? A->conv_bnr : A->bnr, bnc = converts ? A->conv_bnc : A->bnc;
-		if (!(converts && block > 0) && bnr != bnc)
-			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on %D x %D blocks is not served: a BSR matrix is split for square blocks only (A is untouched)\n", bnr, bnc);
-	}
+	if (result == LIS_MATRIX_BSR && bnr != bnc)
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on %D x %D blocks is not served: a BSR matrix is split for square blocks only (A is untouched)\n", bnr, bnc);
 	if (result == LIS_MATRIX_BSR && MDEV(A)->device_only)
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on a matrix that lives in HBM only is not served: its split needs the host arrays (A is untouched)\n");
 	if (solver->options[LIS_OPTIONS_SOLVER] == LIS_SOLVER_JACOBI)
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "the Jacobi solver with -p bjacobi (system rescaling) is not served (A is untouched)\n");
-	if (result != A->matrix_type) LISCHK(lisi_matrix_retype(A, result, result == LIS_MATRIX_BSR ? block : 0));      /* lis_matrix_convert_self */
+	LISCHK(lisi_convert_self(A, result, block));
 	if (A->matrix_type != LIS_MATRIX_BSR) {      /* no block matrix: -p jacobi from here on (ref :233-239), lis_precon_create builds D */
 		solver->options[LIS_OPTIONS_PRECON] = LIS_PRECON_TYPE_JACOBI;
 		precon->precon_type = LIS_PRECON_TYPE_JACOBI;

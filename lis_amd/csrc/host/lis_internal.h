@@ -197,6 +197,7 @@ typedef struct {
 	int last_ilu_bn;                                                                                   /* lis_amd_last_solve_ilu_block: the block size of a block ILU, 0 for the point form */
 	int last_bjacobi, last_bjacobi_bn, last_bjacobi_nr, last_bjacobi_fallback;                         /* lis_amd_last_solve_bjacobi */
 	int last_ssor, last_ssor_blocks, last_ssor_levels_fwd, last_ssor_levels_bwd, last_ssor_launches;   /* lis_amd_last_solve_ssor */
+	int last_ssor_bn;                                                                                  /* lis_amd_last_solve_ssor_block: 1 for the point form, bn for block sweeps */
 } lisi_globals;
 extern lisi_globals lisg;
 
@@ -332,12 +333,15 @@ void    lisd_ilu_free(void *ilu);
 LIS_INT lisd_ilu_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);    /* the factor of A for a solve (made now if the HBM copy was rebuilt since create) */
 LIS_INT lisd_ilu_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
 /* ---- SSOR (lis_ssor.c) */
-LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon);             /* -storage csr, split, WD = 1 / (omega D) unless already built */
+#define LISI_SSOR_MAX_BN 8                                                    /* the block sizes kernels/bsptrsv.hip is instantiated for */
+LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon);             /* -storage csr or bsr, split, WD = (omega D)^-1 unless already built */
 void    lisi_ssor_wd_free(LIS_MATRIX A);
 void    lisd_ssor_free(void *ssor);
 LIS_INT lisd_ssor_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);   /* schedules + WD in HBM for a solve */
 LIS_INT lisd_ssor_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
 /* ---- block Jacobi (lis_bjacobi.c) */
+LIS_INT lisi_storage_result(LIS_MATRIX A, LIS_INT storage, LIS_INT block, LIS_INT *bnr, LIS_INT *bnc);   /* type and blocks of A after lis_matrix_convert_self; A untouched */
+LIS_INT lisi_convert_self(LIS_MATRIX A, LIS_INT result, LIS_INT block);     /* lis_matrix_convert_self to that type */
 LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon);          /* refusals, -storage, then Jacobi (precon_type changed) or split + WD inverted on the device */
 void    lisi_bjacobi_wd_free(LIS_PRECON precon);
 void    lisd_bjacobi_free(void *bjacobi);
