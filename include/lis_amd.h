@@ -151,6 +151,32 @@ LIS_INT lis_amd_bjacobi_psolve(LIS_MATRIX A, LIS_INT transposed, LIS_VECTOR B, L
 /* reps inversions of a copy of A's diagonal blocks, reps psolves X = M^-1 B and reps Jacobi psolves X = B .* d of the same length, each timed by device events
  * into inverse_ms[k] / psolve_ms[k] / jacobi_ms[k] (tools/bjacobi_probe.py) */
 LIS_INT lis_amd_bjacobi_times(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *inverse_ms, double *psolve_ms, double *jacobi_ms);
+/* ---- SAINV (-p sainv [-sainv_drop tol]; A in any served storage format, not split, one rank): M^-1 = Z D^-1 W^T, the stabilised approximate inverse of the
+ * reference (lis_precon_sainv.c:122-378).  The factor is built on the HOST from a CSR copy of A (a sequential A-biorthogonalisation whose pattern depends on the
+ * values) and uploaded once to A's HBM copy, where it is dropped with the copy; every application is two launches in HBM (kernels/sainv.hip).
+ * 1 when the last lis_solve ran -p sainv: nnz(W), nnz(Z) and the chunks of the scatter side (1, or T of lis_amd_set_reference_reductions(T)).  0 otherwise, with 0 in
+ * every field; the other lis_amd_last_solve_* answer 0 after a -p sainv or -p is solve */
+LIS_INT lis_amd_last_solve_sainv(LIS_INT *nnz_w, LIS_INT *nnz_z, LIS_INT *blocks);
+/* the factor of A at drop tolerance tol, built now unless A's HBM copy holds it already; sizes = {n, nnz(W), nnz(Z)}, the room lis_amd_sainv_copy needs */
+LIS_INT lis_amd_sainv_factor(LIS_MATRIX A, LIS_REAL tol, LIS_INT sizes[3]);
+/* W and Z as packed row arrays in the reference's stored order (row i starts with its unit diagonal, then the entries in the order the build appended them),
+ * d[i] = 1 / pivot.  Any pointer may be NULL */
+LIS_INT lis_amd_sainv_copy(LIS_MATRIX A, LIS_REAL tol, LIS_INT *wptr, LIS_INT *windex, LIS_SCALAR *wvalue,
+                           LIS_INT *zptr, LIS_INT *zindex, LIS_SCALAR *zvalue, LIS_SCALAR *d);
+/* X = M^-1 B = Z (D^-1 (W^T B)), or with transposed != 0 X = M^-H B = W (D^-1 (Z^T B)); X may be B */
+LIS_INT lis_amd_sainv_psolve(LIS_MATRIX A, LIS_REAL tol, LIS_VECTOR B, LIS_VECTOR X, LIS_INT transposed);
+/* *build_s: host seconds the build of this factor took, by the host clock (a cached factor reports the build that made it); reps psolves X = M^-1 B timed
+ * by device events into psolve_ms[k] (tools/sainv_probe.py); X must not be B */
+LIS_INT lis_amd_sainv_times(LIS_MATRIX A, LIS_REAL tol, LIS_VECTOR B, LIS_VECTOR X, LIS_INT reps, double *build_s, double *psolve_ms);
+/* info = {host seconds of the build, nnz(W), nnz(Z), bytes one psolve streams, launches per psolve, host builds of SAINV factors in this process so far
+ * (it stands still while solves reuse a cached factor)} */
+LIS_INT lis_amd_sainv_info(LIS_MATRIX A, LIS_REAL tol, double info[6]);
+/* ---- I+S (-p is [-is_alpha a] [-is_m m], -is_level != 0; A in CSR storage, one rank): M^-1 = I - a S, S the first m + 1 stored entries of every row of the strict
+ * upper part (lis_precon_is.c:417-547).  lis_precon_create splits A, which stays split.
+ * Y = M^-1 X (transposed != 0: M^-H X) on a split CSR matrix; Y must not be X */
+LIS_INT lis_amd_is_psolve(LIS_MATRIX A, LIS_SCALAR alpha, LIS_INT m, LIS_VECTOR X, LIS_VECTOR Y, LIS_INT transposed);
+/* 1 when the last lis_solve ran -p is, *m = its -is_m; 0 otherwise, with *m = 0 */
+LIS_INT lis_amd_last_solve_is(LIS_INT *m);
 
 /* vectors */
 LIS_INT lis_amd_vector_sync_host(LIS_VECTOR v);        /* make v->value[] current (D2H if needed)        */

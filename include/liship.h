@@ -564,6 +564,20 @@ int  liship_spmv_csr_transposed_chunked_unordered_f64(int rows, int nsrc, int T,
                                                       const double *x, double *y, void *stream);
 int  liship_csr_transpose_f64(int nrows, int ncols, int nnz, const int *ptr, const int *index, const double *value,
                               int *tptr, int *tindex, double *tvalue, int *work, void *stream);
+/* ---- preconditioners applied as products (kernels/sainv.hip): row sums over a packed CSR {ptr, idx, val}, each sum formed from +0.0 in STORED
+ * order by one lane whatever the row's length, the epilogue in the same kernel.  The transposed forms (liship_csr_transpose_f64: terms by source
+ * row) are summed in T chunks of the nsrc source rows, LIS_GET_ISIE(k, T, nsrc), the chunk sums added in chunk order from +0.0 (T <= 1: one chain).
+ *   sainv_gather_scale  t[r] = (row r . b) * d[r]                      lis_matvech_ilu + the scale loop of lis_psolve_sainv (lis_precon_sainv.c:763-770)
+ *   sainv_rows          x[c] = sum of row c of the transposed form . t    lis_matvec_ilu's scatter (lis_matrix_ilu.c:418-436)
+ *   is_psolve           y[r] = x[r] - alpha * (row r . x)              lis_psolve_is (lis_precon_is.c:449-458); y must not be x
+ *   is_psolveh          y[c] = x[c] - sum of row c of the transposed form . x, tval = alpha * u    lis_psolveh_is (:505-524); y must not be x
+ *   is_truncate         the first min(keep, length) entries of every row of {uptr, uidx, uval} packed at the row starts tptr: tidx, tval, and taval = alpha * value */
+int  liship_sainv_gather_scale_f64(int n, const int *ptr, const int *idx, const double *val, const double *d, const double *b, double *t, void *stream);
+int  liship_sainv_rows_f64(int n, int nsrc, int T, const int *tptr, const int *tidx, const double *tval, const double *t, double *x, void *stream);
+int  liship_is_psolve_f64(int n, const int *ptr, const int *idx, const double *val, double alpha, const double *x, double *y, void *stream);
+int  liship_is_psolveh_f64(int n, int nsrc, int T, const int *tptr, const int *tidx, const double *tval, const double *x, double *y, void *stream);
+int  liship_is_truncate_f64(int n, int keep, const int *uptr, const int *uidx, const double *uval, const int *tptr, double alpha,
+                            int *tidx, double *tval, double *taval, void *stream);
 /* ---- storage-format conversions of a CSR matrix that lives in HBM (kernels/convert.hip): the arrays the reference's host routines
  * build (src/matrix/lis_matrix_ell.c:958-1070, lis_matrix_dia.c:1191-1304, lis_matrix_bsr.c:351-552), bit for bit, from device arrays.
  * liship_csr_row_facts: facts[0] = longest row, facts[1] = 1 when some row is not in ascending column order (two device ints).

@@ -214,6 +214,11 @@ _LISHIP = {
     "liship_poisson3d_rhs": (_ci, [_ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "liship_bdiag_inverse_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp]),
     "liship_bdiag_matvec_f64": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "liship_sainv_gather_scale_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_sainv_rows_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_is_psolve_f64": (_ci, [_ci, _vp, _vp, _vp, _cd, _vp, _vp, _vp]),
+    "liship_is_psolveh_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_is_truncate_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _cd, _vp, _vp, _vp, _vp]),
 }
 
 

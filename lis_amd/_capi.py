@@ -279,6 +279,14 @@ _AMD_PROTOS = {
     "lis_amd_bjacobi_copy": (LIS_INT, [PM, P_DBL]),
     "lis_amd_bjacobi_psolve": (LIS_INT, [PM, LIS_INT, PV, PV]),
     "lis_amd_bjacobi_times": (LIS_INT, [PM, PV, PV, LIS_INT, P_DBL, P_DBL, P_DBL]),
+    "lis_amd_last_solve_sainv": (LIS_INT, [P_INT, P_INT, P_INT]),
+    "lis_amd_sainv_factor": (LIS_INT, [PM, C.c_double, P_INT]),
+    "lis_amd_sainv_copy": (LIS_INT, [PM, C.c_double, P_INT, P_INT, P_DBL, P_INT, P_INT, P_DBL, P_DBL]),
+    "lis_amd_sainv_psolve": (LIS_INT, [PM, C.c_double, PV, PV, LIS_INT]),
+    "lis_amd_sainv_times": (LIS_INT, [PM, C.c_double, PV, PV, LIS_INT, P_DBL, P_DBL]),
+    "lis_amd_sainv_info": (LIS_INT, [PM, C.c_double, P_DBL]),
+    "lis_amd_is_psolve": (LIS_INT, [PM, C.c_double, LIS_INT, PV, PV, LIS_INT]),
+    "lis_amd_last_solve_is": (LIS_INT, [P_INT]),
 }
 
 

@@ -99,6 +99,8 @@ typedef struct {
 	void *ssor;                /* SSOR schedules of the split parts + WD in HBM (lis_ssor.c), dropped with the copy */
 	void *ilu;                 /* ILU(k): symbolic pattern, schedule, sweep layouts and factor in HBM (lis_ilu.c), dropped with the copy */
 	void *bjacobi;             /* block Jacobi: the inverted diagonal blocks of a split BSR matrix in HBM (lis_bjacobi.c), dropped with the copy */
+	void *sainv;               /* SAINV: W, Z, their transposed row forms and d in HBM, built on the host (lis_sainv.c), dropped with the copy */
+	void *is;                  /* I+S: the truncated rows of U and their transposed form in HBM (lis_is.c), dropped with the copy */
 } lisd_mat;
 
 typedef struct {
@@ -120,6 +122,7 @@ typedef struct {
 	int n;
 	int fill, T;               /* ILU: the fill level; SSOR / ILU: the row blocks of the sweeps */
 	double *dinv;              /* Jacobi: 1/diag in HBM, in the numbering the solve runs in */
+	double param; int m;       /* SAINV: the drop tolerance (T: the chunks of the scatter side); I+S: alpha and -is_m */
 } lisi_precon_state;
 
 /* One row per served LIS_PRECON_TYPE_*; a pointer that may be NULL is a step the kind does not have.
@@ -127,7 +130,7 @@ typedef struct {
  *            blocks becomes Jacobi), and lis_precon_create then runs the new type's create
  *   begin    once per solve (lis_solve_kernel): fills the state, makes what a rebuilt HBM copy lost, records lisg.last_*
  *   apply    z = M^-1 r, or M^-H r (transposed).  none: a copy; Jacobi: liship_pmul_f64; SSOR, ILU: the sweeps, r may be z;
- *            block Jacobi: r must NOT be z.  Nothing is looked up or checked per call beyond what the kind's file says
+ *            block Jacobi and I+S: r must NOT be z; SAINV: two products with a work vector between them, r may be z.  Nothing is looked up or checked per call beyond what the kind's file says
  *   by_calls no point diagonal: the fused and device-driven loops (which fold z = r .* dinv into their passes) do not apply, and
  *            the solve never runs renumbered (the sweeps follow the rows' order, the blocks the caller's rows)
  *   the frees: the cache on the HBM copy (the slot of lisd_mat at cache_slot), what the matrix and what the precon own on the host */
@@ -141,7 +144,7 @@ typedef struct {
 	void (*matrix_free)(LIS_MATRIX A);
 	void (*precon_free)(LIS_PRECON precon);
 } lisi_precon_kind;
-#define LISI_PRECON_KINDS 5                                                    /* none, jacobi, ilu, ssor, bjacobi */
+#define LISI_PRECON_KINDS 7                                                    /* none, jacobi, ilu, ssor, bjacobi, sainv, is */
 extern const lisi_precon_kind lisi_precon_kinds[LISI_PRECON_KINDS];           /* lis_solver.c */
 const lisi_precon_kind *lisi_precon_kind_of(LIS_INT type);                    /* NULL: not served */
 void lisi_precon_release(lisd_mat *d, LIS_MATRIX A, LIS_PRECON precon);       /* every kind's frees for the arguments that are not NULL */
@@ -198,6 +201,9 @@ typedef struct {
 	int last_bjacobi, last_bjacobi_bn, last_bjacobi_nr, last_bjacobi_fallback;                         /* lis_amd_last_solve_bjacobi */
 	int last_ssor, last_ssor_blocks, last_ssor_levels_fwd, last_ssor_levels_bwd, last_ssor_launches;   /* lis_amd_last_solve_ssor */
 	int last_ssor_bn;                                                                                  /* lis_amd_last_solve_ssor_block: 1 for the point form, bn for block sweeps */
+	int last_sainv, last_sainv_wnnz, last_sainv_znnz, last_sainv_blocks;                               /* lis_amd_last_solve_sainv */
+	int last_is, last_is_m;                                                                            /* lis_amd_last_solve_is */
+	long long sainv_builds;                                                                            /* host builds of a SAINV factor since lis_initialize (lis_amd_sainv_info) */
 } lisi_globals;
 extern lisi_globals lisg;
 
@@ -347,6 +353,17 @@ void    lisi_bjacobi_wd_free(LIS_PRECON precon);
 void    lisd_bjacobi_free(void *bjacobi);
 LIS_INT lisd_bjacobi_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);   /* the inverse of A's diagonal blocks for a solve (made now if the HBM copy was rebuilt since create) */
 LIS_INT lisd_bjacobi_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
+/* ---- SAINV (lis_sainv.c) */
+LIS_INT lisi_sainv_create(LIS_SOLVER solver, LIS_PRECON precon);            /* refusals, the factor built on the host from a CSR copy of A, uploaded once */
+void    lisd_sainv_free(void *sainv);
+LIS_INT lisd_sainv_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);  /* the factor of A for a solve (built now if the HBM copy was rebuilt since create) */
+LIS_INT lisd_sainv_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
+LIS_INT lisd_rows_transposed(int n, int nnz, const int *dptr, const int *didx, const double *dval, int **tptr, int **tidx, double **tval);   /* fresh HBM arrays: the transposed row form, terms by source row */
+/* ---- I+S (lis_is.c) */
+LIS_INT lisi_is_create(LIS_SOLVER solver, LIS_PRECON precon);               /* refusals, then split A (A stays split) and the truncated rows in HBM */
+void    lisd_is_free(void *is);
+LIS_INT lisd_is_begin(LIS_MATRIX A, LIS_SOLVER solver, lisi_precon_state *st);
+LIS_INT lisd_is_apply(const lisi_precon_state *st, int transposed, const double *b, double *x);
 #define LISI_CHECK_NULL 0
 #define LISI_CHECK_SIZE 1
 #define LISI_CHECK_ASSEMBLED 2

@@ -254,6 +254,10 @@ const lisi_precon_kind lisi_precon_kinds[LISI_PRECON_KINDS] = {
 	{ LIS_PRECON_TYPE_SSOR,    1, lisi_ssor_create,    lisd_ssor_begin,    lisd_ssor_apply,    offsetof(lisd_mat, ssor), lisd_ssor_free, lisi_ssor_wd_free, NULL },
 	/* -storage, then split A + WD = D^-1 block by block on the precon; a matrix without blocks turns p into a Jacobi preconditioner: lis_bjacobi.c */
 	{ LIS_PRECON_TYPE_BJACOBI, 1, lisi_bjacobi_create, lisd_bjacobi_begin, lisd_bjacobi_apply, offsetof(lisd_mat, bjacobi), lisd_bjacobi_free, NULL, lisi_bjacobi_wd_free },
+	/* W, Z, d built on the host from a CSR copy of A, applied as two products in HBM: lis_sainv.c (the precon owns nothing, L / U / D / temp stay NULL) */
+	{ LIS_PRECON_TYPE_SAI,     1, lisi_sainv_create,   lisd_sainv_begin,   lisd_sainv_apply,   offsetof(lisd_mat, sainv), lisd_sainv_free, NULL, NULL },
+	/* split CSR A (A stays split), the first m + 1 entries of U's rows and their transposed form in HBM: lis_is.c */
+	{ LIS_PRECON_TYPE_IS,      1, lisi_is_create,      lisd_is_begin,      lisd_is_apply,      offsetof(lisd_mat, is), lisd_is_free, NULL, NULL },
 };
 
 const lisi_precon_kind *lisi_precon_kind_of(LIS_INT type)
@@ -276,7 +280,7 @@ LIS_INT lis_precon_create(LIS_SOLVER solver, LIS_PRECON *precon)
 	const LIS_INT type = solver->options[LIS_OPTIONS_PRECON];
 	const lisi_precon_kind *k = lisi_precon_kind_of(type);
 	*precon = NULL;
-	if (!k) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ilu, ssor, bjacobi)\n", type);
+	if (!k) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "preconditioner %D is not served by liblis_amd (none, jacobi, ilu, ssor, bjacobi, sainv, is)\n", type);
 	LIS_PRECON p = (LIS_PRECON)calloc(1, sizeof(lisi_precon));
 	if (!p) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(lisi_precon));
 	p->precon_type = type;
@@ -978,7 +982,11 @@ static LIS_INT scale_system(LIS_MATRIX A, LIS_VECTOR b, LIS_SOLVER solver, LIS_I
 	const LIS_INT nsolver = solver->options[LIS_OPTIONS_SOLVER], blk = solver->options[LIS_OPTIONS_STORAGE_BLOCK];
 	LIS_INT scale = solver->options[LIS_OPTIONS_SCALE], err = 0;
 	*scale_out = 0;
-	if (scale == LIS_SCALE_JACOBI && solver->options[LIS_OPTIONS_STORAGE] == LIS_MATRIX_BSR) {
+	/* -p is works on the row-scaled system, whose diagonal is 1 (ref :613-636): A -- split by lis_precon_create, the parts are scaled -- and b are multiplied by
+	 * 1 / diag and stay so, whatever the solver (CG does not turn this scaling into the symmetric one); -scale itself is refused with -p is (lis_is.c) */
+	const int is_rows = solver->options[LIS_OPTIONS_PRECON] == LIS_PRECON_TYPE_IS;
+	if (is_rows) scale = LIS_SCALE_JACOBI;
+	if (!is_rows && scale == LIS_SCALE_JACOBI && solver->options[LIS_OPTIONS_STORAGE] == LIS_MATRIX_BSR) {
 		/* block-diagonal scaling: A becomes BSR, is split and multiplied by the inverse diagonal blocks, b likewise; the iterations then run on
 		 * the split product (ref :659-690).  Feasibility BEFORE A and b are touched: the solvers that multiply by A^T need the transposed split
 		 * product, which lisd_mat_ready_t serves for square blocks only (lis_matvech.c) -- a refusal after the retype / split / scaling would
@@ -991,7 +999,7 @@ static LIS_INT scale_system(LIS_MATRIX A, LIS_VECTOR b, LIS_SOLVER solver, LIS_I
 	}
 	if (!scale) return LIS_SUCCESS;
 	if (!solver->d) LISCHK(lis_vector_duplicate(A, &solver->d));
-	if (scale == LIS_SCALE_JACOBI && nsolver == LIS_SOLVER_CG) scale = LIS_SCALE_SYMM_DIAG;
+	if (scale == LIS_SCALE_JACOBI && nsolver == LIS_SOLVER_CG && !is_rows) scale = LIS_SCALE_SYMM_DIAG;
 	*scale_out = scale;
 	if (!A->is_scaled) return lis_matrix_scale(A, b, solver->d, scale);
 	if (!b->is_scaled) {
@@ -1120,7 +1128,7 @@ static LIS_INT precon_begin(ctx_t *c, LIS_PRECON precon, renumber_t *rn)
 	lisg.last_uniform_jacobi = 0;
 	lisg.last_graph_replays = 0;
 	lisg.last_renumbered = rn->on;
-	lisg.last_ssor = lisg.last_ilu = lisg.last_bjacobi = 0;
+	lisg.last_ssor = lisg.last_ilu = lisg.last_bjacobi = lisg.last_sainv = lisg.last_is = 0;
 	lisg.last_bjacobi_fallback = precon && lisi_is_registered(precon) && PPRIV(precon)->from_bjacobi && precon->precon_type == LIS_PRECON_TYPE_JACOBI;
 	LISCHK(c->pk->begin(c->A, c->s, &c->ps));
 	if (c->pk->type != LIS_PRECON_TYPE_JACOBI) return LIS_SUCCESS;
