@@ -125,7 +125,7 @@ typedef LIS_INT      LIS_Comm;         /* ref:485 */
 #define LIS_EPRINT_OUT 2              /* ref:148 */
 #define LIS_EPRINT_ALL 3              /* ref:149 */
 
-/* eigensolver ids, ref:188-204 (served: PI, II, RQI, CG, CR) */
+/* eigensolver ids, ref:188-204 (served: PI, II, RQI, CG, CR; SI, LI, AI with -ss >= 2) */
 #define LIS_ESOLVER_LEN 16            /* ref:188 */
 #define LIS_ESOLVER_PI 1              /* ref:189 */
 #define LIS_ESOLVER_II 2              /* ref:190 */
@@ -637,9 +637,14 @@ LIS_INT lis_precon_destroy(LIS_PRECON precon);
 LIS_INT lis_solver_get_solvername(LIS_INT solver, char *solvername);
 LIS_INT lis_solver_get_preconname(LIS_INT precon_type, char *preconname);
 LIS_INT lis_solver_output_rhistory(LIS_SOLVER solver, char *filename);  /* ref:1022, src/system/lis_output.c:586 */
-/* ---- eigensolvers, ref:990-1013, 1026 (src/esolver/lis_esolver.c, _pi.c, _ii.c, _rqi.c, _cg.c) ----------------
- * Served: one eigenpair by power (-e pi), inverse (-e ii), Rayleigh quotient (-e rqi), CG (-e cg) and CR (-e cr, the default) iteration, on one rank,
- * in double precision.  -e si | li | ai, the generalized solvers (and lis_gesolve with a B), and the getters only those fill answer
+/* ---- small dense routines of the Lanczos and Arnoldi eigensolvers, ref:943, 953, 955 (src/array/lis_array.c): host arrays, column-major n x n, no device */
+LIS_INT lis_array_nrm2(LIS_INT n, LIS_SCALAR *x, LIS_REAL *value);
+LIS_INT lis_array_cgs(LIS_INT n, LIS_SCALAR *a, LIS_SCALAR *q, LIS_SCALAR *r);       /* classical Gram-Schmidt A = Q R; stops at a column shorter than 1e-12 */
+LIS_INT lis_array_qr(LIS_INT n, LIS_SCALAR *a, LIS_SCALAR *q, LIS_SCALAR *r, LIS_INT *qriter, LIS_REAL *qrerr);   /* A <- R Q until |a[1]| < 1e-12, 100000 sweeps at most */
+/* ---- eigensolvers, ref:990-1013, 1026 (src/esolver/lis_esolver.c, _pi.c, _ii.c, _rqi.c, _cg.c, _si.c, _li.c, _ai.c) ----------------
+ * Served, on one rank, in double precision: one eigenpair by power (-e pi), inverse (-e ii), Rayleigh quotient (-e rqi), CG (-e cg) and CR (-e cr, the default)
+ * iteration; -ss >= 2 eigenpairs by subspace (-e si, -ie pi | ii), Lanczos (-e li) and Arnoldi (-e ai) iteration, with the getters of several pairs.
+ * -e si | li | ai with -ss 1 (the default: one pair is what -e pi / -e ii serve), the generalized solvers (and lis_gesolve with a B) answer
  * LIS_ERR_NOT_IMPLEMENTED before A or x is touched.  -estorage converts A for good, as -storage does in lis_solve. */
 LIS_INT lis_esolver_create(LIS_ESOLVER *esolver);                        /* ref:990 */
 LIS_INT lis_esolver_destroy(LIS_ESOLVER esolver);                        /* ref:991 */
@@ -655,13 +660,13 @@ LIS_INT lis_esolver_get_residualnorm(LIS_ESOLVER esolver, LIS_REAL *residual);  
 LIS_INT lis_esolver_get_status(LIS_ESOLVER esolver, LIS_INT *status);    /* ref:1002 */
 LIS_INT lis_esolver_get_rhistory(LIS_ESOLVER esolver, LIS_VECTOR v);     /* ref:1003 */
 LIS_INT lis_esolver_get_evalues(LIS_ESOLVER esolver, LIS_VECTOR v);      /* ref:1004; as there LIS_ERR_ILL_ARG unless -e is a subspace / Lanczos / Arnoldi solver */
-LIS_INT lis_esolver_get_specific_evalue(LIS_ESOLVER esolver, LIS_INT mode, LIS_SCALAR *evalue);      /* ref:1005; refused */
-LIS_INT lis_esolver_get_evectors(LIS_ESOLVER esolver, LIS_MATRIX M);     /* ref:1006; refused */
-LIS_INT lis_esolver_get_specific_evector(LIS_ESOLVER esolver, LIS_INT mode, LIS_VECTOR x);           /* ref:1007; refused */
+LIS_INT lis_esolver_get_specific_evalue(LIS_ESOLVER esolver, LIS_INT mode, LIS_SCALAR *evalue);      /* ref:1005 */
+LIS_INT lis_esolver_get_evectors(LIS_ESOLVER esolver, LIS_MATRIX M);     /* ref:1006; M is assembled as CSR (COO there) */
+LIS_INT lis_esolver_get_specific_evector(LIS_ESOLVER esolver, LIS_INT mode, LIS_VECTOR x);           /* ref:1007 */
 LIS_INT lis_esolver_get_residualnorms(LIS_ESOLVER esolver, LIS_VECTOR v);                            /* ref:1008; as get_evalues */
-LIS_INT lis_esolver_get_specific_residualnorm(LIS_ESOLVER esolver, LIS_INT mode, LIS_REAL *residual); /* ref:1009; refused */
+LIS_INT lis_esolver_get_specific_residualnorm(LIS_ESOLVER esolver, LIS_INT mode, LIS_REAL *residual); /* ref:1009 */
 LIS_INT lis_esolver_get_iters(LIS_ESOLVER esolver, LIS_VECTOR v);        /* ref:1010; as get_evalues */
-LIS_INT lis_esolver_get_specific_iter(LIS_ESOLVER esolver, LIS_INT mode, LIS_INT *iter);             /* ref:1011; refused */
+LIS_INT lis_esolver_get_specific_iter(LIS_ESOLVER esolver, LIS_INT mode, LIS_INT *iter);             /* ref:1011 */
 LIS_INT lis_esolver_get_esolver(LIS_ESOLVER esolver, LIS_INT *nesol);    /* ref:1012 */
 LIS_INT lis_esolver_get_esolvername(LIS_INT esolver, char *esolvername); /* ref:1013 */
 LIS_INT lis_esolver_output_rhistory(LIS_ESOLVER esolver, char *filename); /* ref:1026, src/system/lis_output.c:659 */

@@ -419,6 +419,15 @@ int  liship_mgs_step_f64(int n, const double *hprev, const double *vprev, double
 #define LISHIP_MULTIDOT_MAX_VECS 8
 #define LISHIP_MULTIDOT_MAX_PAIRS 36
 int  liship_multidot_f64(int n, int nvec, const double *const *vecs, int K, const int (*pairs)[2], double *result, void *work, void *stream);
+/* The tail of one subspace iteration (-e si, lis_esolver_si.c:301-311) in ONE pass over r and v.  sums (HBM) = {sum r^2, theta = <v,r>}, as one
+ * liship_multidot_f64 pass over {r, v} with the pairs (r, r), (v, r) leaves them.  Per element, in this order, each product and each sum rounded once:
+ *   q = (-theta) * v[i] + r[i]  (lis_vector_axpyz; q is not stored), q * q enters the reduction;
+ *   s = (1.0 / sqrt(sums[0])) * r[i]  (lis_vector_scale; the reciprocal formed once per lane from the HBM value, as liship_scale_inv_norm_f64);  r[i] = s; v[i] = s.
+ * result[0] = sum q^2, formed EXACTLY as liship_sumsq_f64 forms it on a 16 B aligned array of n elements: the tree above on the same grid, or the T chunks
+ * of liship_set_reference_reductions(T).  So the six calls nrm2, dot, axpyz, nrm2, scale, copy and {multidot, this} give the same bits (11 against 6
+ * n-vector streams).  r and v must be 16 B aligned and must not overlap (one array given twice included): LISHIP_ERR_ARG otherwise and for n <= 0, with
+ * nothing launched.  sums and result must not overlap either.  A pending liship_krylov_chain step rides in the fold, as in liship_sumsq_f64. */
+int  liship_ritz_tail_f64(int n, const double *sums, double *r, double *v, double *result, void *work, void *stream);
 /* value[k] -= sigma for the FIRST stored entry k of each row whose column is the row; a row without one is left alone (lis_matrix_shift_diagonal_csr,
  * src/matrix/lis_matrix_csr.c:566-603, on arrays in HBM; a split matrix's chain rows start with their diagonal term, host/lis_split.c) */
 int  liship_csr_shift_diagonal_f64(int n, const int *ptr, const int *index, double *value, double sigma, void *stream);

@@ -196,6 +196,7 @@ _LISHIP = {
     "liship_sum_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_dot2_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
     "liship_multidot_f64": (_ci, [_ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "liship_ritz_tail_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_csr_shift_diagonal_f64": (_ci, [_ci, _vp, _vp, _vp, _cd, _vp]),
     "liship_csr_diagonal_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
     "liship_ell_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),

@@ -254,6 +254,10 @@ _PROTOS = {
     "lis_esolver_get_esolvername": (LIS_INT, [LIS_INT, C.c_char_p]),
     "lis_esolver_output_rhistory": (LIS_INT, [PE, C.c_char_p]),
     "lis_matrix_shift_diagonal": (LIS_INT, [PM, LIS_SCALAR]),
+    # small dense routines of the Lanczos / Arnoldi eigensolvers (lis.h:943, 953, 955)
+    "lis_array_nrm2": (LIS_INT, [LIS_INT, P_DBL, P_DBL]),
+    "lis_array_cgs": (LIS_INT, [LIS_INT, P_DBL, P_DBL, P_DBL]),
+    "lis_array_qr": (LIS_INT, [LIS_INT, P_DBL, P_DBL, P_DBL, P_INT, P_DBL]),
     # memory (lis.h:1037-1042)
     "lis_malloc": (C.c_void_p, [C.c_size_t, C.c_char_p]),
     "lis_free": (None, [C.c_void_p]),

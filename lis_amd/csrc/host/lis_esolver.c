@@ -9,8 +9,12 @@
  * The Gram blocks of CG (12 inner products over 6 vectors) and CR (5 over 3, 4 over 4) are taken in one pass each by lisd_multidot -- the bits of the
  * separate dots, which LIS_AMD_NO_FUSION=1 / lis_amd_set_loop_mode(LIS_AMD_LOOP_UNFUSED) brings back (the inner solves keep the default loop form: inner_solve).
  *
- * Refused, with LIS_ERR_NOT_IMPLEMENTED and before A or x is touched: the subspace, Lanczos and Arnoldi solvers (-e si | li | ai), every generalized solver
- * (-e gpi .. gai, lis_gesolve with a B), a job of several ranks, and the getters only those solvers fill (lis_esolver_get_evectors, lis_esolver_get_specific_*).
+ * Served as well: several eigenpairs per solve -- subspace (-e si, -ie pi | ii), Lanczos (-e li) and Arnoldi (-e ai) iteration with -ss >= 2 (lis_esolver_si.c,
+ * _li.c, _ai.c), the getters only they fill, and the small dense QR they call (lis_array.c).  Their device chains and the fused tail of a subspace iteration
+ * (liship_ritz_tail_f64) stand in the section "several eigenpairs per solve" below.
+ *
+ * Refused, with LIS_ERR_NOT_IMPLEMENTED and before A or x is touched: -e si | li | ai with -ss 1 (the default: one pair is what -e pi / -e ii serve), -e si with
+ * an -ie other than pi or ii, every generalized solver (-e gpi .. gai, lis_gesolve with a B), a job of several ranks.
  * -ef quad | switch answers as lis_solve does for -f quad.
  *
  * Deliberate differences from the reference, all outside a converging solve: the arrays of the object start zeroed instead of holding heap contents; a
@@ -19,6 +23,7 @@
  */
 #include <stdio.h>
 #include <ctype.h>
+#include <stdint.h>
 #include "lis_internal.h"
 
 static const char *esolver_keys[] = {"pi", "ii", "rqi", "cg", "cr", "si", "li", "ai", "gpi", "gii", "grqi", "gcg", "gcr", "gsi", "gli", "gai"};   /* ref lis_esolver.c:118 */
@@ -71,11 +76,22 @@ static void work_destroy(LIS_ESOLVER e)
 	}
 }
 
+static int is_multi(LIS_INT nesolver) { return nesolver == LIS_ESOLVER_SI || nesolver == LIS_ESOLVER_LI || nesolver == LIS_ESOLVER_AI; }
+static int is_multi_or_generalized(LIS_INT nesolver) { return is_multi(nesolver) || nesolver == LIS_ESOLVER_GSI || nesolver == LIS_ESOLVER_GLI || nesolver == LIS_ESOLVER_GAI; }
+
+/* the arrays of the object and the eigenvectors an earlier solve left: evector has two slots more than vectors and is filled from slot 0, so the first NULL ends them */
+static void arrays_free(LIS_ESOLVER e)
+{
+	if (e->evector) for (LIS_INT i = 0; e->evector[i]; i++) lis_vector_destroy(e->evector[i]);
+	free(e->rhistory); free(e->evalue); free(e->resid); free(e->iter); free(e->iter2); free(e->evector);
+	e->rhistory = NULL; e->evalue = NULL; e->resid = NULL; e->iter = NULL; e->iter2 = NULL; e->evector = NULL;
+}
+
 LIS_INT lis_esolver_destroy(LIS_ESOLVER e)
-{	/* ref :231-259 (evector holds vectors for the subspace solvers only: not served) */
+{	/* ref :231-259 */
 	if (e) {
 		work_destroy(e);
-		free(e->rhistory); free(e->evalue); free(e->resid); free(e->iter); free(e->iter2); free(e->evector);
+		arrays_free(e);
 		free(e);
 	}
 	return LIS_SUCCESS;
@@ -197,18 +213,27 @@ LIS_INT lis_esolver_output_rhistory(LIS_ESOLVER e, char *filename)
 	return LIS_SUCCESS;
 }
 
-/* what the subspace, Lanczos and Arnoldi solvers fill.  The reference answers LIS_ERR_ILL_ARG for any other solver (:1159-1163 and alike); none of
- * those that could ask is served, and the answer says so */
+/* what the subspace, Lanczos and Arnoldi solvers fill (ref :1153-1355).  On an esolver whose -e names none of them (nor a generalized form) the three that fill
+ * a vector answer LIS_ERR_ILL_ARG as the reference does (:1159-1163) and the others say that they belong to those solvers; on one that names such a solver but
+ * holds no ended solve -- never run, refused, failed -- every getter answers LIS_ERR_ILL_ARG */
 static LIS_INT subspace_only(const char *what)
 {
-	return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "%s is filled by the subspace, Lanczos and Arnoldi eigensolvers only, which liblis_amd does not serve\n", what);
+	return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "%s is filled by the subspace, Lanczos and Arnoldi eigensolvers only (-e si | li | ai)\n", what);
 }
-/* the three that copy the object's arrays of ss entries into a vector (ref :1153-1179, :1261-1287, :1309-1337): as there, LIS_ERR_ILL_ARG unless
- * -e names a subspace, Lanczos or Arnoldi solver -- and those never ran here, so there is nothing to copy for them either */
+static LIS_INT multi_filled(LIS_ESOLVER e, const char *what, LIS_INT mode, int vectors)
+{
+	const LIS_INT nesolver = e->options[LIS_EOPTIONS_ESOLVER], ss = e->options[LIS_EOPTIONS_SUBSPACE];
+	if (!is_multi_or_generalized(nesolver)) return subspace_only(what);
+	if (!e->evalue || !e->resid || !e->iter || !e->evector) return LISI_ERR(LIS_ERR_ILL_ARG, "%s: no eigensolve has filled the esolver\n", what);
+	if (mode < 0 || mode >= ss) return LISI_ERR(LIS_ERR_ILL_ARG, "%s: mode %D is outside the subspace of %D\n", what, mode, ss);
+	if (vectors) for (LIS_INT i = 0; i <= mode; i++) if (!e->evector[i]) return LISI_ERR(LIS_ERR_ILL_ARG, "%s: the solve left no eigenvector %D (-rval true computes Ritz values only)\n", what, i);
+	return LIS_SUCCESS;
+}
+/* the three that copy the object's arrays of ss entries into a vector (ref :1153-1179, :1261-1287, :1309-1337) */
 static LIS_INT per_mode(LIS_ESOLVER e, LIS_VECTOR v, int what)
 {
 	const LIS_INT nesolver = e->options[LIS_EOPTIONS_ESOLVER];
-	if (nesolver != LIS_ESOLVER_SI && nesolver != LIS_ESOLVER_LI && nesolver != LIS_ESOLVER_AI && nesolver != LIS_ESOLVER_GSI && nesolver != LIS_ESOLVER_GLI && nesolver != LIS_ESOLVER_GAI)
+	if (!is_multi_or_generalized(nesolver))
 		return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_ESOLVER is %D (Set Subspace, Lanczos, Arnoldi, Generalized Subspace, Generalized Lanczos, or Generalized Arnoldi)\n", nesolver);
 	if (!e->evalue || !e->resid || !e->iter) return LISI_ERR(LIS_ERR_ILL_ARG, "no eigensolve has filled the esolver\n");
 	const LIS_INT ss = e->options[LIS_EOPTIONS_SUBSPACE];
@@ -226,11 +251,37 @@ static LIS_INT per_mode(LIS_ESOLVER e, LIS_VECTOR v, int what)
 LIS_INT lis_esolver_get_evalues(LIS_ESOLVER e, LIS_VECTOR v) { return per_mode(e, v, 0); }
 LIS_INT lis_esolver_get_residualnorms(LIS_ESOLVER e, LIS_VECTOR v) { return per_mode(e, v, 1); }
 LIS_INT lis_esolver_get_iters(LIS_ESOLVER e, LIS_VECTOR v) { return per_mode(e, v, 2); }
-LIS_INT lis_esolver_get_evectors(LIS_ESOLVER e, LIS_MATRIX M) { (void)e; (void)M; return subspace_only("lis_esolver_get_evectors"); }
-LIS_INT lis_esolver_get_specific_evalue(LIS_ESOLVER e, LIS_INT mode, LIS_SCALAR *evalue) { (void)e; (void)mode; (void)evalue; return subspace_only("lis_esolver_get_specific_evalue"); }
-LIS_INT lis_esolver_get_specific_evector(LIS_ESOLVER e, LIS_INT mode, LIS_VECTOR x) { (void)e; (void)mode; (void)x; return subspace_only("lis_esolver_get_specific_evector"); }
-LIS_INT lis_esolver_get_specific_residualnorm(LIS_ESOLVER e, LIS_INT mode, LIS_REAL *residual) { (void)e; (void)mode; (void)residual; return subspace_only("lis_esolver_get_specific_residualnorm"); }
-LIS_INT lis_esolver_get_specific_iter(LIS_ESOLVER e, LIS_INT mode, LIS_INT *iter) { (void)e; (void)mode; (void)iter; return subspace_only("lis_esolver_get_specific_iter"); }
+LIS_INT lis_esolver_get_specific_evalue(LIS_ESOLVER e, LIS_INT mode, LIS_SCALAR *evalue)
+{ LISCHK(multi_filled(e, "lis_esolver_get_specific_evalue", mode, 0)); *evalue = e->evalue[mode]; return LIS_SUCCESS; }
+LIS_INT lis_esolver_get_specific_residualnorm(LIS_ESOLVER e, LIS_INT mode, LIS_REAL *residual)
+{ LISCHK(multi_filled(e, "lis_esolver_get_specific_residualnorm", mode, 0)); *residual = e->resid[mode]; return LIS_SUCCESS; }
+LIS_INT lis_esolver_get_specific_iter(LIS_ESOLVER e, LIS_INT mode, LIS_INT *iter)
+{ LISCHK(multi_filled(e, "lis_esolver_get_specific_iter", mode, 0)); *iter = e->iter[mode]; return LIS_SUCCESS; }
+LIS_INT lis_esolver_get_specific_evector(LIS_ESOLVER e, LIS_INT mode, LIS_VECTOR x)
+{ LISCHK(multi_filled(e, "lis_esolver_get_specific_evector", mode, 1)); return lis_vector_copy(e->evector[mode], x); }
+
+/* ref :1201-1239: M sized gn x gn, column j = eigenvector j, every entry set (zeros included), then type and assemble.  The reference makes M a COO matrix;
+ * COO is not a storage liblis_amd serves, so M is assembled as CSR -- the same entries in the same order, row by row.  Each vector comes home from HBM once */
+LIS_INT lis_esolver_get_evectors(LIS_ESOLVER e, LIS_MATRIX M)
+{
+	const LIS_INT ss = e->options[LIS_EOPTIONS_SUBSPACE];
+	LISCHK(multi_filled(e, "lis_esolver_get_evectors", ss - 1, 1));
+	LIS_INT n, gn, is, ie, js = 0, err = LIS_SUCCESS;
+	LISCHK(lis_matrix_set_size(M, 0, e->evector[0]->gn));
+	LISCHK(lis_matrix_get_size(M, &n, &gn));
+	LISCHK(lis_matrix_get_range(M, &is, &ie));
+	if (e->evector[0]->origin) { is++; js++; }
+	LIS_SCALAR *col = (LIS_SCALAR *)malloc((size_t)(n > 0 ? n : 1) * sizeof(LIS_SCALAR));
+	if (!col) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)(n * sizeof(LIS_SCALAR)));
+	for (LIS_INT j = 0; j < ss && !err; j++) {
+		err = lis_vector_gather(e->evector[j], col);
+		for (LIS_INT i = 0; i < n && !err; i++) err = lis_matrix_set_value(LIS_INS_VALUE, i + is, j + js, col[i], M);
+	}
+	free(col);
+	if (err) return err;
+	LISCHK(lis_matrix_set_type(M, LIS_MATRIX_CSR));
+	return lis_matrix_assemble(M);
+}
 
 /* ------------------------------------------------------------------ what the five loops share */
 #define ETRY(expr) do { LIS_INT e__ = (expr); if (e__) { err = e__; goto done; } } while (0)
@@ -679,6 +730,353 @@ done:
 	return esolver->retcode;
 }
 
+/* ================================================================== several eigenpairs per solve: subspace, Lanczos, Arnoldi
+ * The orthogonalisation pairs of -e si and the Hessenberg columns of -e ai are taken as a chain whose coefficients stay in HBM (hdev): liship_dot_f64 forms
+ * the first, liship_mgs_step_f64 applies one and forms the next, and nothing waits for the host in between.  The tail of a subspace iteration is two passes
+ * (liship_multidot_f64, liship_ritz_tail_f64) and one read-back.  LIS_AMD_NO_FUSION=1 / LIS_AMD_LOOP_UNFUSED brings the lis_vector_* calls of the reference's
+ * text back: the same bits, in the tree mode and in the reference-order mode (tests/test_esolve_multi_gpu.py). */
+#define EHIP(call) do { int rc__ = (call); if (rc__) { err = lisi_hip_error(__FILE__, __func__, __LINE__, rc__); goto done; } } while (0)
+
+static int chain_ready(LIS_INT n, LIS_VECTOR a, LIS_VECTOR b)
+{	/* liship_ritz_tail_f64 takes 16 B aligned arrays (every vector the library allocates is) */
+	double *pa, *pb;
+	if (lisg.no_fusion || n <= 0) return 0;
+	if (lisd_vec_in(a, &pa) || lisd_vec_in(b, &pb)) return 0;
+	return (((uintptr_t)pa | (uintptr_t)pb) & 15u) == 0;
+}
+
+/* ------------------------------------------------------------------ subspace iteration, lis_esolver_si.c:137-370 */
+static LIS_INT lis_esi(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 1);
+	LIS_MATRIX A = c->A;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER], n = A->n;
+	LIS_VECTOR r = esolver->work[0], q = esolver->work[1], *v = &esolver->work[2];
+	LIS_SCALAR theta = 0.0, dot;
+	LIS_REAL nrm2, resid = 0.0;
+	LIS_INT err = 0, iter, j, k;
+	double etime0, etime, *hdev = NULL;
+	char esolvername[128];
+	int shifted = 0;
+	ETRY(lis_vector_set_all(1.0, r));
+	ETRY(lis_vector_nrm2(r, &nrm2));
+	ETRY(lis_vector_scale(1.0 / nrm2, r));
+	if (c->oshift != 0.0) { ETRY(lis_matrix_shift_diagonal(A, c->oshift)); shifted = 1; }
+	eshift_banner(c);
+	lis_esolver_get_esolvername(niesolver, esolvername);
+	if (c->output) lis_printf(LIS_COMM_WORLD, "inner eigensolver     : %s\n", esolvername);
+	if (niesolver == LIS_ESOLVER_II) ETRY(inner_solver(c, "-i bicg -p none"));
+	if (c->output) {
+		lis_printf(LIS_COMM_WORLD, "size of subspace      : %D\n\n", ss);
+		lis_printf(LIS_COMM_WORLD, "compute eigenpairs in subspace:\n\n");
+	}
+	if (!lisg.no_fusion) EHIP(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(ss + 2)));
+	j = 0;
+	while (j < ss) {
+		etime0 = lis_wtime();
+		ETRY(lis_vector_duplicate(A, &esolver->evector[j]));
+		j = j + 1;
+		ETRY(lis_vector_copy(r, v[j]));
+		if (niesolver == LIS_ESOLVER_II) {                   /* a preconditioner per mode, as there; the earlier one is freed (the reference leaks it) */
+			if (c->precon) { lis_precon_destroy(c->precon); c->precon = NULL; }
+			c->solver->A = A;
+			ETRY(lis_precon_create(c->solver, &c->precon));
+		}
+		const int fused = chain_ready(n, r, v[j]);
+		iter = 0;
+		while (iter < c->emaxiter) {
+			iter = iter + 1;
+			/* QR factorization V*R = Z for starting vector Z: v(j) against v(1) .. v(j-1), dot then axpy, pair by pair */
+			if (fused && j > 1) {
+				double *vj, *vk, *vn;
+				ETRY(lisd_vec_in(v[j], &vj)); ETRY(lisd_vec_in(v[1], &vk));
+				EHIP(liship_dot_f64(n, vj, vk, hdev, lisg.reduce_work, lisg.stream));
+				for (k = 1; k < j - 1; k++) {
+					ETRY(lisd_vec_in(v[k], &vk)); ETRY(lisd_vec_in(v[k + 1], &vn));
+					EHIP(liship_mgs_step_f64(n, hdev + k - 1, vk, vj, vn, hdev + k, lisg.reduce_work, lisg.stream));
+				}
+				ETRY(lisd_vec_in(v[j - 1], &vk));
+				EHIP(liship_scale_to_f64(1, -1.0, hdev + j - 2, hdev + j - 1, lisg.stream));      /* the last coefficient negated in HBM: the axpy below adds */
+				EHIP(liship_axpy_dev_f64(n, hdev + j - 1, vk, vj, lisg.stream));
+				ETRY(lisd_vec_done(v[j]));
+			} else {
+				for (k = 1; k < j; k++) {
+					ETRY(lis_vector_dot(v[j], v[k], &dot));
+					ETRY(lis_vector_axpy(-dot, v[k], v[j]));
+				}
+			}
+			/* kernel: R = A * V or R = A^-1 * V */
+			if (niesolver == LIS_ESOLVER_PI) ETRY(lis_matvec(A, v[j], r));
+			else ETRY(inner_solve(c, v[j], r, 0));
+			if (j == 1 && niesolver == LIS_ESOLVER_II) inner_times(c);
+			/* Z = V*R; resid = ||Z - V*R||_2 / |theta|; r = r / ||r||_2; v(j) = r */
+			if (fused) {
+				static const int pairs[2][2] = {{0, 0}, {1, 0}};
+				double *dr, *dvj, sums[3];
+				ETRY(lisd_vec_in(r, &dr)); ETRY(lisd_vec_in(v[j], &dvj));
+				const double *dv[2] = {dr, dvj};
+				EHIP(liship_multidot_f64(n, 2, dv, 2, pairs, lisg.reduce_out, lisg.reduce_work, lisg.stream));
+				EHIP(liship_ritz_tail_f64(n, lisg.reduce_out, dr, dvj, lisg.reduce_out + 2, lisg.reduce_work, lisg.stream));
+				ETRY(lisd_vec_done(r)); ETRY(lisd_vec_done(v[j]));
+				ETRY(lisd_fetch(3, sums));                       /* the one read-back of the iteration */
+				nrm2 = sqrt(sums[0]); theta = sums[1]; resid = sqrt(sums[2]);
+				resid = resid / fabs(theta);
+			} else {
+				ETRY(lis_vector_nrm2(r, &nrm2));
+				ETRY(lis_vector_dot(v[j], r, &theta));
+				ETRY(lis_vector_axpyz(-theta, v[j], r, q));
+				ETRY(lis_vector_nrm2(q, &resid));
+				resid = resid / fabs(theta);
+				ETRY(lis_vector_scale(1.0 / nrm2, r));
+				ETRY(lis_vector_copy(r, v[j]));
+			}
+			/* convergence check: the history and iter[0] are mode 0's */
+			if (j == 1) {
+				if (c->output & LIS_EPRINT_MEM) esolver->rhistory[iter] = resid;
+				esolver->iter[j - 1] = iter;
+			}
+			if (c->output & LIS_EPRINT_OUT) lis_printf(LIS_COMM_WORLD, "iteration: %5d  relative residual = %E\n", (int)iter, (double)resid);
+			if (c->tol > resid) break;
+		}
+		esolver->evalue[j - 1] = (niesolver == LIS_ESOLVER_PI) ? theta + c->oshift : 1 / theta + c->oshift;
+		esolver->resid[j - 1] = resid;
+		esolver->iter[j - 1] = iter;
+		ETRY(lis_vector_copy(v[j], esolver->evector[j - 1]));
+		etime = lis_wtime() - etime0;
+		if (c->output & (ss > 1)) {                           /* (as written there: the MEM bit of -eprint) */
+			lis_printf(LIS_COMM_WORLD, "Subspace: mode number          = %D\n", j - 1);
+			lis_printf(LIS_COMM_WORLD, "Subspace: eigenvalue           = %e\n", (double)esolver->evalue[j - 1]);
+			lis_printf(LIS_COMM_WORLD, "Subspace: elapsed time         = %e sec.\n", etime);
+			lis_printf(LIS_COMM_WORLD, "Subspace: number of iterations = %D\n", iter);
+			lis_printf(LIS_COMM_WORLD, "Subspace: relative residual    = %e\n\n", (double)resid);
+		}
+	}
+done:
+	if (hdev) (void)liship_free(hdev);
+	if (shifted) { const LIS_INT e2 = lis_matrix_shift_diagonal(A, -c->oshift); if (e2 && !err) err = e2; }
+	inner_destroy(c);
+	if (!err) err = lis_vector_copy(esolver->evector[0], esolver->x);
+	return err;                                              /* LIS_SUCCESS also when a mode stopped at -emaxiter, as there */
+}
+
+/* ------------------------------------------------------------------ what Lanczos and Arnoldi share */
+static LIS_INT multi_banner(ectx_t *c, LIS_INT niesolver)
+{	/* lis_esolver_li.c:192-206: the reference creates a linear solver for these three lines only */
+	char esolvername[128];
+	lis_esolver_get_esolvername(niesolver, esolvername);
+	if (c->output) lis_printf(LIS_COMM_WORLD, "inner eigensolver     : %s\n", esolvername);
+	const LIS_INT err = inner_solver(c, "-i bicg -p none");
+	inner_destroy(c);
+	return err;
+}
+
+/* the refinements after the Ritz values (lis_esolver_li.c:285-346, lis_esolver_ai.c:322-381): per mode a fresh eigensolver of one pair -- -ie's solver with the
+ * outer -emaxiter, -etol and -eprint, shifted by the Ritz value -- run by lis_esolve on evector[i]; mode 0's history, times, count and residual go into the
+ * outer object.  Whatever the inner eigensolver returned, the answer is LIS_SUCCESS, as there. */
+static LIS_INT refine_modes(ectx_t *c, const char *name)
+{
+	LIS_ESOLVER esolver = c->e, esolver2;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE];
+	if (c->output) lis_printf(LIS_COMM_WORLD, "computing refined eigenpairs using inner eigensolver:\n\n");
+	for (LIS_INT i = 0; i < ss; i++) {
+		LIS_SCALAR evalue = 0.0;
+		LISCHK(lis_esolver_create(&esolver2));
+		esolver2->options[LIS_EOPTIONS_ESOLVER] = esolver->options[LIS_EOPTIONS_INNER_ESOLVER];
+		esolver2->options[LIS_EOPTIONS_SUBSPACE] = 1;
+		esolver2->options[LIS_EOPTIONS_MAXITER] = c->emaxiter;
+		esolver2->options[LIS_EOPTIONS_OUTPUT] = esolver->options[LIS_EOPTIONS_OUTPUT];
+		esolver2->params[LIS_EPARAMS_RESID - LIS_EOPTIONS_LEN] = c->tol;
+		LIS_INT err = lis_vector_duplicate(c->A, &esolver->evector[i]);
+		if (err) { lis_esolver_destroy(esolver2); return err; }
+		esolver2->ishift = esolver->evalue[i];
+		(void)lis_esolve(c->A, esolver->evector[i], &evalue, esolver2);
+		if (esolver2->evalue) {
+			esolver->evalue[i] = esolver2->evalue[0];
+			esolver->iter[i] = esolver2->iter[0];
+			esolver->resid[i] = esolver2->resid[0];
+			if (i == 0) {
+				if (c->output & LIS_EPRINT_MEM) for (LIS_INT ic = 0; ic < esolver2->iter[0] + 1; ic++) esolver->rhistory[ic] = esolver2->rhistory[ic];
+				esolver->time = esolver2->time;
+				esolver->ptime += esolver2->ptime; esolver->itime += esolver2->itime;
+				esolver->p_c_time += esolver2->p_c_time; esolver->p_i_time += esolver2->p_i_time;
+			}
+			if (c->output) {
+				lis_printf(LIS_COMM_WORLD, "%s: mode number          = %D\n", name, i);
+				lis_printf(LIS_COMM_WORLD, "%s: eigenvalue           = %e\n", name, (double)esolver->evalue[i]);
+				lis_printf(LIS_COMM_WORLD, "%s: elapsed time         = %e sec.\n", name, esolver2->time);
+				lis_printf(LIS_COMM_WORLD, "%s: number of iterations = %D\n", name, esolver2->iter[0]);
+				lis_printf(LIS_COMM_WORLD, "%s: relative residual    = %e\n\n", name, (double)esolver2->resid[0]);
+			}
+		}
+		lis_esolver_destroy(esolver2);
+	}
+	return lis_vector_copy(esolver->evector[0], esolver->x);
+}
+
+/* ------------------------------------------------------------------ Lanczos, lis_esolver_li.c:149-356 */
+static LIS_INT lis_eli(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 0);
+	LIS_MATRIX A = c->A;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER];
+	LIS_VECTOR r = esolver->work[0], *v = &esolver->work[1];
+	LIS_SCALAR dot, *t = NULL, *tq = NULL, *tr = NULL;
+	LIS_REAL nrm2, qrerr;
+	LIS_INT err = 0, i, j, k, qriter;
+	double time, time0;
+	t = (LIS_SCALAR *)calloc((size_t)ss * ss, sizeof(LIS_SCALAR));
+	tq = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	tr = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	if (!t || !tq || !tr) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)(ss * ss * sizeof(LIS_SCALAR))); goto done; }
+	ETRY(lis_vector_set_all(0.0, v[0]));
+	ETRY(lis_vector_set_all(1.0, r));
+	ETRY(lis_vector_nrm2(r, &nrm2));
+	ETRY(multi_banner(c, niesolver));
+	j = 0;
+	while (j < ss - 1) {
+		j = j + 1;
+		ETRY(lis_vector_copy(r, v[j]));
+		/* v(j) = r / beta(j-1); r = A * v(j); r = r - beta(j-1) * v(j-1) */
+		if (j == 1) {
+			ETRY(lis_vector_scale(1.0 / nrm2, v[j]));
+			ETRY(lis_matvec(A, v[j], r));
+		} else {
+			ETRY(lis_vector_scale(1.0 / t[(j - 2) * ss + j - 1], v[j]));
+			ETRY(lis_matvec(A, v[j], r));
+			ETRY(lis_vector_axpy(-t[(j - 2) * ss + j - 1], v[j - 1], r));
+		}
+		ETRY(lis_vector_dot(v[j], r, &t[(j - 1) * ss + j - 1]));             /* alpha(j) = <v(j), r> */
+		ETRY(lis_vector_axpy(-t[(j - 1) * ss + j - 1], v[j], r));            /* r = r - alpha(j) * v(j) */
+		for (k = 1; k < j; k++) {                                            /* reorthogonalization: of v(j), after r was formed from it, as written there */
+			ETRY(lis_vector_dot(v[j], v[k], &dot));
+			ETRY(lis_vector_axpy(-dot, v[k], v[j]));
+		}
+		ETRY(lis_vector_nrm2(r, &t[(j - 1) * ss + j]));                      /* beta(j) = ||r||_2 */
+		if (fabs(t[(j - 1) * ss + j]) < c->tol) break;                       /* convergence check */
+		t[j * ss + j - 1] = t[(j - 1) * ss + j];
+	}
+	/* eigenvalues of the symmetric tridiagonal matrix */
+	time0 = lis_wtime();
+	ETRY(lis_array_qr(ss, t, tq, tr, &qriter, &qrerr));
+	time = lis_wtime() - time0;
+	for (i = 0; i < ss; i++) esolver->evalue[i] = t[i * ss + i];
+	if (c->output) {
+		lis_printf(LIS_COMM_WORLD, "size of subspace      : %D\n\n", ss);
+		lis_printf(LIS_COMM_WORLD, "Ritz values:\n\n");
+		for (i = 0; i < ss; i++) {
+			lis_printf(LIS_COMM_WORLD, "Lanczos: mode number          = %D\n", i);
+			lis_printf(LIS_COMM_WORLD, "Lanczos: Ritz value           = %e\n", (double)esolver->evalue[i]);
+		}
+		lis_printf(LIS_COMM_WORLD, "Lanczos: elapsed time         = %e sec.\n\n", time);
+	}
+	if (!esolver->options[LIS_EOPTIONS_RVAL]) err = refine_modes(c, "Lanczos");     /* -rval true: iter[] and resid[] stay 0 (heap contents there) */
+done:
+	free(t); free(tq); free(tr);
+	return err;
+}
+
+/* ------------------------------------------------------------------ Arnoldi, lis_esolver_ai.c:151-391 */
+static LIS_INT lis_eai(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 0);
+	LIS_MATRIX A = c->A;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER], n = A->n;
+	LIS_VECTOR w = esolver->work[0], *v = &esolver->work[1];
+	LIS_SCALAR *h = NULL, *hq = NULL, *hr = NULL;
+	LIS_REAL nrm2, hqrerr, D;
+	LIS_INT err = 0, i, j, hqriter;
+	double time, time0, *hdev = NULL;
+	const int fused = !lisg.no_fusion && ss + 1 <= 256;                     /* (a column comes home through the page-locked landing zone) */
+	h = (LIS_SCALAR *)calloc((size_t)ss * ss + 1, sizeof(LIS_SCALAR));      /* (one more than there: h(ss, ss-1), which the last column's norm is written to) */
+	hq = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	hr = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	if (!h || !hq || !hr) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)(ss * ss * sizeof(LIS_SCALAR))); goto done; }
+	ETRY(lis_vector_set_all(1.0, v[0]));
+	ETRY(lis_vector_nrm2(v[0], &nrm2));
+	ETRY(lis_vector_scale(1.0 / nrm2, v[0]));
+	ETRY(multi_banner(c, niesolver));
+	if (fused) EHIP(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(ss + 2)));
+	j = -1;
+	while (j < ss - 1) {
+		j = j + 1;
+		ETRY(lis_matvec(A, v[j], w));                                        /* w = A * v(j) */
+		if (fused) {
+			/* h(i,j) = <v(i), w>; w = w - h(i,j) * v(i), i = 0 .. j, then ||w||^2: one chain, one read-back per column */
+			double *dw, *vi, *vp;
+			ETRY(lisd_vec_in(w, &dw)); ETRY(lisd_vec_in(v[0], &vi));
+			EHIP(liship_dot_f64(n, vi, dw, hdev, lisg.reduce_work, lisg.stream));
+			for (i = 1; i <= j; i++) {
+				ETRY(lisd_vec_in(v[i - 1], &vp)); ETRY(lisd_vec_in(v[i], &vi));
+				EHIP(liship_mgs_step_f64(n, hdev + i - 1, vp, dw, vi, hdev + i, lisg.reduce_work, lisg.stream));
+			}
+			ETRY(lisd_vec_in(v[j], &vp));
+			EHIP(liship_mgs_step_f64(n, hdev + j, vp, dw, NULL, hdev + j + 1, lisg.reduce_work, lisg.stream));
+			ETRY(lisd_vec_done(w));
+			EHIP(liship_memcpy_d2h(lisg.host_out, hdev, sizeof(double) * (size_t)(j + 2), lisg.stream));
+			EHIP(liship_stream_synchronize(lisg.stream));
+			for (i = 0; i <= j; i++) h[i + j * ss] = lisg.host_out[i];
+			h[j + 1 + j * ss] = sqrt(lisg.host_out[j + 1]);
+		} else {
+			for (i = 0; i <= j; i++) {
+				ETRY(lis_vector_dot(v[i], w, &h[i + j * ss]));
+				ETRY(lis_vector_axpy(-h[i + j * ss], v[i], w));
+			}
+			ETRY(lis_vector_nrm2(w, &h[j + 1 + j * ss]));                    /* h(j+1,j) = ||w||_2 */
+		}
+		if (fabs(h[j + 1 + j * ss]) < c->tol) break;                         /* convergence check */
+		ETRY(lis_vector_scale(1 / h[j + 1 + j * ss], w));                    /* v(j+1) = w / h(j+1,j) */
+		ETRY(lis_vector_copy(w, v[j + 1]));
+	}
+	/* eigenvalues of the upper Hessenberg matrix: the diagonal and the 2 x 2 blocks QR leaves (a complex pair gives its real part twice) */
+	time0 = lis_wtime();
+	ETRY(lis_array_qr(ss, h, hq, hr, &hqriter, &hqrerr));
+	time = lis_wtime() - time0;
+	if (c->output) {
+		lis_printf(LIS_COMM_WORLD, "size of subspace      : %D\n\n", ss);
+		lis_printf(LIS_COMM_WORLD, "Ritz values:\n\n");
+	}
+	i = 0;
+	while (i < ss) {
+		i = i + 1;
+		if (ss == i || fabs(h[i + (i - 1) * ss]) < c->tol) {
+			if (c->output) {
+				lis_printf(LIS_COMM_WORLD, "Arnoldi: mode number          = %D\n", i - 1);
+				lis_printf(LIS_COMM_WORLD, "Arnoldi: Ritz value           = %e\n", (double)(h[i - 1 + (i - 1) * ss]));
+			}
+			esolver->evalue[i - 1] = h[i - 1 + (i - 1) * ss];
+		} else {
+			D = (h[i - 1 + (i - 1) * ss] + h[i + i * ss]) * (h[i - 1 + (i - 1) * ss] + h[i + i * ss])
+			    - 4 * (h[i - 1 + (i - 1) * ss] * h[i + i * ss] - h[i - 1 + i * ss] * h[i + (i - 1) * ss]);
+			if (D < 0) {
+				if (c->output) {
+					lis_printf(LIS_COMM_WORLD, "Arnoldi: mode number          = %D\n", i - 1);
+					lis_printf(LIS_COMM_WORLD, "Arnoldi: Ritz value           = (%e, %e)\n", (double)((h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2), (double)sqrt(-D) / 2);
+					lis_printf(LIS_COMM_WORLD, "Arnoldi: mode number          = %D\n", i);
+					lis_printf(LIS_COMM_WORLD, "Arnoldi: Ritz value           = (%e, %e)\n", (double)((h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2), (double)-sqrt(-D) / 2);
+				}
+				esolver->evalue[i - 1] = (h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2;
+				esolver->evalue[i] = (h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2;
+				i = i + 1;
+			} else {
+				if (c->output) {
+					lis_printf(LIS_COMM_WORLD, "Arnoldi: mode number          = %D\n", i - 1);
+					lis_printf(LIS_COMM_WORLD, "Arnoldi: Ritz value           = %e\n", (double)(h[i - 1 + (i - 1) * ss]));
+				}
+				esolver->evalue[i - 1] = h[i - 1 + (i - 1) * ss];
+			}
+		}
+	}
+	lis_printf(LIS_COMM_WORLD, "Arnoldi: elapsed time         = %e sec.\n\n", time);      /* (printed at -eprint none too, as there) */
+	if (!esolver->options[LIS_EOPTIONS_RVAL]) err = refine_modes(c, "Arnoldi");
+done:
+	if (hdev) (void)liship_free(hdev);
+	free(h); free(hq); free(hr);
+	return err;
+}
+
 /* ------------------------------------------------------------------ lis_esolve / lis_gesolve, ref :263-666 */
 static LIS_INT work_alloc(LIS_ESOLVER e, LIS_INT count)
 {	/* lis_e<xx>_malloc_work: NWORK duplicates of A's row layout */
@@ -709,9 +1107,14 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	if (nesolver < 1 || nesolver > LIS_ESOLVER_LEN) return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_ESOLVER is %D (Set between 1 to %D)\n", nesolver, LIS_ESOLVER_LEN);
 	/* what is not served, said before A or x is touched */
 	if (B != NULL) { esolver->retcode = LIS_ERR_NOT_IMPLEMENTED; return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "generalized eigenproblems (lis_gesolve with a matrix B) are not served by liblis_amd\n"); }
-	if (nesolver > LIS_ESOLVER_CR) {
+	if (nesolver > LIS_ESOLVER_CR && !is_multi(nesolver)) {
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd (pi, ii, rqi, cg, cr)\n", esolver_names[nesolver], esolver_keys[nesolver - 1]);
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd (pi, ii, rqi, cg, cr, si, li, ai)\n", esolver_names[nesolver], esolver_keys[nesolver - 1]);
+	}
+	if (is_multi(nesolver) && ss == 1) {
+		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) with a subspace of one vector (-ss 1, the default) is not served by liblis_amd: one eigenpair is what -e pi / -e ii serve\n",
+		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
 	}
 	if (lisg.nprocs > 1 || A->nprocs > 1) { esolver->retcode = LIS_ERR_NOT_IMPLEMENTED; return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_esolve is served on one rank (this job has %D)\n", (LIS_INT)lisg.nprocs); }
 	if (eprecision != LIS_PRECISION_DOUBLE) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Quad precision is not enabled\n"); }
@@ -721,11 +1124,21 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	}
 	if (emaxiter < 0) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_MAXITER(=%D) is less than 0\n", emaxiter); }
 	if (ss < 1 || mode < 0 || mode > ss + 1) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameters LIS_EOPTIONS_SUBSPACE(=%D), LIS_EOPTIONS_MODE(=%D) are out of range\n", ss, mode); }
+	if (is_multi(nesolver)) {                                /* ref :389-411, and the inner eigensolvers the loops can run */
+		const LIS_INT niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER];
+		if (ss > A->gn) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_SUBSPACE is %D (Set less than or equal to matrix size %D)\n", ss, A->gn); }
+		if (mode >= ss) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_MODE is %D (Set less than subspace size %D)\n", mode, ss); }
+		if (nesolver == LIS_ESOLVER_SI ? (niesolver != LIS_ESOLVER_PI && niesolver != LIS_ESOLVER_II) : (niesolver < LIS_ESOLVER_PI || niesolver > LIS_ESOLVER_CR)) {
+			esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;       /* (the reference's subspace loop applies A for -ie pi and -ie ii only) */
+			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "inner eigensolver %D (-ie) is not served by liblis_amd for -e %s (%s)\n", niesolver, esolver_keys[nesolver - 1],
+			                nesolver == LIS_ESOLVER_SI ? "pi, ii" : "pi, ii, rqi, cg, cr");
+		}
+	}
 	if (MDEV(A)->device_only && A->matrix_type != LIS_MATRIX_CSR) { esolver->retcode = LIS_ERR_NOT_IMPLEMENTED; return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "a matrix that lives in HBM only is shifted in CSR storage\n"); }
 	esolver->eprecision = eprecision;
 
 	/* the arrays of the object (ss + 2 entries each, ref :438-550), zeroed */
-	free(esolver->evalue); free(esolver->resid); free(esolver->iter); free(esolver->iter2); free(esolver->evector); free(esolver->rhistory);
+	arrays_free(esolver);                                    /* (with the eigenvectors an earlier solve left) */
 	esolver->evalue = (LIS_SCALAR *)calloc((size_t)ss + 2, sizeof(LIS_SCALAR));
 	esolver->resid = (LIS_REAL *)calloc((size_t)ss + 2, sizeof(LIS_REAL));
 	esolver->iter = (LIS_INT *)calloc((size_t)ss + 2, sizeof(LIS_SCALAR));
@@ -763,7 +1176,7 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	}
 	double time = lis_wtime();
 	esolver->ptime = 0; esolver->itime = 0; esolver->p_c_time = 0; esolver->p_i_time = 0;
-	if ((err = work_alloc(esolver, nesolver == LIS_ESOLVER_CG || nesolver == LIS_ESOLVER_CR ? 6 : 2))) goto fail;
+	if ((err = work_alloc(esolver, nesolver == LIS_ESOLVER_CG || nesolver == LIS_ESOLVER_CR ? 6 : nesolver == LIS_ESOLVER_SI ? 4 + ss : is_multi(nesolver) ? 2 + ss : 2))) goto fail;
 	esolver->x = xx; esolver->xx = x;
 
 	switch (nesolver) {
@@ -771,6 +1184,9 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	case LIS_ESOLVER_II:  err = lis_eii(esolver); break;
 	case LIS_ESOLVER_RQI: err = lis_erqi(esolver); break;
 	case LIS_ESOLVER_CG:  err = lis_ecg(esolver); break;
+	case LIS_ESOLVER_SI:  err = lis_esi(esolver); break;
+	case LIS_ESOLVER_LI:  err = lis_eli(esolver); break;
+	case LIS_ESOLVER_AI:  err = lis_eai(esolver); break;
 	default:              err = lis_ecr(esolver); break;
 	}
 	esolver->retcode = err;
@@ -794,6 +1210,7 @@ fail:
 	esolver->retcode = err;
 	esolver->x = x;
 	lis_vector_destroy(xx);
+	if (is_multi(nesolver)) arrays_free(esolver);            /* the getters of several pairs answer for a solve that ended */
 	return err;
 }
 
