@@ -426,7 +426,8 @@ int  liship_multidot_f64(int n, int nvec, const double *const *vecs, int K, cons
  * result[0] = sum q^2, formed EXACTLY as liship_sumsq_f64 forms it on a 16 B aligned array of n elements: the tree above on the same grid, or the T chunks
  * of liship_set_reference_reductions(T).  So the six calls nrm2, dot, axpyz, nrm2, scale, copy and {multidot, this} give the same bits (11 against 6
  * n-vector streams).  r and v must be 16 B aligned and must not overlap (one array given twice included): LISHIP_ERR_ARG otherwise and for n <= 0, with
- * nothing launched.  sums and result must not overlap either.  A pending liship_krylov_chain step rides in the fold, as in liship_sumsq_f64. */
+ * nothing launched.  sums and result must not overlap either.  It is one more op of the reductions above (kernels/vector_ops.hip), so a pending
+ * liship_krylov_chain step runs behind it wherever liship_sumsq_f64 runs it: in the fold, after a single workgroup, in the reference-order mode. */
 int  liship_ritz_tail_f64(int n, const double *sums, double *r, double *v, double *result, void *work, void *stream);
 /* value[k] -= sigma for the FIRST stored entry k of each row whose column is the row; a row without one is left alone (lis_matrix_shift_diagonal_csr,
  * src/matrix/lis_matrix_csr.c:566-603, on arrays in HBM; a split matrix's chain rows start with their diagonal term, host/lis_split.c) */

@@ -446,10 +446,39 @@ LIS_INT lisd_fetch(int count, double *out)
 {
 	if (lisg.nprocs > 1 && lisg.comm_kind == 1)        /* RCCL gathers the partials straight from HBM: one sync, not two */
 		return lisc_fold(count, out);
-	HIPCHK(liship_memcpy_d2h(lisg.host_out, lisg.reduce_out, (size_t)count * sizeof(double), lisg.stream));
-	HIPCHK(liship_stream_synchronize(lisg.stream));
-	for (int i = 0; i < count; i++) out[i] = lisg.host_out[i];
+	LISCHK(lisd_fetch_from(lisg.reduce_out, count, out));
 	if (lisg.nprocs > 1) LISCHK(lisc_fold(count, out));
+	return LIS_SUCCESS;
+}
+
+/* count doubles from an HBM address to the host, as they are: through the page-locked landing zone, beyond its 256 doubles straight into out */
+LIS_INT lisd_fetch_from(const double *dsrc, int count, double *out)
+{
+	double *land = count <= 256 ? lisg.host_out : out;
+	HIPCHK(liship_memcpy_d2h(land, dsrc, (size_t)count * sizeof(double), lisg.stream));
+	HIPCHK(liship_stream_synchronize(lisg.stream));
+	if (land != out) memcpy(out, land, (size_t)count * sizeof(double));
+	return LIS_SUCCESS;
+}
+
+/* RCCL job: replace this rank's sums in HBM by the sums over all ranks, without leaving the stream */
+LIS_INT lisd_globalize(double *slot, int count)
+{
+	if (lisg.comm_kind != 1) return LIS_SUCCESS;
+	LISCHK(lisc_gather_device(slot, count));
+	HIPCHK(liship_rank_fold_f64(count, lisg.gather_out, lisg.nprocs, slot, lisg.stream));
+	return LIS_SUCCESS;
+}
+
+/* The middle of a modified Gram-Schmidt chain whose coefficients stay in HBM: with hdev[0] = <w, basis[0]> formed by the caller, step k = 1 .. m - 1
+ * applies coefficient k - 1 (w -= hdev[k-1] * basis[k-1]) and forms hdev[k] = <w, basis[k]> in the same pass, each made global across the ranks; nothing
+ * waits for the host.  How the chain starts and how it ends -- coefficient m - 1 is still to be applied -- is the caller's. */
+LIS_INT lisd_mgs_chain(int n, int m, double *const *basis, double *w, double *hdev)
+{
+	for (int k = 1; k < m; k++) {
+		HIPCHK(liship_mgs_step_f64(n, hdev + k - 1, basis[k - 1], w, basis[k], hdev + k, lisg.reduce_work, lisg.stream));
+		LISCHK(lisd_globalize(hdev + k, 1));
+	}
 	return LIS_SUCCESS;
 }
 

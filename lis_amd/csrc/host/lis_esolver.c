@@ -756,7 +756,7 @@ static LIS_INT lis_esi(LIS_ESOLVER esolver)
 	LIS_SCALAR theta = 0.0, dot;
 	LIS_REAL nrm2, resid = 0.0;
 	LIS_INT err = 0, iter, j, k;
-	double etime0, etime, *hdev = NULL;
+	double etime0, etime, *hdev = NULL, **dv = NULL;         /* the chain's coefficients (HBM) and its basis as device pointers */
 	char esolvername[128];
 	int shifted = 0;
 	ETRY(lis_vector_set_all(1.0, r));
@@ -772,6 +772,7 @@ static LIS_INT lis_esi(LIS_ESOLVER esolver)
 		lis_printf(LIS_COMM_WORLD, "compute eigenpairs in subspace:\n\n");
 	}
 	if (!lisg.no_fusion) EHIP(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(ss + 2)));
+	if (!(dv = (double **)malloc(sizeof(double *) * (size_t)(ss + 1)))) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", ss + 1); goto done; }
 	j = 0;
 	while (j < ss) {
 		etime0 = lis_wtime();
@@ -789,16 +790,13 @@ static LIS_INT lis_esi(LIS_ESOLVER esolver)
 			iter = iter + 1;
 			/* QR factorization V*R = Z for starting vector Z: v(j) against v(1) .. v(j-1), dot then axpy, pair by pair */
 			if (fused && j > 1) {
-				double *vj, *vk, *vn;
-				ETRY(lisd_vec_in(v[j], &vj)); ETRY(lisd_vec_in(v[1], &vk));
-				EHIP(liship_dot_f64(n, vj, vk, hdev, lisg.reduce_work, lisg.stream));
-				for (k = 1; k < j - 1; k++) {
-					ETRY(lisd_vec_in(v[k], &vk)); ETRY(lisd_vec_in(v[k + 1], &vn));
-					EHIP(liship_mgs_step_f64(n, hdev + k - 1, vk, vj, vn, hdev + k, lisg.reduce_work, lisg.stream));
-				}
-				ETRY(lisd_vec_in(v[j - 1], &vk));
+				double *vj;
+				ETRY(lisd_vec_in(v[j], &vj));
+				for (k = 1; k < j; k++) ETRY(lisd_vec_in(v[k], &dv[k - 1]));
+				EHIP(liship_dot_f64(n, vj, dv[0], hdev, lisg.reduce_work, lisg.stream));
+				ETRY(lisd_mgs_chain(n, j - 1, dv, vj, hdev));
 				EHIP(liship_scale_to_f64(1, -1.0, hdev + j - 2, hdev + j - 1, lisg.stream));      /* the last coefficient negated in HBM: the axpy below adds */
-				EHIP(liship_axpy_dev_f64(n, hdev + j - 1, vk, vj, lisg.stream));
+				EHIP(liship_axpy_dev_f64(n, hdev + j - 1, dv[j - 2], vj, lisg.stream));
 				ETRY(lisd_vec_done(v[j]));
 			} else {
 				for (k = 1; k < j; k++) {
@@ -854,6 +852,7 @@ static LIS_INT lis_esi(LIS_ESOLVER esolver)
 	}
 done:
 	if (hdev) (void)liship_free(hdev);
+	free(dv);
 	if (shifted) { const LIS_INT e2 = lis_matrix_shift_diagonal(A, -c->oshift); if (e2 && !err) err = e2; }
 	inner_destroy(c);
 	if (!err) err = lis_vector_copy(esolver->evector[0], esolver->x);
@@ -988,7 +987,7 @@ static LIS_INT lis_eai(LIS_ESOLVER esolver)
 	LIS_SCALAR *h = NULL, *hq = NULL, *hr = NULL;
 	LIS_REAL nrm2, hqrerr, D;
 	LIS_INT err = 0, i, j, hqriter;
-	double time, time0, *hdev = NULL;
+	double time, time0, *hdev = NULL, **dv = NULL;
 	const int fused = !lisg.no_fusion && ss + 1 <= 256;                     /* (a column comes home through the page-locked landing zone) */
 	h = (LIS_SCALAR *)calloc((size_t)ss * ss + 1, sizeof(LIS_SCALAR));      /* (one more than there: h(ss, ss-1), which the last column's norm is written to) */
 	hq = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
@@ -999,26 +998,22 @@ static LIS_INT lis_eai(LIS_ESOLVER esolver)
 	ETRY(lis_vector_scale(1.0 / nrm2, v[0]));
 	ETRY(multi_banner(c, niesolver));
 	if (fused) EHIP(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(ss + 2)));
+	if (!(dv = (double **)malloc(sizeof(double *) * (size_t)(ss + 1)))) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", ss + 1); goto done; }
 	j = -1;
 	while (j < ss - 1) {
 		j = j + 1;
 		ETRY(lis_matvec(A, v[j], w));                                        /* w = A * v(j) */
 		if (fused) {
 			/* h(i,j) = <v(i), w>; w = w - h(i,j) * v(i), i = 0 .. j, then ||w||^2: one chain, one read-back per column */
-			double *dw, *vi, *vp;
-			ETRY(lisd_vec_in(w, &dw)); ETRY(lisd_vec_in(v[0], &vi));
-			EHIP(liship_dot_f64(n, vi, dw, hdev, lisg.reduce_work, lisg.stream));
-			for (i = 1; i <= j; i++) {
-				ETRY(lisd_vec_in(v[i - 1], &vp)); ETRY(lisd_vec_in(v[i], &vi));
-				EHIP(liship_mgs_step_f64(n, hdev + i - 1, vp, dw, vi, hdev + i, lisg.reduce_work, lisg.stream));
-			}
-			ETRY(lisd_vec_in(v[j], &vp));
-			EHIP(liship_mgs_step_f64(n, hdev + j, vp, dw, NULL, hdev + j + 1, lisg.reduce_work, lisg.stream));
+			double *dw;
+			ETRY(lisd_vec_in(w, &dw));
+			for (i = 0; i <= j; i++) ETRY(lisd_vec_in(v[i], &dv[i]));
+			EHIP(liship_dot_f64(n, dv[0], dw, hdev, lisg.reduce_work, lisg.stream));
+			ETRY(lisd_mgs_chain(n, j + 1, dv, dw, hdev));
+			EHIP(liship_mgs_step_f64(n, hdev + j, dv[j], dw, NULL, hdev + j + 1, lisg.reduce_work, lisg.stream));
 			ETRY(lisd_vec_done(w));
-			EHIP(liship_memcpy_d2h(lisg.host_out, hdev, sizeof(double) * (size_t)(j + 2), lisg.stream));
-			EHIP(liship_stream_synchronize(lisg.stream));
-			for (i = 0; i <= j; i++) h[i + j * ss] = lisg.host_out[i];
-			h[j + 1 + j * ss] = sqrt(lisg.host_out[j + 1]);
+			ETRY(lisd_fetch_from(hdev, j + 2, h + j * ss));                 /* the column h(0..j, j) and, in h(j+1, j), the sum of squares */
+			h[j + 1 + j * ss] = sqrt(h[j + 1 + j * ss]);
 		} else {
 			for (i = 0; i <= j; i++) {
 				ETRY(lis_vector_dot(v[i], w, &h[i + j * ss]));
@@ -1073,6 +1068,7 @@ static LIS_INT lis_eai(LIS_ESOLVER esolver)
 	if (!esolver->options[LIS_EOPTIONS_RVAL]) err = refine_modes(c, "Arnoldi");
 done:
 	if (hdev) (void)liship_free(hdev);
+	free(dv);
 	free(h); free(hq); free(hr);
 	return err;
 }

@@ -256,6 +256,9 @@ LIS_INT lisd_spmv(LIS_MATRIX A, double *dx, double *dy);      /* y = A x on devi
 LIS_INT lisd_spmv_dot_launch(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq); /* sums -> reduce_out */
 LIS_INT lisd_spmv_dot_launch_to(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq, double *result); /* sums -> result (HBM) */
 LIS_INT lisd_fetch(int count, double *out);                   /* reduce_out[0..count) -> host, cross-rank fold */
+LIS_INT lisd_fetch_from(const double *dsrc, int count, double *out);   /* count doubles of HBM -> host, through the page-locked landing zone */
+LIS_INT lisd_globalize(double *slot, int count);              /* RCCL job: sums in HBM -> the sums over all ranks, on the stream (else a no-op) */
+LIS_INT lisd_mgs_chain(int n, int m, double *const *basis, double *w, double *hdev);   /* steps 1 .. m-1 of a Gram-Schmidt chain kept in HBM */
 LIS_INT lisd_dot(int n, const double *dx, const double *dy, double *out);
 LIS_INT lisd_nrm2(int n, const double *dx, double *out);
 LIS_INT lisd_nrm1(int n, const double *dx, double *out);

@@ -796,15 +796,6 @@ done:
 	return err;
 }
 
-/* RCCL job: replace this rank's sums in HBM by the sums over all ranks, without leaving the stream */
-static LIS_INT globalize(double *slot, int count)
-{
-	if (lisg.comm_kind != 1) return LIS_SUCCESS;
-	LISCHK(lisc_gather_device(slot, count));
-	HIPCHK(liship_rank_fold_f64(count, lisg.gather_out, lisg.nprocs, slot, lisg.stream));
-	return LIS_SUCCESS;
-}
-
 static LIS_INT run_gmres(ctx_t *c)
 {
 	LIS_SOLVER s = c->s;
@@ -843,22 +834,12 @@ static LIS_INT run_gmres(ctx_t *c)
 				 * step's reduction, so the whole column costs ONE host synchronisation instead of i+1; the first
 				 * coefficient <A z, v0> is formed in the product's own pass */
 				TRY(lisd_spmv_dot_launch_to(c->A, zin, v[i1], v[0], 0, hdev));
-				TRY(globalize(hdev, 1));
-				for (int k = 1; k < i; k++) {
-					KTRY(liship_mgs_step_f64(n, hdev + k - 1, v[k - 1], v[i1], v[k], hdev + k, lisg.reduce_work, lisg.stream));
-					TRY(globalize(hdev + k, 1));
-				}
+				TRY(lisd_globalize(hdev, 1));
+				TRY(lisd_mgs_chain(n, i, v, v[i1], hdev));
 				KTRY(liship_mgs_step_f64(n, hdev + i - 1, v[i - 1], v[i1], NULL, hdev + i, lisg.reduce_work, lisg.stream));
-				TRY(globalize(hdev + i, 1));
+				TRY(lisd_globalize(hdev + i, 1));
 				KTRY(liship_scale_inv_norm_f64(n, hdev + i, v[i1], lisg.stream));
-				if (i + 1 <= 256) {                        /* through the page-locked landing zone */
-					KTRY(liship_memcpy_d2h(lisg.host_out, hdev, sizeof(double) * (size_t)(i + 1), lisg.stream));
-					KTRY(liship_stream_synchronize(lisg.stream));
-					memcpy(hc, lisg.host_out, sizeof(double) * (size_t)(i + 1));
-				} else {
-					KTRY(liship_memcpy_d2h(hc, hdev, sizeof(double) * (size_t)(i + 1), lisg.stream));
-					KTRY(liship_stream_synchronize(lisg.stream));
-				}
+				TRY(lisd_fetch_from(hdev, i + 1, hc));
 				hc[i1] = sqrt(hc[i1]);
 			} else {
 				for (int k = 0; k < i; k++) {                  /* modified Gram-Schmidt */

@@ -6,38 +6,20 @@
 // direction update, update + norm + dot) apply the SAME expressions in the SAME order per element --
 // fusing removes passes over HBM, not roundings.
 //
-// Launch shape (measured, tools/ubench_axpy.hip, 1 GiB vectors): one-shot grid, 4 independent 16 B
-// accesses per lane per array issued before the first use, non-temporal stores always, non-temporal
-// loads once the vectors are larger than the 256 MiB Infinity Cache: 4.8 -> 6.1 TB/s for axpy.
+// The lane mapping, the launch shape and the launch choice of every streaming pass here are stated in
+// vector_pass.hpp.  The CG direction update is its vector_pass applied to a functor over one element,
+// behind the kernel's prologue (guard, coefficients from HBM); ew_kernel and reduce_level1 write the same
+// walk out: their machine code is the one every recorded time of these kernels was measured on.
 //
 // Reductions (src/vector/lis_vector_ops.c) are trees: every lane accumulates its slice, a wavefront
 // butterfly (__shfl_xor) + LDS folds the workgroup, the per-workgroup partials are folded by further
 // one-shot passes until one workgroup finishes.  The tree depends only on n, so a result is
 // reproducible run to run; it is NOT the reference's left-to-right order (which itself changes with
 // OMP_NUM_THREADS, SURVEY 7 "hard parts").
-#include "common.hpp"
+#include "vector_pass.hpp"
 #include "liship.h"
 
 namespace {
-
-constexpr int BLOCK = 256;
-constexpr int NW = BLOCK / WAVE;
-constexpr int U = 4;                               // 16 B accesses per lane per array
-constexpr int PAIRS_PER_BLOCK = BLOCK * U;         // 2048 doubles per workgroup
-constexpr long long NT_LOAD_ELEMS = 32LL << 20;    // vectors beyond 256 MiB: stream past the caches
-constexpr size_t MAX_PARTIALS = (1u << 20) + 4096; // level-1 partials of a 2^31-element vector (+ level 2)
-
-inline int blocks_for(long long npairs) { return (int)((npairs + PAIRS_PER_BLOCK - 1) / PAIRS_PER_BLOCK); }
-
-template <bool NT> __device__ __forceinline__ v2f64 ld2(const double *p, long long pair)
-{
-    const v2f64 *q = reinterpret_cast<const v2f64 *>(p) + pair;
-    return NT ? __builtin_nontemporal_load(q) : *q;
-}
-__device__ __forceinline__ void st2(double *p, long long pair, v2f64 v)
-{
-    __builtin_nontemporal_store(v, reinterpret_cast<v2f64 *>(p) + pair);
-}
 
 // ---- device-driven Krylov loops ----------------------------------------------------------------------
 // A solver that keeps its scalars in HBM (liship.h "krylov state") enqueues many iterations without a host
@@ -89,6 +71,7 @@ void ew_kernel(int n, double a, double b, const double *in0, const double *in1, 
     if (D.pa) a = D.pa[0];
     if (D.pb) b = D.pb[0];
     if (OP == EW_SCALE_DEV) a = 1.0 / sqrt(in1[0]);     // in1: device scalar (a sum of squares), lis_solver_gmres.c:229-232
+    // the walk of vector_pass (vector_pass.hpp), written out: any change to the lane mapping there is due here
     if (VEC) {
         const long long npairs = n >> 1;
         const long long base = (long long)blockIdx.x * PAIRS_PER_BLOCK + threadIdx.x;
@@ -134,12 +117,11 @@ int run_ew(int n, double a, double b, const double *in0, const double *in1, cons
     if (n == 0) return 0;
     constexpr int NIN = EwArity<OP>::value;
     const bool vec = aligned16(out) && (NIN < 1 || aligned16(in0)) && (NIN < 2 || aligned16(in1)) && (NIN < 3 || aligned16(in2));
-    const int grid = blocks_for(vec ? (n + 1) / 2 : ((long long)n + 1) / 2);
     hipStream_t st = as_stream(stream);
     const Dev D{pa, pb, g_guard};
-    if (!vec)                       ew_kernel<OP, false, false><<<grid, BLOCK, 0, st>>>(n, a, b, in0, in1, in2, out, D);
-    else if (n > NT_LOAD_ELEMS)     ew_kernel<OP, true, true><<<grid, BLOCK, 0, st>>>(n, a, b, in0, in1, in2, out, D);
-    else                            ew_kernel<OP, false, true><<<grid, BLOCK, 0, st>>>(n, a, b, in0, in1, in2, out, D);
+    launch_pass(vec, n, [&](auto nt, auto v) {
+        ew_kernel<OP, decltype(nt)::value, decltype(v)::value><<<pass_grid(n), BLOCK, 0, st>>>(n, a, b, in0, in1, in2, out, D);
+    });
     LAUNCH_CHECK();
     return 0;
 }
@@ -156,57 +138,19 @@ void cg_direction_kernel(int n, const double *__restrict__ palpha, const double 
 {
     if (skip && skip[0] != 0.0) return;
     const double alpha = XUP ? palpha[0] : 0.0, beta = pbeta[0];
-    auto one = [&](double rv, double dv, double pv, double xv, double &po, double &xo) {
-        if (XUP) xo = xv + alpha * pv;                   // x[i] += alpha * p[i]
-        const double z = JAC == 1 ? rv * dv : JAC == 2 ? rv * dc : rv;       // z = M^-1 r
-        po = z + beta * pv;                              // p[i] = z[i] + beta * p[i]
-    };
-    if (VEC) {
-        const long long npairs = n >> 1;
-        const long long base = (long long)blockIdx.x * PAIRS_PER_BLOCK + threadIdx.x;
-        v2f64 rv[U], dv[U], pv[U], xv[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const long long q = base + u * BLOCK;
-            if (q < npairs) {
-                rv[u] = ld2<NT>(r, q); pv[u] = ld2<NT>(p, q);
-                if (JAC == 1) dv[u] = ld2<NT>(dinv, q);
-                if (XUP) xv[u] = ld2<NT>(x, q);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const long long q = base + u * BLOCK;
-            if (q < npairs) {
-                double p0 = 0.0, p1 = 0.0, x0 = 0.0, x1 = 0.0;
-                one(rv[u].x, JAC == 1 ? dv[u].x : 0.0, pv[u].x, XUP ? xv[u].x : 0.0, p0, x0);
-                one(rv[u].y, JAC == 1 ? dv[u].y : 0.0, pv[u].y, XUP ? xv[u].y : 0.0, p1, x1);
-                v2f64 po, xo;
-                po.x = p0; po.y = p1; xo.x = x0; xo.y = x1;
-                st2(p, q, po);
-                if (XUP) st2(x, q, xo);
-            }
-        }
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const int i = n - 1;
-            double po, xo;
-            one(r[i], JAC == 1 ? dinv[i] : 0.0, p[i], XUP ? x[i] : 0.0, po, xo);
-            p[i] = po;
-            if (XUP) x[i] = xo;
-        }
-    } else {
-        const long long i0 = (long long)blockIdx.x * (2 * PAIRS_PER_BLOCK) + threadIdx.x;
-#pragma unroll
-        for (int u = 0; u < 2 * U; u++) {
-            const long long i = i0 + u * BLOCK;
-            if (i < n) {
-                double po, xo;
-                one(r[i], JAC == 1 ? dinv[i] : 0.0, p[i], XUP ? x[i] : 0.0, po, xo);
-                p[i] = po;
-                if (XUP) x[i] = xo;
-            }
-        }
-    }
+    constexpr int ID = 2, IX = ID + (JAC == 1), NIN = IX + XUP, NOUT = 1 + XUP;      // inputs r, p, [dinv], [x]; outputs p, [x]
+    const double *in[NIN] = {r, p};
+    double *out[NOUT] = {p};
+    if constexpr (JAC == 1) in[ID] = dinv;
+    if constexpr (XUP) { in[IX] = x; out[1] = x; }
+    vector_pass<NT, VEC, NIN, NOUT>(n, in, out, [&](const double (&v)[NIN], double (&o)[NOUT]) {
+        const double rv = v[0], pv = v[1];
+        if constexpr (XUP) o[1] = v[IX] + alpha * pv;    // x[i] += alpha * p[i]
+        double z = rv;                                   // z = M^-1 r
+        if constexpr (JAC == 1) z = rv * v[ID];
+        if constexpr (JAC == 2) z = rv * dc;
+        o[0] = z + beta * pv;                           // p[i] = z[i] + beta * p[i]
+    });
 }
 
 template <int JAC, bool XUP>
@@ -215,11 +159,10 @@ int run_cg_direction(int n, const double *palpha, const double *pbeta, const dou
     if (n < 0 || !pbeta || !r || !p || (XUP && (!palpha || !x)) || (JAC == 1 && !dinv)) return LISHIP_ERR_ARG;
     if (n == 0) return 0;
     const bool vec = aligned16(r) && aligned16(p) && (JAC != 1 || aligned16(dinv)) && (!XUP || aligned16(x));
-    const int grid = blocks_for(((long long)n + 1) / 2);
     hipStream_t st = as_stream(stream);
-    if (!vec)                   cg_direction_kernel<false, false, JAC, XUP><<<grid, BLOCK, 0, st>>>(n, palpha, pbeta, r, dinv, dc, p, x, g_guard);
-    else if (n > NT_LOAD_ELEMS) cg_direction_kernel<true, true, JAC, XUP><<<grid, BLOCK, 0, st>>>(n, palpha, pbeta, r, dinv, dc, p, x, g_guard);
-    else                        cg_direction_kernel<false, true, JAC, XUP><<<grid, BLOCK, 0, st>>>(n, palpha, pbeta, r, dinv, dc, p, x, g_guard);
+    launch_pass(vec, n, [&](auto nt, auto v) {
+        cg_direction_kernel<decltype(nt)::value, decltype(v)::value, JAC, XUP><<<pass_grid(n), BLOCK, 0, st>>>(n, palpha, pbeta, r, dinv, dc, p, x, g_guard);
+    });
     LAUNCH_CHECK();
     return 0;
 }
@@ -236,7 +179,8 @@ enum RedOp { RED_DOT, RED_SUMSQ, RED_ABS, RED_SUM, RED_DOT2,
              RED_COUNT_NE,      // result {number of x[i] whose bits differ from a's}
              RED_BICGSTAB_END,  // e += (*pb)*d; e += (*pc)*y; y += a*x; results {sum y^2, sum w*y}   (x-iterate and residual of BiCGSTAB)
              RED_AXPYD_DOT,     // y += (-*sp)*x; result {sum y*w}      (one modified Gram-Schmidt step)
-             RED_AXPYD_SUMSQ    // y += (-*sp)*x; result {sum y^2}      (the last one)
+             RED_AXPYD_SUMSQ,   // y += (-*sp)*x; result {sum y^2}      (the last one)
+             RED_RITZ_TAIL      // q = (-sp[1])*y + x (not stored); ox = oy = (1/sqrt(sp[0]))*x; result {sum q^2}   (x: r, y: v of a subspace iteration)
 };
 template <int OP> struct RedResults { static constexpr int value =
     (OP == RED_DOT2 || OP == RED_AXPY_NRM2_DOT || OP == RED_CG_UPDATE_JAC || OP == RED_AXPY_NRM2_JAC || OP == RED_AXPY_NRM2_JACU || OP == RED_BICGSTAB_END) ? 2 : 1; };
@@ -255,7 +199,7 @@ struct RedArgs {
 
 // one element of a reduction: the fused forms' in-place results (ox, oy) and the term(s) this element adds to the sum(s).
 // Shared by the tree kernels and the reference-order kernel, so the two orders add the SAME terms.
-struct RedCoef { double a, adev, cb, cc, c; };
+struct RedCoef { double a, adev, cb, cc, c, inv; };
 template <int OP>
 __device__ __forceinline__ void red_term(const RedCoef &K, double x, double y, double w, double d, double e,
                                          double &ox, double &oy, double &v0, double &v1)
@@ -291,16 +235,24 @@ __device__ __forceinline__ void red_term(const RedCoef &K, double x, double y, d
         oy = y + K.adev * x;            // y += (-h)*x, h read from HBM: no host round trip between steps
         if (OP == RED_AXPYD_DOT) v0 = oy * w; else v0 = oy * oy;
     }
+    if (OP == RED_RITZ_TAIL) {          // lis_esolver_si.c:301-311; x: r, y: v (r is loaded and stored first)
+        const double q = K.adev * y + x;// lis_vector_axpyz(-theta, v, r, q); q is not stored
+        v0 = q * q;
+        ox = oy = K.inv * x;            // lis_vector_scale(1 / nrm2, r); lis_vector_copy(r, v)
+    }
 }
 
+// what an op reads and writes: x always, the other inputs and the two outputs as listed (reduce_level1 and reduce_ref_kernel both read this)
 template <int OP> struct RedShape {
-    static constexpr bool IS_CG = (OP == RED_CG_UPDATE || OP == RED_CG_UPDATE_JAC || OP == RED_BICGSTAB_END);     // five inputs, two outputs
-    static constexpr bool IS_AXD = (OP == RED_AXPYD_DOT || OP == RED_AXPYD_SUMSQ);
-    static constexpr bool IS_AXN = (OP == RED_AXPY_NRM2 || OP == RED_AXPY_NRM2_DOT || OP == RED_AXPY_NRM2_JAC || OP == RED_AXPY_NRM2_JACU);
-    static constexpr bool HAS_Y = (OP == RED_DOT || OP == RED_DOT2 || IS_CG || IS_AXN || IS_AXD);
-    static constexpr bool HAS_W = (IS_CG || OP == RED_AXPY_NRM2_DOT || OP == RED_AXPYD_DOT);
-    static constexpr bool HAS_D = IS_CG;
+    static constexpr bool UPD2 = (OP == RED_CG_UPDATE || OP == RED_CG_UPDATE_JAC || OP == RED_BICGSTAB_END);      // an iterate and a residual updated
+    static constexpr bool AXN = (OP == RED_AXPY_NRM2 || OP == RED_AXPY_NRM2_DOT || OP == RED_AXPY_NRM2_JAC || OP == RED_AXPY_NRM2_JACU);
+    static constexpr bool AXD = (OP == RED_AXPYD_DOT || OP == RED_AXPYD_SUMSQ);
+    static constexpr bool HAS_Y = (OP == RED_DOT || OP == RED_DOT2 || UPD2 || AXN || AXD || OP == RED_RITZ_TAIL);
+    static constexpr bool HAS_W = (UPD2 || OP == RED_AXPY_NRM2_DOT || OP == RED_AXPYD_DOT);
+    static constexpr bool HAS_D = UPD2;
     static constexpr bool HAS_E = (OP == RED_CG_UPDATE_JAC || OP == RED_AXPY_NRM2_JAC || OP == RED_BICGSTAB_END);
+    static constexpr bool STORES_OX = (UPD2 || OP == RED_RITZ_TAIL);
+    static constexpr bool STORES_OY = (UPD2 || AXN || AXD || OP == RED_RITZ_TAIL);
 };
 
 template <int OP>
@@ -309,10 +261,11 @@ __device__ __forceinline__ RedCoef red_coef(RedArgs &A)
     if (A.pa) A.a = A.pa[0];
     RedCoef K;
     K.a = A.a;
-    K.adev = (OP == RED_AXPYD_DOT || OP == RED_AXPYD_SUMSQ) ? -A.sp[0] : 0.0;
+    K.adev = RedShape<OP>::AXD ? -A.sp[0] : OP == RED_RITZ_TAIL ? -A.sp[1] : 0.0;
     K.cb = OP == RED_BICGSTAB_END ? A.pb[0] : 0.0;
     K.cc = OP == RED_BICGSTAB_END ? A.pc[0] : 0.0;
     K.c = A.c;
+    K.inv = OP == RED_RITZ_TAIL ? 1.0 / sqrt(A.sp[0]) : 0.0;     // formed once per lane, as EW_SCALE_DEV's
     return K;
 }
 
@@ -322,6 +275,7 @@ void reduce_level1(RedArgs A, int stride, double *__restrict__ partial, bool roo
 {
     __shared__ double scratch[NW];
     constexpr int NRES = RedResults<OP>::value;
+    using S = RedShape<OP>;
     double s0 = 0.0, s1 = 0.0;
     const int n = A.n;
     if (A.skip && A.skip[0] != 0.0) return;
@@ -332,13 +286,7 @@ void reduce_level1(RedArgs A, int stride, double *__restrict__ partial, bool roo
         s0 += v0;
         if (NRES == 2) s1 += v1;
     };
-    constexpr bool IS_CG = (OP == RED_CG_UPDATE || OP == RED_CG_UPDATE_JAC || OP == RED_BICGSTAB_END);     // five inputs, two outputs
-    constexpr bool IS_AXD = (OP == RED_AXPYD_DOT || OP == RED_AXPYD_SUMSQ);
-    constexpr bool IS_AXN = (OP == RED_AXPY_NRM2 || OP == RED_AXPY_NRM2_DOT || OP == RED_AXPY_NRM2_JAC || OP == RED_AXPY_NRM2_JACU);
-    constexpr bool HAS_Y = (OP == RED_DOT || OP == RED_DOT2 || IS_CG || IS_AXN || IS_AXD);
-    constexpr bool HAS_W = (IS_CG || OP == RED_AXPY_NRM2_DOT || OP == RED_AXPYD_DOT);
-    constexpr bool HAS_D = IS_CG;
-    constexpr bool HAS_E = (OP == RED_CG_UPDATE_JAC || OP == RED_AXPY_NRM2_JAC || OP == RED_BICGSTAB_END);
+    // the walk of vector_pass (vector_pass.hpp), written out: any change to the lane mapping there is due here
     if (VEC) {
         const long long npairs = n >> 1;
         const long long base = (long long)blockIdx.x * PAIRS_PER_BLOCK + threadIdx.x;
@@ -348,10 +296,10 @@ void reduce_level1(RedArgs A, int stride, double *__restrict__ partial, bool roo
             const long long p = base + u * BLOCK;
             if (p < npairs) {
                 x[u] = ld2<NT>(A.x, p);
-                if (HAS_Y) y[u] = ld2<NT>(A.y, p);
-                if (HAS_W) w[u] = ld2<NT>(A.w, p);
-                if (HAS_D) d[u] = ld2<NT>(A.d, p);
-                if (HAS_E) e[u] = ld2<NT>(A.e, p);
+                if (S::HAS_Y) y[u] = ld2<NT>(A.y, p);
+                if (S::HAS_W) w[u] = ld2<NT>(A.w, p);
+                if (S::HAS_D) d[u] = ld2<NT>(A.d, p);
+                if (S::HAS_E) e[u] = ld2<NT>(A.e, p);
             }
         }
 #pragma unroll
@@ -359,20 +307,20 @@ void reduce_level1(RedArgs A, int stride, double *__restrict__ partial, bool roo
             const long long p = base + u * BLOCK;
             if (p < npairs) {
                 double ox0 = 0.0, oy0 = 0.0, ox1 = 0.0, oy1 = 0.0;
-                term(x[u].x, HAS_Y ? y[u].x : 0.0, HAS_W ? w[u].x : 0.0, HAS_D ? d[u].x : 0.0, HAS_E ? e[u].x : 0.0, ox0, oy0);
-                term(x[u].y, HAS_Y ? y[u].y : 0.0, HAS_W ? w[u].y : 0.0, HAS_D ? d[u].y : 0.0, HAS_E ? e[u].y : 0.0, ox1, oy1);
+                term(x[u].x, S::HAS_Y ? y[u].x : 0.0, S::HAS_W ? w[u].x : 0.0, S::HAS_D ? d[u].x : 0.0, S::HAS_E ? e[u].x : 0.0, ox0, oy0);
+                term(x[u].y, S::HAS_Y ? y[u].y : 0.0, S::HAS_W ? w[u].y : 0.0, S::HAS_D ? d[u].y : 0.0, S::HAS_E ? e[u].y : 0.0, ox1, oy1);
                 v2f64 ox, oy;
                 ox.x = ox0; ox.y = ox1; oy.x = oy0; oy.y = oy1;
-                if (IS_CG) { st2(A.ox, p, ox); st2(A.oy, p, oy); }
-                if (IS_AXN || IS_AXD) st2(A.oy, p, oy);
+                if (S::STORES_OX) st2(A.ox, p, ox);
+                if (S::STORES_OY) st2(A.oy, p, oy);
             }
         }
         if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
             const int i = n - 1;
             double ox, oy;
-            term(A.x[i], HAS_Y ? A.y[i] : 0.0, HAS_W ? A.w[i] : 0.0, HAS_D ? A.d[i] : 0.0, HAS_E ? A.e[i] : 0.0, ox, oy);
-            if (IS_CG) { A.ox[i] = ox; A.oy[i] = oy; }
-            if (IS_AXN || IS_AXD) A.oy[i] = oy;
+            term(A.x[i], S::HAS_Y ? A.y[i] : 0.0, S::HAS_W ? A.w[i] : 0.0, S::HAS_D ? A.d[i] : 0.0, S::HAS_E ? A.e[i] : 0.0, ox, oy);
+            if (S::STORES_OX) A.ox[i] = ox;
+            if (S::STORES_OY) A.oy[i] = oy;
         }
     } else {
         const long long i0 = (long long)blockIdx.x * (2 * PAIRS_PER_BLOCK) + threadIdx.x;
@@ -380,9 +328,9 @@ void reduce_level1(RedArgs A, int stride, double *__restrict__ partial, bool roo
             const long long i = i0 + u * BLOCK;
             if (i < n) {
                 double ox, oy;
-                term(A.x[i], HAS_Y ? A.y[i] : 0.0, HAS_W ? A.w[i] : 0.0, HAS_D ? A.d[i] : 0.0, HAS_E ? A.e[i] : 0.0, ox, oy);
-                if (IS_CG) { A.ox[i] = ox; A.oy[i] = oy; }
-                if (IS_AXN || IS_AXD) A.oy[i] = oy;
+                term(A.x[i], S::HAS_Y ? A.y[i] : 0.0, S::HAS_W ? A.w[i] : 0.0, S::HAS_D ? A.d[i] : 0.0, S::HAS_E ? A.e[i] : 0.0, ox, oy);
+                if (S::STORES_OX) A.ox[i] = ox;
+                if (S::STORES_OY) A.oy[i] = oy;
             }
         }
     }
@@ -403,7 +351,6 @@ void reduce_level1(RedArgs A, int stride, double *__restrict__ partial, bool roo
 // result carries the reference's bits for OMP_NUM_THREADS = T; a parity mode, not a fast one (one lane adds at ~8 cycles a term).
 // A multi-rank job whose ranks hold the row blocks LIS_GET_ISIE(rank, P, gn) at T = 1 forms, with the rank-order fold, the sum
 // of a single rank at T = P.
-constexpr int REF_TILE = 2048;
 int g_ref_chunks = 0;
 
 template <int OP>
@@ -417,10 +364,9 @@ void reduce_ref_kernel(RedArgs A, int T, double *__restrict__ partial)
     if (A.skip && A.skip[0] != 0.0) return;
     const RedCoef K = red_coef<OP>(A);
     const int n = A.n, c = blockIdx.x;
-    long long is, ie;                                   // LIS_GET_ISIE(c, T, n, is, ie)
-    if (c < n % T) { ie = n / T + 1; is = ie * c; } else { ie = n / T; is = ie * c + n % T; }
-    ie += is;
-    double s = 0.0;                                     // lane 0: the first result's running sum; lane 64: the second's
+    long long is, ie;
+    chunk_bounds(c, T, n, is, ie);
+    double s = 0.0;                                    // lane 0: the first result's running sum; lane 64: the second's
     for (long long base = is; base < ie; base += REF_TILE) {
         const int cnt = (int)(ie - base < REF_TILE ? ie - base : REF_TILE);
         for (int j = threadIdx.x; j < cnt; j += BLOCK) {
@@ -428,8 +374,8 @@ void reduce_ref_kernel(RedArgs A, int T, double *__restrict__ partial)
             double ox = 0.0, oy = 0.0, v0, v1;
             red_term<OP>(K, A.x[i], S::HAS_Y ? A.y[i] : 0.0, S::HAS_W ? A.w[i] : 0.0, S::HAS_D ? A.d[i] : 0.0, S::HAS_E ? A.e[i] : 0.0,
                          ox, oy, v0, v1);
-            if (S::IS_CG) { A.ox[i] = ox; A.oy[i] = oy; }
-            if (S::IS_AXN || S::IS_AXD) A.oy[i] = oy;
+            if (S::STORES_OX) A.ox[i] = ox;
+            if (S::STORES_OY) A.oy[i] = oy;
             t0[j] = v0;
             if (NRES == 2) t1[j] = v1;
         }
@@ -561,8 +507,7 @@ inline Chain take_chain() { Chain c = g_chain; g_chain.step = 0; return c; }
 
 // levels >= 2: out[k*ostride + block] = sum of in[k*istride + block*2048 ...), finally one block
 __global__ __launch_bounds__(BLOCK)
-void reduce_fold(int count, int nres, int istride, int ostride, const double *__restrict__ in, double *__restrict__ out,
-                 bool root)
+void reduce_fold(int count, int nres, int istride, int ostride, const double *__restrict__ in, double *__restrict__ out)
 {
     __shared__ double scratch[NW];
     for (int k = 0; k < nres; k++) {
@@ -575,7 +520,7 @@ void reduce_fold(int count, int nres, int istride, int ostride, const double *__
             if (i < count) s += src[i];
         }
         const double t = block_sum<NW>(s, scratch);
-        if (threadIdx.x == 0) out[(size_t)k * ostride + blockIdx.x] = root ? sqrt(t) : t;
+        if (threadIdx.x == 0) out[(size_t)k * ostride + blockIdx.x] = t;
     }
 }
 
@@ -630,14 +575,9 @@ int fold_partials(int count, int nres, int stride, double *partial, double *spar
             LAUNCH_CHECK();
             return 0;
         }
-        const int blocks = (count + 2 * PAIRS_PER_BLOCK - 1) / (2 * PAIRS_PER_BLOCK);
-        if (blocks == 1) {                          // (not reached any more: counts this small take the branch above)
-            reduce_fold<<<1, BLOCK, 0, st>>>(count, nres, cstride, 1, cur, result, root);
-            LAUNCH_CHECK();
-            return 0;
-        }
+        const int blocks = (count + 2 * PAIRS_PER_BLOCK - 1) / (2 * PAIRS_PER_BLOCK);     // at least 5: count is above 2^14
         double *dst = bufs[which];
-        reduce_fold<<<blocks, BLOCK, 0, st>>>(count, nres, cstride, blocks, cur, dst, false);
+        reduce_fold<<<blocks, BLOCK, 0, st>>>(count, nres, cstride, blocks, cur, dst);
         LAUNCH_CHECK();
         cur = dst; cstride = blocks; count = blocks;
         which ^= 1;
@@ -660,7 +600,7 @@ int run_reduce(RedArgs A, double *result, void *work, bool root, void *stream)
     if (A.e) vec = vec && aligned16(A.e);
     if (A.ox) vec = vec && aligned16(A.ox);
     if (A.oy) vec = vec && aligned16(A.oy);
-    int grid = blocks_for(vec ? (n + 1) / 2 : ((long long)n + 1) / 2);
+    int grid = pass_grid(n);
     if (grid < 1) grid = 1;
     double *partial = static_cast<double *>(work);
     double *spare = partial + 2 * MAX_PARTIALS;              // second half of the scratch
@@ -677,9 +617,9 @@ int run_reduce(RedArgs A, double *result, void *work, bool root, void *stream)
     const bool single = (grid == 1);                         // one block: it writes result[k] itself
     double *dst = single ? result : partial;
     const bool r1 = single && root;
-    if (!vec)                   reduce_level1<OP, false, false><<<grid, BLOCK, 0, st>>>(A, grid, dst, r1);
-    else if (n > NT_LOAD_ELEMS) reduce_level1<OP, true, true><<<grid, BLOCK, 0, st>>>(A, grid, dst, r1);
-    else                        reduce_level1<OP, false, true><<<grid, BLOCK, 0, st>>>(A, grid, dst, r1);
+    launch_pass(vec, n, [&](auto nt, auto v) {
+        reduce_level1<OP, decltype(nt)::value, decltype(v)::value><<<grid, BLOCK, 0, st>>>(A, grid, dst, r1);
+    });
     LAUNCH_CHECK();
     if (single) {                                            // no fold to ride in: the announced step gets its own launch
         const Chain c = take_chain();
@@ -840,6 +780,19 @@ extern "C" int liship_mgs_step_f64(int n, const double *hprev, const double *vpr
 // x *= 1/sqrt(*sumsq), sumsq in HBM  (lis_vector_nrm2 + lis_vector_scale, lis_solver_gmres.c:229-232)
 extern "C" int liship_scale_inv_norm_f64(int n, const double *sumsq, double *x, void *s)
 { return run_ew<EW_SCALE_DEV>(n, 0.0, 0.0, x, sumsq, nullptr, x, s); }
+// the tail of a subspace iteration (lis_esolver_si.c:301-311) in one pass, RED_RITZ_TAIL: sums = {sum r^2, theta = <v,r>} in HBM; the sum of q^2 is
+// liship_sumsq_f64's of a 16 B aligned array of n elements (the same grid, lane mapping and folds: it IS that reduction with another term)
+extern "C" int liship_ritz_tail_f64(int n, const double *sums, double *r, double *v, double *result, void *work, void *stream)
+{
+    if (n <= 0 || !sums || !r || !v || !result || !work) return LISHIP_ERR_ARG;
+    if (!aligned16(r) || !aligned16(v)) return LISHIP_ERR_ARG;
+    {	// r and v are each read and written by the lane that owns the element: arrays that overlap (one array given twice included) are refused
+        const uintptr_t a = reinterpret_cast<uintptr_t>(r), b = reinterpret_cast<uintptr_t>(v), len = (uintptr_t)n * sizeof(double);
+        if (a < b + len && b < a + len) return LISHIP_ERR_ARG;
+    }
+    RedArgs A{n, 0.0, r, v, nullptr, nullptr, nullptr, r, v, sums};
+    return run_reduce<RED_RITZ_TAIL>(A, result, work, false, stream);
+}
 
 // ---- device-driven Krylov loops: coefficient-from-HBM forms and the scalar steps (liship.h) --------------
 extern "C" int liship_krylov_guard(const double *flag) { g_guard = flag; return 0; }

@@ -1,6 +1,7 @@
-"""liship_ritz_tail_f64 (kernels/eigen.hip), the fused tail of a subspace iteration, against a numpy model built from tests/reduction_model.py: the new r,
-the new v and the sum of q^2 in every bit, in the tree mode (T = 0) and in the reference-order mode (T chunks summed left to right, the partials in chunk
-order), at every size where the launch takes another shape; guard words behind both arrays; the refusals; and the six separate liship_* calls it replaces."""
+"""liship_ritz_tail_f64 (kernels/vector_ops.hip, the reduction op RED_RITZ_TAIL), the fused tail of a subspace iteration, against a numpy model built from
+tests/reduction_model.py: the new r, the new v and the sum of q^2 in every bit, in the tree mode (T = 0) and in the reference-order mode (T chunks summed left to
+right, the partials in chunk order), at every size where the launch takes another shape; guard words behind both arrays; the refusals; the six separate
+liship_* calls it replaces; and an announced liship_krylov_chain step, which it runs wherever liship_sumsq_f64 runs it."""
 import numpy as np
 import pytest
 
@@ -137,6 +138,38 @@ def test_the_sum_is_the_one_liship_sumsq_forms(lib, work):
         check(lib.liship_sumsq_f64(n, dq.ptr, res.ptr, work.ptr, None))
         check(lib.liship_device_synchronize())
         assert same_bits(res.to_host()[:1], [want_sum])
+
+
+@pytest.mark.parametrize("T", [0, 3])
+@pytest.mark.parametrize("n", [3, 4097])                    # one workgroup (no fold to ride in), a fold
+def test_an_announced_step_runs_as_behind_liship_sumsq(lib, work, n, T):
+    """liship.h: "a pending liship_krylov_chain step rides in the fold, as in liship_sumsq_f64" -- with one workgroup and in the reference-order mode too.
+    The state block after {announce, ritz_tail into SUM0} equals, in every bit, the block after {announce, liship_sumsq_f64 of the stored q into SUM0},
+    and nothing stays pending: a flush behind it changes nothing."""
+    import krylov_model as km
+    r, v, sums, s, want_sum = case(n, T)
+    st = km.new_state(rho=0.7310585786300049, rho_old=1.3, bnrm=3.0, tol=1e-300, iter=3.0, nhist=3.0, nrm2=0.125, not_half=0.0)
+    st[19:] = np.arange(19, km.KS_LEN) + 0.5
+    hist = 8
+    check(lib.liship_set_reference_reductions(T))
+
+    def after(launch):
+        dst, dh = DA.from_host(st), DA.from_host(sentinels(hist))
+        check(lib.liship_krylov_chain(km.STEP_CG_RESID, dst.ptr, dh.ptr))
+        launch(dst.ptr + 8 * km.KS_SUM0)
+        check(lib.liship_device_synchronize())
+        return dst, dh, dst.to_host(), dh.to_host()
+
+    dr, dv, dq, dsums = Vec(r), Vec(v), Vec(np.zeros(n)), DA.from_host(np.array(sums))
+    check(lib.liship_axpyz_f64(n, -sums[1], dv.ptr, dr.ptr, dq.ptr, None))          # q, stored
+    _, _, want, want_hist = after(lambda res: check(lib.liship_sumsq_f64(n, dq.ptr, res, work.ptr, None)))
+    dst, dh, got, got_hist = after(lambda res: check(lib.liship_ritz_tail_f64(n, dsums.ptr, dr.ptr, dv.ptr, res, work.ptr, None)))
+    assert same_bits(want[km.KS_SUM0:km.KS_SUM0 + 1], [want_sum]) and want[km.KS_ITER] == 4.0          # the step ran behind liship_sumsq_f64
+    assert same_bits(got, want), np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
+    assert same_bits(got_hist, want_hist)
+    check(lib.liship_krylov_chain_flush(None))
+    check(lib.liship_device_synchronize())
+    assert same_bits(dst.to_host(), got) and same_bits(dh.to_host(), got_hist)
 
 
 @pytest.mark.parametrize("T", [0, 8])
