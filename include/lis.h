@@ -581,6 +581,12 @@ LIS_INT lis_matrix_scale(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR D, LIS_INT actio
  * edited there by a kernel, its host arrays on the host, and nothing crosses the bus (host/lis_shift.c).  The reference keeps this one in its
  * internal header too (src/matrix lis_matrix.h; lis_matrix_ops.c:781) */
 LIS_INT lis_matrix_shift_diagonal(LIS_MATRIX A, LIS_SCALAR sigma);
+/* A <- A - sigma B, the shift of the generalized eigensolvers (lis_matrix_ops.c:833; internal header there too).  The reference forms it through two dense
+ * n x n copies; here the rows are merged by kernels on the HBM copies (host/lis_shift.c, kernels/spgeam.hip) and leave what the dense route leaves: per row the
+ * union of the two patterns in ascending column order, every entry (-sigma) * b + a in two roundings, entries that come out exactly 0.0 dropped, A's storage
+ * type kept.  A->nnz follows; A->ptr / index / value are new arrays afterwards (pointers read before the call are stale), filled from HBM on their first touch.
+ * One rank; neither matrix split; LIS_ERR_ILL_ARG when A and B differ in size.  lis_amd_last_shift_matrix (lis_amd.h) says which path the last call took */
+LIS_INT lis_matrix_shift_matrix(LIS_MATRIX A, LIS_MATRIX B, LIS_SCALAR sigma);
 LIS_INT lis_matrix_convert(LIS_MATRIX Ain, LIS_MATRIX Aout);
 /* A = L + D + U in A->L / A->D / A->U (is_splited): lis_matvec then adds D x first, the L entries, the U entries.  The
  * reference keeps these two in its internal header (src/matrix lis_matrix.h; lis_matrix_ops.c:860, :1052) */

@@ -178,6 +178,12 @@ LIS_INT lis_amd_is_psolve(LIS_MATRIX A, LIS_SCALAR alpha, LIS_INT m, LIS_VECTOR 
 /* 1 when the last lis_solve ran -p is, *m = its -is_m; 0 otherwise, with *m = 0 */
 LIS_INT lis_amd_last_solve_is(LIS_INT *m);
 
+/* the last lis_matrix_shift_matrix (also those inside lis_gesolve): info[0] = 1 when every row was updated where it lay (one launch, A's pattern kept), 0 when A's
+ * three arrays were rebuilt (rows out of order, entries of B outside A's pattern, results that cancelled to 0.0); info[1], info[2] = A's nnz before and after */
+LIS_INT lis_amd_last_shift_matrix(LIS_INT info[3]);
+/* the arrays of A's HBM copy (a CSR matrix, not split; uploads if needed): device pointers, valid until the copy is rebuilt or A is shifted by a matrix */
+LIS_INT lis_amd_matrix_device_csr(LIS_MATRIX A, LIS_INT **dptr, LIS_INT **dindex, LIS_SCALAR **dvalue);
+
 /* vectors */
 LIS_INT lis_amd_vector_sync_host(LIS_VECTOR v);        /* make v->value[] current (D2H if needed)        */
 LIS_INT lis_amd_vector_host_modified(LIS_VECTOR v);    /* v->value[] was written directly: HBM copy stale */

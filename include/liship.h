@@ -432,6 +432,21 @@ int  liship_ritz_tail_f64(int n, const double *sums, double *r, double *v, doubl
 /* value[k] -= sigma for the FIRST stored entry k of each row whose column is the row; a row without one is left alone (lis_matrix_shift_diagonal_csr,
  * src/matrix/lis_matrix_csr.c:566-603, on arrays in HBM; a split matrix's chain rows start with their diagonal term, host/lis_split.c) */
 int  liship_csr_shift_diagonal_f64(int n, const int *ptr, const int *index, double *value, double sigma, void *stream);
+/* A <- A - sigma B on two CSR matrices of n rows in HBM (lis_matrix_shift_matrix, kernels/spgeam.hip): every row of the result holds the union of the two rows'
+ * columns in ascending order, every entry is (-sigma) * b + a with an absent term counting as 0.0 -- the product and the sum rounded once each --, and an entry
+ * that comes out exactly 0.0 is dropped (what the reference's dense route leaves, src/matrix/lis_matrix_ops.c:833-856).  Columns are unique within a row, in
+ * any order.  One lane per row, LISHIP_SHIFT_MATRIX_ROWS rows per workgroup.
+ *   _try   ONE launch.  A row whose result keeps A's layout (A's columns ascending, every surviving entry of B on a column A stores, no result 0.0) is updated in
+ *          avalue[] where it lies: done[r] = 1, count[r] = its length.  Any other row is left untouched: done[r] = 0, count[r] = the length of its result,
+ *          *flag += 1 (*flag is zeroed first, on the stream).  *flag == 0 afterwards: A holds A - sigma B.  count, done: n device ints, flag: one.
+ *   _scan  nptr[0 .. n] = the exclusive scan of count[], *nnz (host) = nptr[n]; scratch: (n / 4096 + 2) long long in HBM.  Waits for the stream.
+ *   _fill  nindex / nvalue (nptr[n] entries each): row r from nptr[r] -- a done row copied from A, any other row merged from A's untouched row and B's. */
+#define LISHIP_SHIFT_MATRIX_ROWS 256
+int  liship_csr_shift_matrix_try_f64(int n, const int *aptr, const int *aindex, double *avalue, const int *bptr, const int *bindex, const double *bvalue,
+                                     double sigma, int *count, int *done, int *flag, void *stream);
+int  liship_csr_shift_matrix_scan(int n, const int *count, int *nptr, long long *scratch, int *nnz, void *stream);
+int  liship_csr_shift_matrix_fill_f64(int n, const int *aptr, const int *aindex, const double *avalue, const int *bptr, const int *bindex, const double *bvalue,
+                                      double sigma, const int *done, const int *nptr, int *nindex, double *nvalue, void *stream);
 /* x *= 1/sqrt(*sumsq) with sumsq in HBM  (lis_vector_nrm2 + lis_vector_scale, lis_solver_gmres.c:229-232) */
 int  liship_scale_inv_norm_f64(int n, const double *sumsq, double *x, void *stream);
 

@@ -198,6 +198,9 @@ _LISHIP = {
     "liship_multidot_f64": (_ci, [_ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp]),
     "liship_ritz_tail_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_csr_shift_diagonal_f64": (_ci, [_ci, _vp, _vp, _vp, _cd, _vp]),
+    "liship_csr_shift_matrix_try_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _cd, _vp, _vp, _vp, _vp]),
+    "liship_csr_shift_matrix_scan": (_ci, [_ci, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_csr_shift_matrix_fill_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _cd, _vp, _vp, _vp, _vp, _vp]),
     "liship_csr_diagonal_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
     "liship_ell_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
     "liship_dia_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),

@@ -254,6 +254,7 @@ _PROTOS = {
     "lis_esolver_get_esolvername": (LIS_INT, [LIS_INT, C.c_char_p]),
     "lis_esolver_output_rhistory": (LIS_INT, [PE, C.c_char_p]),
     "lis_matrix_shift_diagonal": (LIS_INT, [PM, LIS_SCALAR]),
+    "lis_matrix_shift_matrix": (LIS_INT, [PM, PM, LIS_SCALAR]),
     # small dense routines of the Lanczos / Arnoldi eigensolvers (lis.h:943, 953, 955)
     "lis_array_nrm2": (LIS_INT, [LIS_INT, P_DBL, P_DBL]),
     "lis_array_cgs": (LIS_INT, [LIS_INT, P_DBL, P_DBL, P_DBL]),
@@ -291,6 +292,8 @@ _AMD_PROTOS = {
     "lis_amd_sainv_info": (LIS_INT, [PM, C.c_double, P_DBL]),
     "lis_amd_is_psolve": (LIS_INT, [PM, C.c_double, LIS_INT, PV, PV, LIS_INT]),
     "lis_amd_last_solve_is": (LIS_INT, [P_INT]),
+    "lis_amd_last_shift_matrix": (LIS_INT, [P_INT]),
+    "lis_amd_matrix_device_csr": (LIS_INT, [PM, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
 }
 
 

@@ -13,8 +13,14 @@
  * _li.c, _ai.c), the getters only they fill, and the small dense QR they call (lis_array.c).  Their device chains and the fused tail of a subspace iteration
  * (liship_ritz_tail_f64) stand in the section "several eigenpairs per solve" below.
  *
- * Refused, with LIS_ERR_NOT_IMPLEMENTED and before A or x is touched: -e si | li | ai with -ss 1 (the default: one pair is what -e pi / -e ii serve), -e si with
- * an -ie other than pi or ii, every generalized solver (-e gpi .. gai, lis_gesolve with a B), a job of several ranks.
+ * Served as well: the generalized problem A x = lambda B x through lis_gesolve with a matrix B and -e gpi | gii | grqi | gcr (lis_esolver_pi.c:305-464,
+ * _ii.c:357-520, _rqi.c:350-501, _cg.c:1063-1265), in the section "the generalized problem" below.  Their shift is lis_matrix_shift_matrix (lis_shift.c,
+ * kernels/spgeam.hip): A - sigma B merged row by row in HBM where the reference goes through two dense n x n copies.
+ *
+ * Refused, with LIS_ERR_NOT_IMPLEMENTED and before A, B or x is touched: -e si | li | ai with -ss 1 (the default: one pair is what -e pi / -e ii serve), -e si with
+ * an -ie other than pi or ii, a B together with a standard -e (the reference silently ignores B there), a generalized -e through lis_esolve or with B = NULL (the
+ * reference's loops multiply by that NULL), -e gcg (the reference's loop never updates x and ends in NaN: -e gcr is the one that works), -e gsi | gli | gai, a
+ * job of several ranks.
  * -ef quad | switch answers as lis_solve does for -f quad.
  *
  * Deliberate differences from the reference, all outside a converging solve: the arrays of the object start zeroed instead of holding heap contents; a
@@ -77,6 +83,7 @@ static void work_destroy(LIS_ESOLVER e)
 }
 
 static int is_multi(LIS_INT nesolver) { return nesolver == LIS_ESOLVER_SI || nesolver == LIS_ESOLVER_LI || nesolver == LIS_ESOLVER_AI; }
+static int is_generalized(LIS_INT nesolver) { return nesolver >= LIS_ESOLVER_GPI && nesolver <= LIS_ESOLVER_GAI; }
 static int is_multi_or_generalized(LIS_INT nesolver) { return is_multi(nesolver) || nesolver == LIS_ESOLVER_GSI || nesolver == LIS_ESOLVER_GLI || nesolver == LIS_ESOLVER_GAI; }
 
 /* the arrays of the object and the eigenvectors an earlier solve left: evector has two slots more than vectors and is filled from slot 0, so the first NULL ends them */
@@ -350,14 +357,15 @@ static void inner_destroy(ectx_t *c)
  * lis_solve's own passes do NOT give the same bits fused and unfused in the tree mode (the product's fused dot epilogue sums in another order than
  * liship_dot_f64: `lis_solve -i cg` on the 10 x 10 Laplacian ends with another x under LIS_AMD_NO_FUSION=1), so inside an esolve that switch selects the
  * esolver's own passes only -- the Gram blocks -- and a fused and an unfused esolve agree in every bit (tests/test_esolve_gpu.py) */
-static LIS_INT inner_solve(ectx_t *c, LIS_VECTOR b, LIS_VECTOR y, int whole)
+static LIS_INT inner_solve_on(ectx_t *c, LIS_MATRIX M, LIS_VECTOR b, LIS_VECTOR y, int whole)
 {
 	const int held = lisg.no_fusion;
 	lisg.no_fusion = 0;
-	const LIS_INT err = whole ? lis_solve(c->A, b, y, c->solver) : lis_solve_kernel(c->A, b, y, c->solver, c->precon);
+	const LIS_INT err = whole ? lis_solve(M, b, y, c->solver) : lis_solve_kernel(M, b, y, c->solver, c->precon);
 	lisg.no_fusion = held;
 	return err;
 }
+static LIS_INT inner_solve(ectx_t *c, LIS_VECTOR b, LIS_VECTOR y, int whole) { return inner_solve_on(c, c->A, b, y, whole); }
 
 /* the preconditioner of cg / cr made ready for lis_psolve calls outside a solve: the row's begin, as lis_solve_kernel runs it */
 static LIS_INT psolve_begin(ectx_t *c)
@@ -1073,6 +1081,272 @@ done:
 	return err;
 }
 
+/* ================================================================== the generalized problem A x = lambda B x: power, inverse, Rayleigh quotient, CR
+ * The reference's four loops that work (lis_egcg never updates x or p from its Ritz vector and ends in NaN: refused in lis_gesolve), statement for statement
+ * in the helpers above.  A - sigma B is lis_matrix_shift_matrix (lis_shift.c): kernels on the HBM copies.  Sums that share a vector go through one
+ * lisd_multidot pass -- rho and <B v, B v> of -e grqi, the three dot groups of -e gcr --, the bits of the separate dots (LIS_AMD_NO_FUSION=1 runs those). */
+static LIS_INT gshift_back(LIS_MATRIX A, LIS_MATRIX B, LIS_SCALAR sigma, LIS_INT err)
+{
+	const LIS_INT e2 = lis_matrix_shift_matrix(A, B, -sigma);
+	return (e2 && (!err || err == LIS_MAXITER)) ? e2 : err;
+}
+
+/* ------------------------------------------------------------------ generalized power iteration, lis_esolver_pi.c:305-464 (the preconditioner is B's, the solves are with B) */
+static LIS_INT lis_egpi(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 1);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	LIS_VECTOR v = esolver->x, w = esolver->work[0], y = esolver->work[1], q = esolver->work[2];
+	LIS_SCALAR eta, theta = 0.0;
+	LIS_REAL nrm2, resid = 0.0;
+	LIS_INT err = 0, iter = 0, iter2, code = LIS_MAXITER;
+	int shifted = 0;
+	if (esolver->options[LIS_EOPTIONS_INITGUESS_ONES]) ETRY(lis_vector_set_all(1.0, v));
+	if (c->oshift != 0.0) { ETRY(lis_matrix_shift_matrix(A, B, c->oshift)); shifted = 1; }
+	eshift_banner(c);
+	ETRY(inner_solver(c, "-i bicg -p none"));
+	c->solver->A = B;
+	ETRY(lis_precon_create(c->solver, &c->precon));
+	while (iter < c->emaxiter) {
+		iter = iter + 1;
+		ETRY(lis_vector_nrm2(v, &nrm2));                     /* v = v / ||v||_2 */
+		ETRY(lis_vector_scale(1.0 / nrm2, v));
+		ETRY(lis_matvec(A, v, w));                           /* w = A * v */
+		ETRY(lis_vector_dot(v, w, &eta));                    /* v = v / <v,w>^1/2, w = w / <v,w>^1/2 */
+		eta = sqrt(eta);
+		ETRY(lis_vector_scale(1.0 / eta, v));
+		ETRY(lis_vector_scale(1.0 / eta, w));
+		ETRY(inner_solve_on(c, B, w, y, 0));                 /* y = B^-1 * w */
+		lis_solver_get_iter(c->solver, &iter2);
+		ETRY(lis_vector_dot(w, y, &theta));                  /* theta = <w,y> */
+		ETRY(lis_vector_axpyz(-theta, v, y, q));             /* resid = ||y - theta * v||_2 / |theta| */
+		ETRY(lis_vector_nrm2(q, &resid));
+		resid = resid / fabs(theta);
+		ETRY(lis_vector_copy(y, v));                         /* v = y */
+		inner_times(c);
+		enote(c, iter, resid);
+		if (c->tol >= resid) { code = LIS_SUCCESS; break; }
+	}
+	esolver->retcode = code;
+	esolver->iter[0] = iter;
+	esolver->resid[0] = resid;
+	esolver->evalue[0] = theta + c->oshift;
+	ETRY(normalize(v));
+	err = code;
+done:
+	if (shifted) err = gshift_back(A, B, c->oshift, err);
+	inner_destroy(c);
+	return err;
+}
+
+/* ------------------------------------------------------------------ generalized inverse iteration, lis_esolver_ii.c:357-520 */
+static LIS_INT lis_egii(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 1);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	LIS_VECTOR v = esolver->x, w = esolver->work[0], y = esolver->work[1], q = esolver->work[2];
+	LIS_SCALAR eta, theta = 0.0;
+	LIS_REAL nrm2, resid = 0.0;
+	LIS_INT err = 0, iter = 0, iter2, code = LIS_MAXITER;
+	int shifted = 0;
+	if (esolver->options[LIS_EOPTIONS_INITGUESS_ONES]) ETRY(lis_vector_set_all(1.0, v));
+	if (c->oshift != 0.0) { ETRY(lis_matrix_shift_matrix(A, B, c->oshift)); shifted = 1; }
+	eshift_banner(c);
+	ETRY(inner_solver(c, "-i bicg -p none"));
+	c->solver->A = A;
+	ETRY(lis_precon_create(c->solver, &c->precon));
+	while (iter < c->emaxiter) {
+		iter = iter + 1;
+		ETRY(lis_vector_nrm2(v, &nrm2));                     /* v = v / ||v||_2 */
+		ETRY(lis_vector_scale(1.0 / nrm2, v));
+		ETRY(lis_matvec(B, v, w));                           /* w = B * v */
+		ETRY(lis_vector_dot(w, v, &eta));                    /* v = v / <w,v>^1/2, w = w / <w,v>^1/2 */
+		eta = sqrt(eta);
+		ETRY(lis_vector_scale(1.0 / eta, v));
+		ETRY(lis_vector_scale(1.0 / eta, w));
+		ETRY(inner_solve(c, w, y, 0));                       /* y = A^-1 * w */
+		lis_solver_get_iter(c->solver, &iter2);
+		ETRY(lis_vector_dot(w, y, &theta));                  /* theta = <w,y> */
+		ETRY(lis_vector_axpyz(-theta, v, y, q));             /* resid = ||y - theta * v||_2 / |theta| */
+		ETRY(lis_vector_nrm2(q, &resid));
+		resid = resid / fabs(theta);
+		ETRY(lis_vector_copy(y, v));                         /* v = y */
+		inner_times(c);
+		enote(c, iter, resid);
+		if (c->tol >= resid) { code = LIS_SUCCESS; break; }
+	}
+	esolver->retcode = code;
+	esolver->iter[0] = iter;
+	esolver->resid[0] = resid;
+	esolver->evalue[0] = 1.0 / theta + c->oshift;
+	ETRY(normalize(v));
+	err = code;
+done:
+	if (shifted) err = gshift_back(A, B, c->oshift, err);
+	inner_destroy(c);
+	return err;
+}
+
+/* ------------------------------------------------------------------ generalized Rayleigh quotient iteration, lis_esolver_rqi.c:350-501 (no -shift: rho is the shift;
+ * the preconditioner is made once, of the unshifted A) */
+static LIS_INT lis_egrqi(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 0);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	LIS_VECTOR v = esolver->x, w = esolver->work[0], y = esolver->work[1];
+	LIS_SCALAR theta, eta, dotww, rho = 0.0;
+	LIS_REAL nrm2, resid = 0.0;
+	LIS_INT err = 0, iter = 0, iter2, code = LIS_MAXITER;
+	int shifted = 0;
+	if (esolver->options[LIS_EOPTIONS_INITGUESS_ONES]) ETRY(lis_vector_set_all(1.0, v));
+	ETRY(inner_solver(c, "-i bicg -p none"));
+	c->solver->A = A;
+	ETRY(lis_precon_create(c->solver, &c->precon));
+	ETRY(lis_vector_nrm2(v, &nrm2));                         /* v = v / ||v||_2 */
+	ETRY(lis_vector_scale(1.0 / nrm2, v));
+	ETRY(lis_matvec(B, v, w));                               /* w = B * v */
+	ETRY(lis_matvec(A, v, y));                               /* rho = <B*v,A*v> / <B*v,B*v>: two sums over {w, y}, one pass */
+	{
+		LIS_VECTOR vs[2] = {w, y};
+		static const int pairs[2][2] = {{0, 1}, {0, 0}};
+		double g[2];
+		ETRY(gram(v->n, 2, vs, 2, pairs, g));
+		rho = g[0]; dotww = g[1];
+	}
+	rho = rho / dotww;
+	while (iter < c->emaxiter) {
+		iter = iter + 1;
+		ETRY(lis_matrix_shift_matrix(A, B, rho));            /* y = (A - rho * B)^-1 * w */
+		shifted = 1;
+		ETRY(inner_solve(c, w, y, 0));
+		ETRY(lis_matrix_shift_matrix(A, B, -rho));
+		shifted = 0;
+		lis_solver_get_iter(c->solver, &iter2);
+		ETRY(lis_vector_dot(w, y, &theta));                  /* theta = <w,y> */
+		ETRY(lis_matvec(B, y, w));                           /* w = B * y */
+		ETRY(lis_vector_dot(w, y, &eta));                    /* eta = <w,y>^1/2 */
+		eta = sqrt(eta);
+		ETRY(lis_vector_scale(1.0 / eta, y));                /* v = y / eta */
+		ETRY(lis_vector_copy(y, v));
+		ETRY(lis_vector_scale(1.0 / eta, w));                /* w = w / eta */
+		rho = rho + theta / (eta * eta);                     /* rho = rho + theta / eta^2 */
+		resid = 1.0 / fabs(theta);                           /* resid = 1 / |theta| */
+		enote(c, iter, resid);
+		inner_times(c);
+		if (c->tol >= resid) { code = LIS_SUCCESS; break; }
+	}
+	esolver->retcode = code;
+	esolver->iter[0] = iter;
+	esolver->resid[0] = resid;
+	esolver->evalue[0] = rho;
+	ETRY(normalize(v));
+	err = code;
+done:
+	if (shifted) (void)lis_matrix_shift_matrix(A, B, -rho);  /* an inner solve failed between the two shifts: A goes back */
+	inner_destroy(c);
+	return err;
+}
+
+/* ------------------------------------------------------------------ generalized CR, lis_esolver_cg.c:1063-1265 */
+static LIS_INT lis_egcr(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 1);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	LIS_VECTOR x = esolver->x;
+	LIS_VECTOR r = esolver->work[0], p = esolver->work[1], w = esolver->work[2], Ax = esolver->work[3], Ap = esolver->work[4], Aw = esolver->work[5];
+	LIS_VECTOR Bx = esolver->work[6], Bp = esolver->work[7], Bw = esolver->work[8];
+	LIS_SCALAR lambda = 0.0, alpha, beta;
+	LIS_SCALAR rAp, rBp, BxBx, ApAp, ApBp, BpBp, AwAp, AwBp, ApBw, BwBp;
+	LIS_REAL nrm2, resid = 0.0;
+	LIS_INT err = 0, iter = 0;
+	double ptime = 0.0, time;
+	int shifted = 0;
+	static const int xpairs[2][2] = {{0, 1}, {1, 1}};        /* <A*x,B*x>, <B*x,B*x> over {Ax, Bx} */
+	if (esolver->options[LIS_EOPTIONS_INITGUESS_ONES]) ETRY(lis_vector_set_all(1.0, x));
+	if (c->oshift != 0.0) { ETRY(lis_matrix_shift_matrix(A, B, c->oshift)); shifted = 1; }
+	eshift_banner(c);
+	ETRY(lis_vector_nrm2(x, &nrm2));
+	ETRY(lis_vector_scale(1.0 / nrm2, x));
+	ETRY(lis_matvec(A, x, Ax));
+	ETRY(lis_matvec(B, x, Bx));
+	ETRY(inner_solver(c, "-i bicg -p none"));
+	c->solver->A = A;                                        /* lis_solve_setup(A, solver): the solver made ready for preconditioning */
+	ETRY(lis_precon_create(c->solver, &c->precon));
+	ETRY(psolve_begin(c));
+	{	/* lambda = <A*x,B*x> / <B*x,B*x> */
+		LIS_VECTOR vs[2] = {Ax, Bx};
+		double g[2];
+		ETRY(gram(x->n, 2, vs, 2, xpairs, g));
+		lambda = g[0]; BxBx = g[1];
+	}
+	lambda = lambda / BxBx;
+	ETRY(lis_vector_axpyz(-lambda, Bx, Ax, r));              /* r = lambda * B * x - A * x */
+	ETRY(lis_vector_scale(-1.0, r));
+	ETRY(lis_vector_copy(r, p));
+	ETRY(lis_matvec(A, p, Ap));
+	ETRY(lis_matvec(B, p, Bp));
+	while (iter < c->emaxiter) {
+		iter = iter + 1;
+		{	/* alpha = (<r,A*p> - lambda * <r,B*p>) / (<A*p,A*p> - 2 * lambda * <A*p,B*p> + lambda^2 * <B*p,B*p>): five sums, one pass */
+			LIS_VECTOR vs[3] = {r, Ap, Bp};
+			static const int pairs[5][2] = {{0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+			double g[5];
+			ETRY(gram(x->n, 3, vs, 5, pairs, g));
+			rAp = g[0]; rBp = g[1]; ApAp = g[2]; ApBp = g[3]; BpBp = g[4];
+		}
+		alpha = (rAp - lambda * rBp) / (ApAp - 2.0 * lambda * ApBp + lambda * lambda * BpBp);
+		ETRY(lis_vector_axpy(alpha, p, x));                  /* x = x + alpha * p */
+		ETRY(lis_matvec(A, x, Ax));                          /* lambda = <A*x,B*x> / <B*x,B*x> */
+		ETRY(lis_matvec(B, x, Bx));
+		{
+			LIS_VECTOR vs[2] = {Ax, Bx};
+			double g[2];
+			ETRY(gram(x->n, 2, vs, 2, xpairs, g));
+			lambda = g[0]; BxBx = g[1];
+		}
+		lambda = lambda / BxBx;
+		ETRY(lis_vector_axpyz(-lambda, Bx, Ax, r));          /* r = lambda * B * x - A * x */
+		ETRY(lis_vector_scale(-1.0, r));
+		time = lis_wtime();
+		ETRY(psolve(c, r, w));                               /* w = M^-1 * r */
+		ptime += lis_wtime() - time;
+		ETRY(lis_matvec(A, w, Aw));
+		ETRY(lis_matvec(B, w, Bw));
+		{	/* beta = -[<A*w,A*p> - lambda * (<A*w,B*p> + <A*p,B*w>) + lambda^2 * <B*w,B*p>] / [the denominator of alpha]: four sums, one pass */
+			LIS_VECTOR vs[4] = {Aw, Ap, Bp, Bw};
+			static const int pairs[4][2] = {{0, 1}, {0, 2}, {1, 3}, {3, 2}};
+			double g[4];
+			ETRY(gram(x->n, 4, vs, 4, pairs, g));
+			AwAp = g[0]; AwBp = g[1]; ApBw = g[2]; BwBp = g[3];
+		}
+		beta = -(AwAp - lambda * (AwBp + ApBw) + lambda * lambda * BwBp) / (ApAp - 2.0 * lambda * ApBp + lambda * lambda * BpBp);
+		ETRY(lis_vector_xpay(w, beta, p));                   /* p = w + beta * p */
+		ETRY(lis_vector_xpay(Aw, beta, Ap));                 /* A*p = A*w + beta * A*p */
+		ETRY(lis_vector_xpay(Bw, beta, Bp));                 /* B*p = B*w + beta * B*p */
+		ETRY(lis_vector_nrm2(r, &nrm2));                     /* convergence check */
+		resid = nrm2 / fabs(lambda);
+		enote(c, iter, resid);
+		if (resid < c->tol) break;
+	}
+	esolver->iter[0] = iter;
+	esolver->resid[0] = resid;
+	esolver->evalue[0] = lambda + c->oshift;
+	ETRY(normalize(x));
+	esolver->ptime = ptime;
+	esolver->itime = c->solver->itime; esolver->p_c_time = c->solver->p_c_time; esolver->p_i_time = c->solver->p_i_time;
+done:
+	if (c->solver) c->solver->precon = NULL;
+	inner_destroy(c);
+	if (shifted) { const LIS_INT e2 = lis_matrix_shift_matrix(A, B, -c->oshift); if (e2 && !err) err = e2; }
+	if (err) return err;
+	esolver->retcode = (resid < c->tol) ? LIS_SUCCESS : LIS_MAXITER;
+	return esolver->retcode;
+}
+
 /* ------------------------------------------------------------------ lis_esolve / lis_gesolve, ref :263-666 */
 static LIS_INT work_alloc(LIS_ESOLVER e, LIS_INT count)
 {	/* lis_e<xx>_malloc_work: NWORK duplicates of A's row layout */
@@ -1096,16 +1370,35 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	if (x == NULL) return LISI_ERR(LIS_ERR_ILL_ARG, "vector x is undefined\n");
 	if (A->n != x->n) return LIS_ERR_ILL_ARG;
 	if (A->gn <= 0) return LISI_ERR(LIS_ERR_ILL_ARG, "Size n(=%D) of matrix A is less than 0\n", A->gn);
+	if (B != NULL) {                                         /* ref :323-336 */
+		LISCHK(lisi_matrix_check(B, LISI_CHECK_ASSEMBLED));
+		if (B->n != x->n) return LISI_ERR(LIS_ERR_ILL_ARG, "matrix B (n = %D) and vector x (n = %D) differ in size\n", B->n, x->n);
+		if (B->gn <= 0) return LISI_ERR(LIS_ERR_ILL_ARG, "Size n(=%D) of matrix B is less than 0\n", B->gn);
+	}
 	const LIS_INT nesolver = esolver->options[LIS_EOPTIONS_ESOLVER], ss = esolver->options[LIS_EOPTIONS_SUBSPACE], mode = esolver->options[LIS_EOPTIONS_MODE];
 	const LIS_INT emaxiter = esolver->options[LIS_EOPTIONS_MAXITER], output = esolver->options[LIS_EOPTIONS_OUTPUT];
 	const LIS_INT estorage = esolver->options[LIS_EOPTIONS_STORAGE], eblock = esolver->options[LIS_EOPTIONS_STORAGE_BLOCK];
 	const LIS_INT eprecision = esolver->options[LIS_EOPTIONS_PRECISION];
 	if (nesolver < 1 || nesolver > LIS_ESOLVER_LEN) return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_ESOLVER is %D (Set between 1 to %D)\n", nesolver, LIS_ESOLVER_LEN);
 	/* what is not served, said before A or x is touched */
-	if (B != NULL) { esolver->retcode = LIS_ERR_NOT_IMPLEMENTED; return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "generalized eigenproblems (lis_gesolve with a matrix B) are not served by liblis_amd\n"); }
-	if (nesolver > LIS_ESOLVER_CR && !is_multi(nesolver)) {
+	if (B != NULL && !is_generalized(nesolver)) {             /* (the reference runs the standard loop and never reads B) */
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd (pi, ii, rqi, cg, cr, si, li, ai)\n", esolver_names[nesolver], esolver_keys[nesolver - 1]);
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "generalized eigenproblems (lis_gesolve with a matrix B) are served by -e gpi | gii | grqi | gcr: %s (-e %s) is a standard eigensolver, which would ignore B\n",
+		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
+	}
+	if (is_generalized(nesolver) && B == NULL) {              /* (the reference's loops multiply by that NULL) */
+		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd without a matrix B: lis_esolve serves pi, ii, rqi, cg, cr, si, li, ai, lis_gesolve with a B gpi, gii, grqi, gcr\n",
+		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
+	}
+	if (nesolver == LIS_ESOLVER_GCG) {
+		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver Generalized CG (-e gcg) is not served by liblis_amd: the reference's loop never updates x from its Ritz vector and ends in NaN at every thread count; -e gcr is the generalized solver of that family that works\n");
+	}
+	if (nesolver == LIS_ESOLVER_GSI || nesolver == LIS_ESOLVER_GLI || nesolver == LIS_ESOLVER_GAI) {
+		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd: several pairs of a generalized problem are not served yet (one pair: gpi, gii, grqi, gcr)\n",
+		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
 	}
 	if (is_multi(nesolver) && ss == 1) {
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
@@ -1129,6 +1422,10 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "inner eigensolver %D (-ie) is not served by liblis_amd for -e %s (%s)\n", niesolver, esolver_keys[nesolver - 1],
 			                nesolver == LIS_ESOLVER_SI ? "pi, ii" : "pi, ii, rqi, cg, cr");
 		}
+	}
+	if (B != NULL && (A->is_splited || B->is_splited || !lisi_format_served(B->matrix_type) || B->np != B->n || A->np != A->n)) {
+		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_gesolve: A and B must be unsplit matrices in a served storage format without ghost columns (lis_matrix_shift_matrix)\n");
 	}
 	if (MDEV(A)->device_only && A->matrix_type != LIS_MATRIX_CSR) { esolver->retcode = LIS_ERR_NOT_IMPLEMENTED; return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "a matrix that lives in HBM only is shifted in CSR storage\n"); }
 	esolver->eprecision = eprecision;
@@ -1162,7 +1459,7 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	/* -estorage: the caller's matrix itself is converted and stays converted, ref :553-570 (as -storage in lis_solve) */
 	if (estorage > 0 && A->matrix_type != estorage && (err = lisi_matrix_retype(A, estorage, estorage == LIS_MATRIX_BSR ? eblock : 0))) goto fail;
 
-	esolver->A = A; esolver->B = NULL;
+	esolver->A = A; esolver->B = B;
 	if (output) {
 		lis_printf(LIS_COMM_WORLD, "precision             : %s\n", eprecision_keys[eprecision]);
 		lis_printf(LIS_COMM_WORLD, "eigensolver           : %s\n", esolver_names[nesolver]);
@@ -1172,7 +1469,8 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	}
 	double time = lis_wtime();
 	esolver->ptime = 0; esolver->itime = 0; esolver->p_c_time = 0; esolver->p_i_time = 0;
-	if ((err = work_alloc(esolver, nesolver == LIS_ESOLVER_CG || nesolver == LIS_ESOLVER_CR ? 6 : nesolver == LIS_ESOLVER_SI ? 4 + ss : is_multi(nesolver) ? 2 + ss : 2))) goto fail;
+	if ((err = work_alloc(esolver, nesolver == LIS_ESOLVER_CG || nesolver == LIS_ESOLVER_CR ? 6 : nesolver == LIS_ESOLVER_SI ? 4 + ss : is_multi(nesolver) ? 2 + ss :
+	                               nesolver == LIS_ESOLVER_GCR ? 9 : is_generalized(nesolver) ? 3 : 2))) goto fail;
 	esolver->x = xx; esolver->xx = x;
 
 	switch (nesolver) {
@@ -1183,6 +1481,10 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	case LIS_ESOLVER_SI:  err = lis_esi(esolver); break;
 	case LIS_ESOLVER_LI:  err = lis_eli(esolver); break;
 	case LIS_ESOLVER_AI:  err = lis_eai(esolver); break;
+	case LIS_ESOLVER_GPI: err = lis_egpi(esolver); break;
+	case LIS_ESOLVER_GII: err = lis_egii(esolver); break;
+	case LIS_ESOLVER_GRQI: err = lis_egrqi(esolver); break;
+	case LIS_ESOLVER_GCR: err = lis_egcr(esolver); break;
 	default:              err = lis_ecr(esolver); break;
 	}
 	esolver->retcode = err;

@@ -265,6 +265,9 @@ void bsr_to_rows(int n, int bnr, int bnc, const int *__restrict__ bptr, const in
 }
 } // namespace
 
+// the scan above for the other kernel files (spgeam.hip): declared where it is used, as the liship_internal_* of common.hpp
+int liship_internal_exclusive_scan(int m, const int *count, int *out, long long *scratch, void *stream) { return exclusive_scan(m, count, out, scratch, as_stream(stream)); }
+
 // rptr: n + 1 ints; ridx / rval: bnnz * bnr * bnc entries (fewer are used when the last block row is padded).  All device pointers.
 extern "C" int liship_bsr_to_rows(int n, int bnr, int bnc, const int *bptr, const int *bindex, const double *value, int *rptr, int *rindex, double *rvalue, void *stream)
 {
