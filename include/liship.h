@@ -449,6 +449,17 @@ int  liship_csr_shift_matrix_fill_f64(int n, const int *aptr, const int *aindex,
                                       double sigma, const int *done, const int *nptr, int *nindex, double *nvalue, void *stream);
 /* x *= 1/sqrt(*sumsq) with sumsq in HBM  (lis_vector_nrm2 + lis_vector_scale, lis_solver_gmres.c:229-232) */
 int  liship_scale_inv_norm_f64(int n, const double *sumsq, double *x, void *stream);
+/* The pair passes: two vectors scaled by one factor in ONE walk (vector_pass<NT, VEC, 2, 2>, kernels/vector_pass.hpp: the 16 B walk when all four arrays are
+ * 16 B aligned, else the 8 B walk; non-temporal loads beyond the Infinity Cache).  Each result is one rounded product, so both give the bits of the separate calls.
+ *   liship_scale2_inv_sqrt_f64: a = 1.0 / sqrt(*s), formed once per lane from the HBM value as liship_scale_inv_norm_f64 forms it (no fabs: *s < 0 gives NaN
+ *     everywhere); v[i] = a * v[i]; w[i] = a * w[i].  Behind liship_dot_f64(..., s) it is `eta = sqrt(<v,w>); scale(1/eta, v); scale(1/eta, w)` of the generalized
+ *     subspace iteration (lis_esolver_si.c:604-607) in one launch and with no host wait.
+ *   liship_scale2_to_f64: out0[i] = alpha * in0[i]; out1[i] = alpha * in1[i] -- `copy r -> w; copy q -> v; scale w; scale v` of the generalized Lanczos
+ *     iteration (lis_esolver_li.c:546-549): one launch and 4 n-vector streams for four launches and 8.
+ * The two outputs must not overlap, and an output may meet an input only as its own input, whole (out0 == in0, out1 == in1).  Any other overlap, v == w, s inside
+ * v or w, a NULL array or n <= 0: LISHIP_ERR_ARG with nothing launched. */
+int  liship_scale2_inv_sqrt_f64(int n, const double *s, double *v, double *w, void *stream);
+int  liship_scale2_to_f64(int n, double alpha, const double *in0, const double *in1, double *out0, double *out1, void *stream);
 
 /* ------------------------------------------------------------------ device-driven Krylov loops
  * The scalars of CG / BiCGSTAB (rho, alpha, beta, omega, the residual norm, the iteration count and the

@@ -185,6 +185,8 @@ _LISHIP = {
     "liship_axpy_sumsq_dot_f64": (_ci, [_ci, _cd, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_mgs_step_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_scale_inv_norm_f64": (_ci, [_ci, _vp, _vp, _vp]),
+    "liship_scale2_inv_sqrt_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
+    "liship_scale2_to_f64": (_ci, [_ci, _cd, _vp, _vp, _vp, _vp, _vp]),
     "liship_lincomb_f64": (_ci, [_ci, _ci, _vp, _vp, _ci, _vp, _vp]),
     "liship_reduce_work_bytes": (_sz, []),
     "liship_set_reference_reductions": (_ci, [_ci]),

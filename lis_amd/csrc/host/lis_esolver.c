@@ -17,9 +17,14 @@
  * _ii.c:357-520, _rqi.c:350-501, _cg.c:1063-1265), in the section "the generalized problem" below.  Their shift is lis_matrix_shift_matrix (lis_shift.c,
  * kernels/spgeam.hip): A - sigma B merged row by row in HBM where the reference goes through two dense n x n copies.
  *
- * Refused, with LIS_ERR_NOT_IMPLEMENTED and before A, B or x is touched: -e si | li | ai with -ss 1 (the default: one pair is what -e pi / -e ii serve), -e si with
- * an -ie other than pi or ii, a B together with a standard -e (the reference silently ignores B there), a generalized -e through lis_esolve or with B = NULL (the
- * reference's loops multiply by that NULL), -e gcg (the reference's loop never updates x and ends in NaN: -e gcr is the one that works), -e gsi | gli | gai, a
+ * Served as well: several pairs of the generalized problem -- -e gsi (-ige gpi | gii), -e gli and -e gai (-ige gpi | gii | grqi | gcr) with -ss >= 2
+ * (lis_esolver_si.c:456-719, _li.c:456-694, _ai.c:491-750), in the section "several pairs of the generalized problem" below, with the two pair passes
+ * liship_scale2_inv_sqrt_f64 and liship_scale2_to_f64 (kernels/vector_ops.hip).  Lanczos and Arnoldi refine each mode through lis_gesolve with -ige's solver.
+ *
+ * Refused, with LIS_ERR_NOT_IMPLEMENTED and before A, B or x is touched: -e si | li | ai | gsi | gli | gai with -ss 1 (the default: one pair is what -e pi / -e ii
+ * and -e gpi / -e gii serve), -e si with an -ie other than pi or ii, -e gsi with an -ige other than gpi or gii (the reference's loop then applies neither matrix),
+ * -e gli | gai with -ige gcg or a standard solver, a B together with a standard -e (the reference silently ignores B there), a generalized -e through lis_esolve
+ * or with B = NULL (the reference's loops multiply by that NULL), -e gcg (the reference's loop never updates x and ends in NaN: -e gcr is the one that works), a
  * job of several ranks.
  * -ef quad | switch answers as lis_solve does for -f quad.
  *
@@ -84,7 +89,8 @@ static void work_destroy(LIS_ESOLVER e)
 
 static int is_multi(LIS_INT nesolver) { return nesolver == LIS_ESOLVER_SI || nesolver == LIS_ESOLVER_LI || nesolver == LIS_ESOLVER_AI; }
 static int is_generalized(LIS_INT nesolver) { return nesolver >= LIS_ESOLVER_GPI && nesolver <= LIS_ESOLVER_GAI; }
-static int is_multi_or_generalized(LIS_INT nesolver) { return is_multi(nesolver) || nesolver == LIS_ESOLVER_GSI || nesolver == LIS_ESOLVER_GLI || nesolver == LIS_ESOLVER_GAI; }
+static int is_gmulti(LIS_INT nesolver) { return nesolver == LIS_ESOLVER_GSI || nesolver == LIS_ESOLVER_GLI || nesolver == LIS_ESOLVER_GAI; }
+static int is_multi_or_generalized(LIS_INT nesolver) { return is_multi(nesolver) || is_gmulti(nesolver); }
 
 /* the arrays of the object and the eigenvectors an earlier solve left: evector has two slots more than vectors and is filled from slot 0, so the first NULL ends them */
 static void arrays_free(LIS_ESOLVER e)
@@ -225,7 +231,7 @@ LIS_INT lis_esolver_output_rhistory(LIS_ESOLVER e, char *filename)
  * holds no ended solve -- never run, refused, failed -- every getter answers LIS_ERR_ILL_ARG */
 static LIS_INT subspace_only(const char *what)
 {
-	return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "%s is filled by the subspace, Lanczos and Arnoldi eigensolvers only (-e si | li | ai)\n", what);
+	return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "%s is filled by the subspace, Lanczos and Arnoldi eigensolvers only (-e si | li | ai | gsi | gli | gai)\n", what);
 }
 static LIS_INT multi_filled(LIS_ESOLVER e, const char *what, LIS_INT mode, int vectors)
 {
@@ -753,6 +759,31 @@ static int chain_ready(LIS_INT n, LIS_VECTOR a, LIS_VECTOR b)
 	return (((uintptr_t)pa | (uintptr_t)pb) & 15u) == 0;
 }
 
+/* QR factorization V*R = Z for starting vector Z of the two subspace iterations: v(j) against v(1) .. v(j-1), dot then axpy, pair by pair (lis_esolver_si.c:248-252,
+ * :589-593) -- as one chain in HBM, or the lis_vector_* calls */
+static LIS_INT orthogonalise(LIS_INT n, LIS_INT j, LIS_VECTOR *v, int fused, double *hdev, double **dv)
+{
+	LIS_INT err = 0, k;
+	LIS_SCALAR dot;
+	if (fused && j > 1) {
+		double *vj;
+		ETRY(lisd_vec_in(v[j], &vj));
+		for (k = 1; k < j; k++) ETRY(lisd_vec_in(v[k], &dv[k - 1]));
+		EHIP(liship_dot_f64(n, vj, dv[0], hdev, lisg.reduce_work, lisg.stream));
+		ETRY(lisd_mgs_chain(n, j - 1, dv, vj, hdev));
+		EHIP(liship_scale_to_f64(1, -1.0, hdev + j - 2, hdev + j - 1, lisg.stream));      /* the last coefficient negated in HBM: the axpy below adds */
+		EHIP(liship_axpy_dev_f64(n, hdev + j - 1, dv[j - 2], vj, lisg.stream));
+		ETRY(lisd_vec_done(v[j]));
+	} else {
+		for (k = 1; k < j; k++) {
+			ETRY(lis_vector_dot(v[j], v[k], &dot));
+			ETRY(lis_vector_axpy(-dot, v[k], v[j]));
+		}
+	}
+done:
+	return err;
+}
+
 /* ------------------------------------------------------------------ subspace iteration, lis_esolver_si.c:137-370 */
 static LIS_INT lis_esi(LIS_ESOLVER esolver)
 {
@@ -761,9 +792,9 @@ static LIS_INT lis_esi(LIS_ESOLVER esolver)
 	LIS_MATRIX A = c->A;
 	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER], n = A->n;
 	LIS_VECTOR r = esolver->work[0], q = esolver->work[1], *v = &esolver->work[2];
-	LIS_SCALAR theta = 0.0, dot;
+	LIS_SCALAR theta = 0.0;
 	LIS_REAL nrm2, resid = 0.0;
-	LIS_INT err = 0, iter, j, k;
+	LIS_INT err = 0, iter, j;
 	double etime0, etime, *hdev = NULL, **dv = NULL;         /* the chain's coefficients (HBM) and its basis as device pointers */
 	char esolvername[128];
 	int shifted = 0;
@@ -796,22 +827,8 @@ static LIS_INT lis_esi(LIS_ESOLVER esolver)
 		iter = 0;
 		while (iter < c->emaxiter) {
 			iter = iter + 1;
-			/* QR factorization V*R = Z for starting vector Z: v(j) against v(1) .. v(j-1), dot then axpy, pair by pair */
-			if (fused && j > 1) {
-				double *vj;
-				ETRY(lisd_vec_in(v[j], &vj));
-				for (k = 1; k < j; k++) ETRY(lisd_vec_in(v[k], &dv[k - 1]));
-				EHIP(liship_dot_f64(n, vj, dv[0], hdev, lisg.reduce_work, lisg.stream));
-				ETRY(lisd_mgs_chain(n, j - 1, dv, vj, hdev));
-				EHIP(liship_scale_to_f64(1, -1.0, hdev + j - 2, hdev + j - 1, lisg.stream));      /* the last coefficient negated in HBM: the axpy below adds */
-				EHIP(liship_axpy_dev_f64(n, hdev + j - 1, dv[j - 2], vj, lisg.stream));
-				ETRY(lisd_vec_done(v[j]));
-			} else {
-				for (k = 1; k < j; k++) {
-					ETRY(lis_vector_dot(v[j], v[k], &dot));
-					ETRY(lis_vector_axpy(-dot, v[k], v[j]));
-				}
-			}
+			/* QR factorization V*R = Z for starting vector Z */
+			ETRY(orthogonalise(n, j, v, fused, hdev, dv));
 			/* kernel: R = A * V or R = A^-1 * V */
 			if (niesolver == LIS_ESOLVER_PI) ETRY(lis_matvec(A, v[j], r));
 			else ETRY(inner_solve(c, v[j], r, 0));
@@ -878,18 +895,20 @@ static LIS_INT multi_banner(ectx_t *c, LIS_INT niesolver)
 	return err;
 }
 
-/* the refinements after the Ritz values (lis_esolver_li.c:285-346, lis_esolver_ai.c:322-381): per mode a fresh eigensolver of one pair -- -ie's solver with the
- * outer -emaxiter, -etol and -eprint, shifted by the Ritz value -- run by lis_esolve on evector[i]; mode 0's history, times, count and residual go into the
- * outer object.  Whatever the inner eigensolver returned, the answer is LIS_SUCCESS, as there. */
+/* the refinements after the Ritz values (lis_esolver_li.c:285-346, :627-683, lis_esolver_ai.c:322-381, :684-739): per mode a fresh eigensolver of one pair --
+ * -ie's solver, or -ige's under a B, with the outer -emaxiter, -etol and -eprint, shifted by the Ritz value -- run by lis_gesolve on evector[i]; mode 0's
+ * history, times, count and residual go into the outer object.  Whatever the inner eigensolver returned, the answer is LIS_SUCCESS, as there.  Under a B each
+ * refinement shifts A by its Ritz value and back (lis_matrix_shift_matrix), so A's arrays carry that drift afterwards, as the reference's do. */
 static LIS_INT refine_modes(ectx_t *c, const char *name)
 {
 	LIS_ESOLVER esolver = c->e, esolver2;
+	LIS_MATRIX B = esolver->B;                               /* the generalized forms refine through lis_gesolve(A, B, ...) with -ige's solver */
 	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE];
 	if (c->output) lis_printf(LIS_COMM_WORLD, "computing refined eigenpairs using inner eigensolver:\n\n");
 	for (LIS_INT i = 0; i < ss; i++) {
 		LIS_SCALAR evalue = 0.0;
 		LISCHK(lis_esolver_create(&esolver2));
-		esolver2->options[LIS_EOPTIONS_ESOLVER] = esolver->options[LIS_EOPTIONS_INNER_ESOLVER];
+		esolver2->options[LIS_EOPTIONS_ESOLVER] = esolver->options[B ? LIS_EOPTIONS_INNER_GENERALIZED_ESOLVER : LIS_EOPTIONS_INNER_ESOLVER];
 		esolver2->options[LIS_EOPTIONS_SUBSPACE] = 1;
 		esolver2->options[LIS_EOPTIONS_MAXITER] = c->emaxiter;
 		esolver2->options[LIS_EOPTIONS_OUTPUT] = esolver->options[LIS_EOPTIONS_OUTPUT];
@@ -897,7 +916,7 @@ static LIS_INT refine_modes(ectx_t *c, const char *name)
 		LIS_INT err = lis_vector_duplicate(c->A, &esolver->evector[i]);
 		if (err) { lis_esolver_destroy(esolver2); return err; }
 		esolver2->ishift = esolver->evalue[i];
-		(void)lis_esolve(c->A, esolver->evector[i], &evalue, esolver2);
+		(void)lis_gesolve(c->A, B, esolver->evector[i], &evalue, esolver2);
 		if (esolver2->evalue) {
 			esolver->evalue[i] = esolver2->evalue[0];
 			esolver->iter[i] = esolver2->iter[0];
@@ -1347,6 +1366,322 @@ done:
 	return esolver->retcode;
 }
 
+/* ================================================================== several pairs of the generalized problem: subspace, Lanczos, Arnoldi
+ * lis_egsi, lis_egli and lis_egai of the reference statement for statement, with the helpers of the two sections above.  The fused forms keep what those of
+ * -e si / -e ai keep in HBM and add the two pair passes (liship_scale2_inv_sqrt_f64, liship_scale2_to_f64); no sum is taken from a product's fused-dot epilogue,
+ * whose tree is not liship_dot_f64's, so fused and unfused agree in every bit (tests/test_gesolve_multi_gpu.py).  LIS_AMD_NO_FUSION=1 runs the lis_vector_* calls. */
+
+/* the banner of the three and the linear solver they keep: "-i bicg -p none", then the command line's options */
+static LIS_INT gmulti_solver(ectx_t *c, LIS_INT nigesolver)
+{
+	char esolvername[128];
+	lis_esolver_get_esolvername(nigesolver, esolvername);
+	if (c->output) lis_printf(LIS_COMM_WORLD, "inner eigensolver     : %s\n", esolvername);
+	return inner_solver(c, "-i bicg -p none");
+}
+
+/* ------------------------------------------------------------------ generalized subspace iteration, lis_esolver_si.c:456-719.  As written there: v(j) is
+ * orthogonalised against the earlier v(k) with the plain dot, not the B-inner product; eta = <v,w>^1/2 without fabs, so a negative sum gives NaN from there on;
+ * work[4] (Ax there) is v(1) and has no use of its own.  With -ige gii the reference creates a preconditioner on A and then, falling through, on B, and leaks
+ * both per mode: each is created once per mode here and freed, B's being the one the solves run with. */
+static LIS_INT lis_egsi(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 1);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], nigesolver = esolver->options[LIS_EOPTIONS_INNER_GENERALIZED_ESOLVER], n = A->n;
+	const int power = nigesolver == LIS_ESOLVER_GPI;
+	LIS_VECTOR y = esolver->work[0], w = esolver->work[1], q = esolver->work[2], *v = &esolver->work[3];
+	LIS_SCALAR theta = 0.0, eta;
+	LIS_REAL nrm2, resid = 0.0;
+	LIS_INT err = 0, iter, j;
+	double etime0, etime, *hdev = NULL, **dv = NULL;         /* the chain's coefficients (HBM) and its basis as device pointers */
+	int shifted = 0;
+	ETRY(lis_vector_set_all(1.0, y));
+	ETRY(lis_vector_nrm2(y, &nrm2));
+	ETRY(lis_vector_scale(1.0 / nrm2, y));
+	if (c->oshift != 0.0) { ETRY(lis_matrix_shift_matrix(A, B, c->oshift)); shifted = 1; }
+	eshift_banner(c);
+	ETRY(gmulti_solver(c, nigesolver));
+	if (c->output) {
+		lis_printf(LIS_COMM_WORLD, "size of subspace      : %D\n\n", ss);
+		lis_printf(LIS_COMM_WORLD, "compute eigenpairs in subspace:\n\n");
+	}
+	if (!lisg.no_fusion) EHIP(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(ss + 2)));
+	if (!(dv = (double **)malloc(sizeof(double *) * (size_t)(ss + 1)))) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", ss + 1); goto done; }
+	j = 0;
+	while (j < ss) {
+		etime0 = lis_wtime();
+		ETRY(lis_vector_duplicate(A, &esolver->evector[j]));
+		j = j + 1;
+		ETRY(lis_vector_copy(y, v[j]));
+		if (c->precon) { lis_precon_destroy(c->precon); c->precon = NULL; }
+		if (!power) {
+			c->solver->A = A;
+			ETRY(lis_precon_create(c->solver, &c->precon));
+			lis_precon_destroy(c->precon); c->precon = NULL;
+		}
+		c->solver->A = B;
+		ETRY(lis_precon_create(c->solver, &c->precon));
+		const int fused = chain_ready(n, y, v[j]) && chain_ready(n, w, w);
+		iter = 0;
+		while (iter < c->emaxiter) {
+			iter = iter + 1;
+			/* QR factorization V*R = Z for starting vector Z */
+			ETRY(orthogonalise(n, j, v, fused, hdev, dv));
+			/* kernel: w = A * v (gpi) or w = B * v (gii); v = v / <v,w>^1/2, w = w / <v,w>^1/2; y = B^-1 * w or y = A^-1 * w */
+			ETRY(lis_matvec(power ? A : B, v[j], w));
+			if (fused) {
+				double *dvj, *dw;
+				ETRY(lisd_vec_in(v[j], &dvj)); ETRY(lisd_vec_in(w, &dw));
+				EHIP(liship_dot_f64(n, dvj, dw, lisg.reduce_out, lisg.reduce_work, lisg.stream));
+				EHIP(liship_scale2_inv_sqrt_f64(n, lisg.reduce_out, dvj, dw, lisg.stream));
+				ETRY(lisd_vec_done(v[j])); ETRY(lisd_vec_done(w));
+			} else {
+				ETRY(lis_vector_dot(v[j], w, &eta));
+				eta = sqrt(eta);
+				ETRY(lis_vector_scale(1.0 / eta, v[j]));
+				ETRY(lis_vector_scale(1.0 / eta, w));
+			}
+			ETRY(inner_solve_on(c, power ? B : A, w, y, 0));
+			if (j == 1) inner_times(c);
+			/* theta = <w,y>; resid = ||y - theta * v||_2 / |theta|; y = y / ||y||_2; v = y */
+			if (fused) {
+				static const int pairs[2][2] = {{0, 0}, {1, 0}};
+				double *dy, *dw, *dvj, sums[3];
+				ETRY(lisd_vec_in(y, &dy)); ETRY(lisd_vec_in(w, &dw)); ETRY(lisd_vec_in(v[j], &dvj));
+				const double *dyw[2] = {dy, dw};
+				EHIP(liship_multidot_f64(n, 2, dyw, 2, pairs, lisg.reduce_out, lisg.reduce_work, lisg.stream));
+				EHIP(liship_ritz_tail_f64(n, lisg.reduce_out, dy, dvj, lisg.reduce_out + 2, lisg.reduce_work, lisg.stream));
+				ETRY(lisd_vec_done(y)); ETRY(lisd_vec_done(v[j]));
+				ETRY(lisd_fetch(3, sums));                       /* the one read-back of the iteration */
+				nrm2 = sqrt(sums[0]); theta = sums[1]; resid = sqrt(sums[2]);
+				resid = resid / fabs(theta);
+			} else {
+				ETRY(lis_vector_dot(w, y, &theta));
+				ETRY(lis_vector_axpyz(-theta, v[j], y, q));
+				ETRY(lis_vector_nrm2(q, &resid));
+				resid = resid / fabs(theta);
+				ETRY(lis_vector_nrm2(y, &nrm2));
+				ETRY(lis_vector_scale(1.0 / nrm2, y));
+				ETRY(lis_vector_copy(y, v[j]));
+			}
+			/* convergence check: the history and iter[0] are mode 0's */
+			if (j == 1) {
+				if (c->output & LIS_EPRINT_MEM) esolver->rhistory[iter] = resid;
+				esolver->iter[j - 1] = iter;
+			}
+			if (c->output & LIS_EPRINT_OUT) lis_printf(LIS_COMM_WORLD, "iteration: %5d  relative residual = %E\n", (int)iter, (double)resid);
+			if (c->tol > resid) break;
+		}
+		esolver->evalue[j - 1] = power ? theta + c->oshift : 1.0 / theta + c->oshift;
+		esolver->resid[j - 1] = resid;
+		esolver->iter[j - 1] = iter;
+		ETRY(lis_vector_copy(v[j], esolver->evector[j - 1]));
+		etime = lis_wtime() - etime0;
+		if (c->output & (ss > 1)) {                           /* (as written there: the MEM bit of -eprint) */
+			lis_printf(LIS_COMM_WORLD, "Generalized Subspace: mode number          = %D\n", j - 1);
+			lis_printf(LIS_COMM_WORLD, "Generalized Subspace: eigenvalue           = %e\n", (double)esolver->evalue[j - 1]);
+			lis_printf(LIS_COMM_WORLD, "Generalized Subspace: elapsed time         = %e sec.\n", etime);
+			lis_printf(LIS_COMM_WORLD, "Generalized Subspace: number of iterations = %D\n", iter);
+			lis_printf(LIS_COMM_WORLD, "Generalized Subspace: relative residual    = %e\n\n", (double)resid);
+		}
+	}
+done:
+	if (hdev) (void)liship_free(hdev);
+	free(dv);
+	if (shifted) { const LIS_INT e2 = lis_matrix_shift_matrix(A, B, -c->oshift); if (e2 && !err) err = e2; }
+	inner_destroy(c);
+	if (!err) err = lis_vector_copy(esolver->evector[0], esolver->x);
+	return err;                                              /* LIS_SUCCESS also when a mode stopped at -emaxiter, as there */
+}
+
+/* ------------------------------------------------------------------ generalized Lanczos, lis_esolver_li.c:456-694.  As written there: w = &work[2] and
+ * v = &work[3], so w(j+1) and v(j) are one vector -- the copy r -> w(j) overwrites v(j-1), and the reorthogonalisation of v(j) runs against overwritten vectors
+ * (it does not feed t[]); the start is r = B * q with beta = |<q,r>|^1/2, B q = r is solved every step, and t(j, j-1) is |<q,r>|^1/2, not a 2-norm. */
+static LIS_INT lis_egli(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 0);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], nigesolver = esolver->options[LIS_EOPTIONS_INNER_GENERALIZED_ESOLVER], n = A->n;
+	LIS_VECTOR q = esolver->work[0], r = esolver->work[1], *w = &esolver->work[2], *v = &esolver->work[3];
+	LIS_SCALAR beta, dot, div, *t = NULL, *tq = NULL, *tr = NULL;
+	LIS_REAL qrerr;
+	LIS_INT err = 0, i, j, k, qriter;
+	double time, time0;
+	t = (LIS_SCALAR *)calloc((size_t)ss * ss, sizeof(LIS_SCALAR));
+	tq = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	tr = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	if (!t || !tq || !tr) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)(ss * ss * sizeof(LIS_SCALAR))); goto done; }
+	ETRY(lis_vector_set_all(0.0, w[0]));
+	ETRY(lis_vector_set_all(0.0, v[0]));
+	ETRY(lis_vector_set_all(1.0, q));
+	ETRY(gmulti_solver(c, nigesolver));
+	c->solver->A = B;
+	ETRY(lis_precon_create(c->solver, &c->precon));
+	j = 0;
+	while (j < ss - 1) {
+		j = j + 1;
+		/* w(j) = r / beta(j-1); v(j) = q / beta(j-1); r = A * v(j); r = r - beta(j-1) * w(j-1) */
+		if (j == 1) {
+			ETRY(lis_matvec(B, q, r));
+			ETRY(lis_vector_dot(q, r, &beta));
+			beta = sqrt(fabs(beta));
+			div = beta;
+		} else div = t[(j - 2) * ss + j - 1];
+		if (chain_ready(n, r, q) && chain_ready(n, w[j], v[j])) {            /* copy, copy, scale, scale: one pass */
+			double *dr, *dq, *dwj, *dvj;
+			ETRY(lisd_vec_in(r, &dr)); ETRY(lisd_vec_in(q, &dq));
+			ETRY(lisd_vec_out(w[j], &dwj)); ETRY(lisd_vec_out(v[j], &dvj));
+			EHIP(liship_scale2_to_f64(n, 1.0 / div, dr, dq, dwj, dvj, lisg.stream));
+			ETRY(lisd_vec_done(w[j])); ETRY(lisd_vec_done(v[j]));
+		} else {
+			ETRY(lis_vector_copy(r, w[j]));
+			ETRY(lis_vector_copy(q, v[j]));
+			ETRY(lis_vector_scale(1.0 / div, w[j]));
+			ETRY(lis_vector_scale(1.0 / div, v[j]));
+		}
+		ETRY(lis_matvec(A, v[j], r));
+		ETRY(lis_vector_axpy(-div, w[j - 1], r));
+		ETRY(lis_vector_dot(v[j], r, &t[(j - 1) * ss + j - 1]));             /* alpha(j) = <v(j), r> */
+		ETRY(lis_vector_axpy(-t[(j - 1) * ss + j - 1], w[j], r));            /* r = r - alpha(j) * w(j) */
+		for (k = 1; k < j; k++) {                                            /* reorthogonalization, as written there */
+			ETRY(lis_vector_dot(v[j], v[k], &dot));
+			ETRY(lis_vector_axpy(-dot, v[k], v[j]));
+		}
+		ETRY(inner_solve_on(c, B, r, q, 0));                                 /* solve B * q = r */
+		ETRY(lis_vector_dot(q, r, &beta));                                   /* beta(j) = |<q,r>|^1/2 */
+		beta = sqrt(fabs(beta));
+		t[(j - 1) * ss + j] = beta;
+		if (fabs(t[(j - 1) * ss + j]) < c->tol) break;                       /* convergence check */
+		t[j * ss + j - 1] = t[(j - 1) * ss + j];
+	}
+	/* eigenvalues of the symmetric tridiagonal matrix */
+	time0 = lis_wtime();
+	ETRY(lis_array_qr(ss, t, tq, tr, &qriter, &qrerr));
+	time = lis_wtime() - time0;
+	for (i = 0; i < ss; i++) esolver->evalue[i] = t[i * ss + i];
+	if (c->output) {
+		lis_printf(LIS_COMM_WORLD, "size of subspace      : %D\n\n", ss);
+		lis_printf(LIS_COMM_WORLD, "Ritz values :\n\n");
+		for (i = 0; i < ss; i++) {
+			lis_printf(LIS_COMM_WORLD, "Generalized Lanczos: mode number          = %D\n", i);
+			lis_printf(LIS_COMM_WORLD, "Generalized Lanczos: Ritz value           = %e\n", (double)esolver->evalue[i]);
+		}
+		lis_printf(LIS_COMM_WORLD, "Lanczos: elapsed time         = %e sec.\n\n", time);
+	}
+	if (!esolver->options[LIS_EOPTIONS_RVAL]) err = refine_modes(c, "Generalized Lanczos");     /* -rval true: iter[] and resid[] stay 0 (heap contents there) */
+done:
+	inner_destroy(c);
+	free(t); free(tq); free(tr);
+	return err;
+}
+
+/* ------------------------------------------------------------------ generalized Arnoldi, lis_esolver_ai.c:491-750: lis_eai with w = B^-1 * (A * v(j)) -- solve,
+ * then copy y -> w -- in front of the Hessenberg column, which is taken as lis_eai takes it.  (At i = ss the reference reads h(ss, ss-1) and h(ss, ss), past
+ * its array; the last mode's Ritz value is the diagonal entry here, as in lis_eai.) */
+static LIS_INT lis_egai(LIS_ESOLVER esolver)
+{
+	ectx_t cx, *c = &cx;
+	ectx_begin(c, esolver, 0);
+	LIS_MATRIX A = c->A, B = esolver->B;
+	const LIS_INT ss = esolver->options[LIS_EOPTIONS_SUBSPACE], nigesolver = esolver->options[LIS_EOPTIONS_INNER_GENERALIZED_ESOLVER], n = A->n;
+	LIS_VECTOR w = esolver->work[0], y = esolver->work[1], *v = &esolver->work[2];
+	LIS_SCALAR *h = NULL, *hq = NULL, *hr = NULL;
+	LIS_REAL nrm2, hqrerr, D;
+	LIS_INT err = 0, i, j, hqriter;
+	double time, time0, *hdev = NULL, **dv = NULL;
+	const int fused = !lisg.no_fusion && ss + 1 <= 256;                     /* (a column comes home through the page-locked landing zone) */
+	h = (LIS_SCALAR *)calloc((size_t)ss * ss + 1, sizeof(LIS_SCALAR));      /* (one more than there: h(ss, ss-1), which the last column's norm is written to) */
+	hq = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	hr = (LIS_SCALAR *)malloc((size_t)ss * ss * sizeof(LIS_SCALAR));
+	if (!h || !hq || !hr) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)(ss * ss * sizeof(LIS_SCALAR))); goto done; }
+	ETRY(lis_vector_set_all(1.0, v[0]));
+	ETRY(lis_vector_nrm2(v[0], &nrm2));
+	ETRY(lis_vector_scale(1.0 / nrm2, v[0]));
+	ETRY(gmulti_solver(c, nigesolver));
+	c->solver->A = B;
+	ETRY(lis_precon_create(c->solver, &c->precon));
+	if (fused) EHIP(lisd_malloc((void **)&hdev, sizeof(double) * (size_t)(ss + 2)));
+	if (!(dv = (double **)malloc(sizeof(double *) * (size_t)(ss + 1)))) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", ss + 1); goto done; }
+	j = -1;
+	while (j < ss - 1) {
+		j = j + 1;
+		ETRY(lis_matvec(A, v[j], w));                                        /* w = A * v(j) */
+		ETRY(inner_solve_on(c, B, w, y, 0));                                 /* w = B^-1 * w */
+		ETRY(lis_vector_copy(y, w));
+		if (fused) {
+			/* h(i,j) = <v(i), w>; w = w - h(i,j) * v(i), i = 0 .. j, then ||w||^2: one chain, one read-back per column */
+			double *dw;
+			ETRY(lisd_vec_in(w, &dw));
+			for (i = 0; i <= j; i++) ETRY(lisd_vec_in(v[i], &dv[i]));
+			EHIP(liship_dot_f64(n, dv[0], dw, hdev, lisg.reduce_work, lisg.stream));
+			ETRY(lisd_mgs_chain(n, j + 1, dv, dw, hdev));
+			EHIP(liship_mgs_step_f64(n, hdev + j, dv[j], dw, NULL, hdev + j + 1, lisg.reduce_work, lisg.stream));
+			ETRY(lisd_vec_done(w));
+			ETRY(lisd_fetch_from(hdev, j + 2, h + j * ss));                 /* the column h(0..j, j) and, in h(j+1, j), the sum of squares */
+			h[j + 1 + j * ss] = sqrt(h[j + 1 + j * ss]);
+		} else {
+			for (i = 0; i <= j; i++) {
+				ETRY(lis_vector_dot(v[i], w, &h[i + j * ss]));
+				ETRY(lis_vector_axpy(-h[i + j * ss], v[i], w));
+			}
+			ETRY(lis_vector_nrm2(w, &h[j + 1 + j * ss]));                    /* h(j+1,j) = ||w||_2 */
+		}
+		if (fabs(h[j + 1 + j * ss]) < c->tol) break;                         /* convergence check */
+		ETRY(lis_vector_scale(1 / h[j + 1 + j * ss], w));                    /* v(j+1) = w / h(j+1,j) */
+		ETRY(lis_vector_copy(w, v[j + 1]));
+	}
+	/* eigenvalues of the upper Hessenberg matrix: the diagonal and the 2 x 2 blocks QR leaves (a complex pair gives its real part twice) */
+	time0 = lis_wtime();
+	ETRY(lis_array_qr(ss, h, hq, hr, &hqriter, &hqrerr));
+	time = lis_wtime() - time0;
+	if (c->output) {
+		lis_printf(LIS_COMM_WORLD, "size of subspace      : %D\n\n", ss);
+		lis_printf(LIS_COMM_WORLD, "Ritz values:\n\n");
+	}
+	i = 0;
+	while (i < ss) {
+		i = i + 1;
+		if (ss == i || fabs(h[i + (i - 1) * ss]) < c->tol) {
+			if (c->output) {
+				lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: mode number              = %D\n", i - 1);
+				lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: Ritz value               = %e\n", (double)(h[i - 1 + (i - 1) * ss]));
+			}
+			esolver->evalue[i - 1] = h[i - 1 + (i - 1) * ss];
+		} else {
+			D = (h[i - 1 + (i - 1) * ss] + h[i + i * ss]) * (h[i - 1 + (i - 1) * ss] + h[i + i * ss])
+			    - 4 * (h[i - 1 + (i - 1) * ss] * h[i + i * ss] - h[i - 1 + i * ss] * h[i + (i - 1) * ss]);
+			if (D < 0) {
+				if (c->output) {
+					lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: mode number              = %D\n", i - 1);
+					lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: Ritz value               = (%e, %e)\n", (double)((h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2), (double)sqrt(-D) / 2);
+					lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: mode number              = %D\n", i);
+					lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: Ritz value               = (%e, %e)\n", (double)((h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2), (double)-sqrt(-D) / 2);
+				}
+				esolver->evalue[i - 1] = (h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2;
+				esolver->evalue[i] = (h[i - 1 + (i - 1) * ss] + h[i + i * ss]) / 2;
+				i = i + 1;
+			} else {
+				if (c->output) {
+					lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: mode number              = %D\n", i - 1);
+					lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: Ritz value               = %e\n", (double)(h[i - 1 + (i - 1) * ss]));
+				}
+				esolver->evalue[i - 1] = h[i - 1 + (i - 1) * ss];
+			}
+		}
+	}
+	lis_printf(LIS_COMM_WORLD, "Generalized Arnoldi: elapsed time         = %e sec.\n\n", time);      /* (printed at -eprint none too, as there) */
+	if (!esolver->options[LIS_EOPTIONS_RVAL]) err = refine_modes(c, "Generalized Arnoldi");
+done:
+	inner_destroy(c);
+	if (hdev) (void)liship_free(hdev);
+	free(dv);
+	free(h); free(hq); free(hr);
+	return err;
+}
+
 /* ------------------------------------------------------------------ lis_esolve / lis_gesolve, ref :263-666 */
 static LIS_INT work_alloc(LIS_ESOLVER e, LIS_INT count)
 {	/* lis_e<xx>_malloc_work: NWORK duplicates of A's row layout */
@@ -1383,21 +1718,21 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	/* what is not served, said before A or x is touched */
 	if (B != NULL && !is_generalized(nesolver)) {             /* (the reference runs the standard loop and never reads B) */
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "generalized eigenproblems (lis_gesolve with a matrix B) are served by -e gpi | gii | grqi | gcr: %s (-e %s) is a standard eigensolver, which would ignore B\n",
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "generalized eigenproblems (lis_gesolve with a matrix B) are served by -e gpi | gii | grqi | gcr | gsi | gli | gai: %s (-e %s) is a standard eigensolver, which would ignore B\n",
 		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
 	}
 	if (is_generalized(nesolver) && B == NULL) {              /* (the reference's loops multiply by that NULL) */
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd without a matrix B: lis_esolve serves pi, ii, rqi, cg, cr, si, li, ai, lis_gesolve with a B gpi, gii, grqi, gcr\n",
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd without a matrix B: lis_esolve serves pi, ii, rqi, cg, cr, si, li, ai, lis_gesolve with a B gpi, gii, grqi, gcr, gsi, gli, gai\n",
 		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
 	}
 	if (nesolver == LIS_ESOLVER_GCG) {
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver Generalized CG (-e gcg) is not served by liblis_amd: the reference's loop never updates x from its Ritz vector and ends in NaN at every thread count; -e gcr is the generalized solver of that family that works\n");
 	}
-	if (nesolver == LIS_ESOLVER_GSI || nesolver == LIS_ESOLVER_GLI || nesolver == LIS_ESOLVER_GAI) {
+	if (is_gmulti(nesolver) && ss == 1) {
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) is not served by liblis_amd: several pairs of a generalized problem are not served yet (one pair: gpi, gii, grqi, gcr)\n",
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "eigensolver %s (-e %s) serves several pairs; a subspace of one vector (-ss 1, the default) is not served by liblis_amd: one pair is what -e gpi / -e gii serve\n",
 		                esolver_names[nesolver], esolver_keys[nesolver - 1]);
 	}
 	if (is_multi(nesolver) && ss == 1) {
@@ -1413,14 +1748,20 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	}
 	if (emaxiter < 0) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_MAXITER(=%D) is less than 0\n", emaxiter); }
 	if (ss < 1 || mode < 0 || mode > ss + 1) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameters LIS_EOPTIONS_SUBSPACE(=%D), LIS_EOPTIONS_MODE(=%D) are out of range\n", ss, mode); }
-	if (is_multi(nesolver)) {                                /* ref :389-411, and the inner eigensolvers the loops can run */
-		const LIS_INT niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER];
+	if (is_multi(nesolver) || is_gmulti(nesolver)) {         /* ref :389-411, and the inner eigensolvers the loops can run */
+		const LIS_INT niesolver = esolver->options[LIS_EOPTIONS_INNER_ESOLVER], nigesolver = esolver->options[LIS_EOPTIONS_INNER_GENERALIZED_ESOLVER];
 		if (ss > A->gn) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_SUBSPACE is %D (Set less than or equal to matrix size %D)\n", ss, A->gn); }
 		if (mode >= ss) { esolver->retcode = LIS_ERR_ILL_ARG; return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_MODE is %D (Set less than subspace size %D)\n", mode, ss); }
-		if (nesolver == LIS_ESOLVER_SI ? (niesolver != LIS_ESOLVER_PI && niesolver != LIS_ESOLVER_II) : (niesolver < LIS_ESOLVER_PI || niesolver > LIS_ESOLVER_CR)) {
+		if (is_multi(nesolver) && (nesolver == LIS_ESOLVER_SI ? (niesolver != LIS_ESOLVER_PI && niesolver != LIS_ESOLVER_II) : (niesolver < LIS_ESOLVER_PI || niesolver > LIS_ESOLVER_CR))) {
 			esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;       /* (the reference's subspace loop applies A for -ie pi and -ie ii only) */
 			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "inner eigensolver %D (-ie) is not served by liblis_amd for -e %s (%s)\n", niesolver, esolver_keys[nesolver - 1],
 			                nesolver == LIS_ESOLVER_SI ? "pi, ii" : "pi, ii, rqi, cg, cr");
+		}
+		if (nesolver == LIS_ESOLVER_GSI ? (nigesolver != LIS_ESOLVER_GPI && nigesolver != LIS_ESOLVER_GII)
+		                                : is_gmulti(nesolver) && nigesolver != LIS_ESOLVER_GPI && nigesolver != LIS_ESOLVER_GII && nigesolver != LIS_ESOLVER_GRQI && nigesolver != LIS_ESOLVER_GCR) {
+			esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;       /* (the reference's generalized subspace loop applies neither matrix for another -ige; its gcg ends in NaN) */
+			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "inner generalized eigensolver %D (-ige) is not served by liblis_amd for -e %s (%s)\n", nigesolver, esolver_keys[nesolver - 1],
+			                nesolver == LIS_ESOLVER_GSI ? "gpi, gii" : "gpi, gii, grqi, gcr");
 		}
 	}
 	if (B != NULL && (A->is_splited || B->is_splited || !lisi_format_served(B->matrix_type) || B->np != B->n || A->np != A->n)) {
@@ -1470,6 +1811,7 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	double time = lis_wtime();
 	esolver->ptime = 0; esolver->itime = 0; esolver->p_c_time = 0; esolver->p_i_time = 0;
 	if ((err = work_alloc(esolver, nesolver == LIS_ESOLVER_CG || nesolver == LIS_ESOLVER_CR ? 6 : nesolver == LIS_ESOLVER_SI ? 4 + ss : is_multi(nesolver) ? 2 + ss :
+	                               nesolver == LIS_ESOLVER_GSI ? 5 + ss : nesolver == LIS_ESOLVER_GLI ? 4 + ss : nesolver == LIS_ESOLVER_GAI ? 3 + ss :
 	                               nesolver == LIS_ESOLVER_GCR ? 9 : is_generalized(nesolver) ? 3 : 2))) goto fail;
 	esolver->x = xx; esolver->xx = x;
 
@@ -1485,6 +1827,9 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 	case LIS_ESOLVER_GII: err = lis_egii(esolver); break;
 	case LIS_ESOLVER_GRQI: err = lis_egrqi(esolver); break;
 	case LIS_ESOLVER_GCR: err = lis_egcr(esolver); break;
+	case LIS_ESOLVER_GSI: err = lis_egsi(esolver); break;
+	case LIS_ESOLVER_GLI: err = lis_egli(esolver); break;
+	case LIS_ESOLVER_GAI: err = lis_egai(esolver); break;
 	default:              err = lis_ecr(esolver); break;
 	}
 	esolver->retcode = err;
@@ -1508,7 +1853,7 @@ fail:
 	esolver->retcode = err;
 	esolver->x = x;
 	lis_vector_destroy(xx);
-	if (is_multi(nesolver)) arrays_free(esolver);            /* the getters of several pairs answer for a solve that ended */
+	if (is_multi(nesolver) || is_gmulti(nesolver)) arrays_free(esolver);            /* the getters of several pairs answer for a solve that ended */
 	return err;
 }
 

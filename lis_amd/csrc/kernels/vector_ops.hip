@@ -167,6 +167,44 @@ int run_cg_direction(int n, const double *palpha, const double *pbeta, const dou
     return 0;
 }
 
+// The pair passes (liship.h): out0 = a * in0, out1 = a * in1 in one walk, each result one rounded product -- the bits of two
+// EW_SCALE_TO passes.  ps != NULL: a = 1 / sqrt(*ps), formed once per lane from the HBM value, as EW_SCALE_DEV forms it.
+template <bool NT, bool VEC>
+__global__ __launch_bounds__(BLOCK)
+void scale2_kernel(int n, double a, const double *ps, const double *in0, const double *in1, double *out0, double *out1, const double *skip)
+{
+    if (skip && skip[0] != 0.0) return;
+    if (ps) a = 1.0 / sqrt(ps[0]);
+    const double *in[2] = {in0, in1};
+    double *out[2] = {out0, out1};
+    vector_pass<NT, VEC, 2, 2>(n, in, out, [&](const double (&x)[2], double (&o)[2]) {
+        o[0] = a * x[0];
+        o[1] = a * x[1];
+    });
+}
+
+inline bool spans_overlap(const void *p, const void *q, int n)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q), len = (uintptr_t)n * sizeof(double);
+    return a < b + len && b < a + len;
+}
+
+// the two outputs are disjoint; an output meets an input only as its own input, whole (each lane reads its elements before it writes them)
+int run_scale2(int n, double a, const double *ps, const double *in0, const double *in1, double *out0, double *out1, void *stream)
+{
+    if (n <= 0 || !in0 || !in1 || !out0 || !out1) return LISHIP_ERR_ARG;
+    if (spans_overlap(out0, out1, n) || spans_overlap(out0, in1, n) || spans_overlap(out1, in0, n)) return LISHIP_ERR_ARG;
+    if ((out0 != in0 && spans_overlap(out0, in0, n)) || (out1 != in1 && spans_overlap(out1, in1, n))) return LISHIP_ERR_ARG;
+    if (ps && ((ps >= out0 && ps < out0 + n) || (ps >= out1 && ps < out1 + n))) return LISHIP_ERR_ARG;      // (*ps is read by every lane while others store)
+    const bool vec = aligned16(in0) && aligned16(in1) && aligned16(out0) && aligned16(out1);
+    hipStream_t st = as_stream(stream);
+    launch_pass(vec, n, [&](auto nt, auto v) {
+        scale2_kernel<decltype(nt)::value, decltype(v)::value><<<pass_grid(n), BLOCK, 0, st>>>(n, a, ps, in0, in1, out0, out1, g_guard);
+    });
+    LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- reductions -------------------------------------------------------------------------------------
 // level 1: partial[k*stride + block] for k < NRES; levels >= 2 sum partial arrays the same way
 enum RedOp { RED_DOT, RED_SUMSQ, RED_ABS, RED_SUM, RED_DOT2,
@@ -780,6 +818,11 @@ extern "C" int liship_mgs_step_f64(int n, const double *hprev, const double *vpr
 // x *= 1/sqrt(*sumsq), sumsq in HBM  (lis_vector_nrm2 + lis_vector_scale, lis_solver_gmres.c:229-232)
 extern "C" int liship_scale_inv_norm_f64(int n, const double *sumsq, double *x, void *s)
 { return run_ew<EW_SCALE_DEV>(n, 0.0, 0.0, x, sumsq, nullptr, x, s); }
+// the pair passes of the generalized subspace and Lanczos iterations (lis_esolver_si.c:604-607, lis_esolver_li.c:546-549)
+extern "C" int liship_scale2_inv_sqrt_f64(int n, const double *sp, double *v, double *w, void *s)
+{ return sp ? run_scale2(n, 0.0, sp, v, w, v, w, s) : LISHIP_ERR_ARG; }
+extern "C" int liship_scale2_to_f64(int n, double a, const double *in0, const double *in1, double *out0, double *out1, void *s)
+{ return run_scale2(n, a, nullptr, in0, in1, out0, out1, s); }
 // the tail of a subspace iteration (lis_esolver_si.c:301-311) in one pass, RED_RITZ_TAIL: sums = {sum r^2, theta = <v,r>} in HBM; the sum of q^2 is
 // liship_sumsq_f64's of a 16 B aligned array of n elements (the same grid, lane mapping and folds: it IS that reduction with another term)
 extern "C" int liship_ritz_tail_f64(int n, const double *sums, double *r, double *v, double *result, void *work, void *stream)
