@@ -600,6 +600,29 @@ int  liship_spmv_csr_transposed_chunked_unordered_f64(int rows, int nsrc, int T,
                                                       const double *x, double *y, void *stream);
 int  liship_csr_transpose_f64(int nrows, int ncols, int nnz, const int *ptr, const int *index, const double *value,
                               int *tptr, int *tindex, double *tvalue, int *work, void *stream);
+/* ---- the same method keyed by an arbitrary key (kernels/transpose.hip): a STABLE grouping of the entries 0 .. nnz-1.  Segment c of the result lists the entries
+ * with key[k] == c in ascending k: tindex = src[k], tvalue = value[k]; tptr has nkeys + 1 ints.  key = row, src = col: the CSR rows of triplets in stored order
+ * (lis_matvec_coo); key = col, src = row: their transposed operator (lis_matvech_coo).  Every key must lie in [0, nkeys).  Scratch is the routine's own; it
+ * synchronizes the stream.  liship_key_facts: *flags_host bit 0 = key[] is not non-decreasing, bit 1 = a key outside [0, nkeys).  liship_sorted_key_starts:
+ * ptr[r] = first k with key[k] >= r, for r = 0 .. nkeys, of a non-decreasing key[].  liship_group_by_key_borders: {32, 33, 2048}, the segment lengths at which the
+ * ordering kernels change (insertion sort up to 32; 33 .. 2048 ranked by a wavefront in LDS when nnz > 8 nkeys; a heap sort beyond, and for those otherwise). */
+int  liship_key_facts(int nkeys, int nnz, const int *key, int *flags_host, void *stream);
+int  liship_sorted_key_starts(int nkeys, int nnz, const int *key, int *ptr, void *stream);
+int  liship_group_by_key_f64(int nkeys, int nnz, const int *key, const int *src, const double *value, int *tptr, int *tindex, double *tvalue, void *stream);
+int  liship_group_by_key_borders(int out[3]);
+/* ---- COO (kernels/coo.hip): the CSR row form of nnz triplets, rows listing their entries in ascending k -- the sums of the reference's serial lis_matvec_coo.
+ * ptr: n + 1 ints of the caller's.  row[] non-decreasing: ptr[] from the row starts and *index = col, *value = value THEMSELVES (no copy); otherwise fresh arrays
+ * (liship_free), grouped by liship_group_by_key_f64.  LISHIP_ERR_ARG for a row outside [0, n).  Synchronizes the stream. */
+int  liship_coo_rows_f64(int n, int nnz, const int *row, const int *col, const double *value, int *ptr, int **index, double **out_value, void *stream);
+/* ---- DNS (kernels/dns.hip): value[j*n + i], n rows, np columns, every entry multiplied (zeros too).
+ *   liship_spmv_dns_f64     y[i] = the chain over j = 0 .. np-1 from +0.0 of value[j*n+i] * x[j], every product rounded before it is added (lis_matvec_dns)
+ *   liship_spmv_dns_t_f64   y[j] = the T sums over the row chunks LIS_GET_ISIE(k, T, n), each a chain from +0.0 of value[j*n+i] * x[i], added in chunk order
+ *                           from +0.0 (lis_matvech_dns of the OpenMP build at T threads; T = 1: one chain)
+ * Pure streams of 8 n np bytes; value, x and y need only the alignment of a double.  liship_dns_tile_info: {rows of y per workgroup, columns per slab} of the
+ * forward kernel, {entries of y per workgroup, rows per slab} of the transposed one. */
+int  liship_dns_tile_info(int info[4]);
+int  liship_spmv_dns_f64(int n, int np, const double *value, const double *x, double *y, void *stream);
+int  liship_spmv_dns_t_f64(int n, int np, int T, const double *value, const double *x, double *y, void *stream);
 /* ---- preconditioners applied as products (kernels/sainv.hip): row sums over a packed CSR {ptr, idx, val}, each sum formed from +0.0 in STORED
  * order by one lane whatever the row's length, the epilogue in the same kernel.  The transposed forms (liship_csr_transpose_f64: terms by source
  * row) are summed in T chunks of the nsrc source rows, LIS_GET_ISIE(k, T, nsrc), the chunk sums added in chunk order from +0.0 (T <= 1: one chain).
@@ -641,6 +664,10 @@ int  liship_csr_to_bsr(int n, int bnr, int bnc, int bnnz, const int *ptr, const 
  * reference's unstable quicksort, lis_convert.c): entry j of row perm[s] goes to [jptr[j] + s] */
 int  liship_csr_to_jad(int n, const int *perm, const int *jptr, const int *ptr, const int *index, const double *value,
                        int *jad_index, double *jad_value, void *stream);
+/* COO: row[k] = the row of entry k (col and value of the triplets are index and value as they stand: lis_matrix_coo.c:753-763).  DNS: dns[j*n + i], n * np doubles,
+ * zero-filled here, then every entry in stored order, so that a duplicate (i, j) leaves its last value (lis_matrix_dns.c:784-797) */
+int  liship_csr_to_coo(int n, const int *ptr, int *row, void *stream);
+int  liship_csr_to_dns_f64(int n, int np, const int *ptr, const int *index, const double *value, double *dns, void *stream);
 /* reverse halo: y[export_index[i]] += wr[i], indices unique within one call  (lis_reduce, lis_matrix_mpi.c:988-996) */
 int  liship_scatter_add_f64(int count, const int *export_index, const double *wr, double *y, void *stream);
 

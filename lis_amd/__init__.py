@@ -213,6 +213,16 @@ _LISHIP = {
     "liship_spmv_csr_transposed_chunked_unordered_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_bsr_to_rows": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_csr_transpose_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_key_facts": (_ci, [_ci, _ci, _vp, C.POINTER(_ci), _vp]),
+    "liship_sorted_key_starts": (_ci, [_ci, _ci, _vp, _vp, _vp]),
+    "liship_group_by_key_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_group_by_key_borders": (_ci, [C.POINTER(_ci)]),
+    "liship_coo_rows_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _pvp, _pvp, _vp]),
+    "liship_dns_tile_info": (_ci, [C.POINTER(_ci)]),
+    "liship_spmv_dns_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
+    "liship_spmv_dns_t_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "liship_csr_to_coo": (_ci, [_ci, _vp, _vp, _vp]),
+    "liship_csr_to_dns_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp]),
     "liship_gather_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_scatter_add_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_poisson3d_nnz": (C.c_longlong, [_ci, _ci, _ci, _ci, _ci]),

@@ -1,11 +1,11 @@
 /*
- * lis_convert.c -- lis_matrix_convert / lis_matrix_copy: the storage layouts of the six served formats.
+ * lis_convert.c -- lis_matrix_convert / lis_matrix_copy: the storage layouts of the eight served formats.
  *
  * One-off host work that DEFINES the data layout each SpMV kernel streams, and with it the summation
  * order of every row.  Layouts are the reference's at one OpenMP thread (its DIA and JAD layouts are
  * blocked by the producer's thread count): csr2ell src/matrix/lis_matrix_ell.c:958-1070,
  * csr2dia lis_matrix_dia.c:1191-1304, csr2jad lis_matrix_jad.c:1591-1770, csr2bsr lis_matrix_bsr.c:351-552,
- * csr2csc lis_matrix_csc.c:904-1087; dispatcher lis_matrix_ops.c:128-322.
+ * csr2csc lis_matrix_csc.c:904-1087, csr2coo / coo2csr lis_matrix_coo.c:737-851, csr2dns / dns2csr lis_matrix_dns.c:744-915; dispatcher lis_matrix_ops.c:128-322.
  */
 #include "lis_internal.h"
 #ifdef _OPENMP
@@ -312,9 +312,72 @@ fail:
 	return err;
 }
 
+/* triplets in row order, a row's entries in stored order (ref lis_matrix_coo.c:753-763) */
+static LIS_INT csr2coo(LIS_MATRIX A, LIS_MATRIX B)
+{
+	const LIS_INT n = A->n, nnz = A->nnz;
+	LIS_INT err = 0, *row = NULL, *col = NULL; LIS_SCALAR *value = NULL;
+	NEW(row, LIS_INT, nnz); NEW(col, LIS_INT, nnz); NEW(value, LIS_SCALAR, nnz);
+	#pragma omp parallel for schedule(static) num_threads(lisi_host_threads())
+	for (LIS_INT i = 0; i < n; i++)
+		for (LIS_INT k = A->ptr[i]; k < A->ptr[i + 1]; k++) { row[k] = i; col[k] = A->index[k]; value[k] = A->value[k]; }
+	return finish(B, lis_matrix_set_coo(nnz, row, col, value, B));
+fail:
+	free(row); free(col); free(value);
+	return err;
+}
+
+/* zero-fill, then every entry in stored order: a duplicate (i, j) leaves its last value (ref lis_matrix_dns.c:784-797; rows are independent) */
+static LIS_INT csr2dns(LIS_MATRIX A, LIS_MATRIX B)
+{
+	const LIS_INT n = A->n, np = A->np;
+	const size_t count = (size_t)n * (size_t)np;
+	LIS_INT err = 0; LIS_SCALAR *value = NULL;
+	NEW(value, LIS_SCALAR, count);
+	#pragma omp parallel for schedule(static) num_threads(lisi_host_threads())
+	for (LIS_INT j = 0; j < np; j++) memset(value + (size_t)j * n, 0, sizeof(LIS_SCALAR) * (size_t)n);
+	#pragma omp parallel for schedule(static) num_threads(lisi_host_threads())
+	for (LIS_INT i = 0; i < n; i++)
+		for (LIS_INT k = A->ptr[i]; k < A->ptr[i + 1]; k++) value[(size_t)i + (size_t)n * (size_t)A->index[k]] = A->value[k];
+	return finish(B, lis_matrix_set_dns(value, B));
+fail:
+	free(value);
+	return err;
+}
+
+/* ascending sort of i1[] carrying i2[] and d1[]: the reference's lis_sort_iid restated (src/system/lis_sort.c:183-213 -- middle pivot parked at the end, strict
+ * Hoare scans).  It is unstable, and it moves entries inside a row even when the rows were ascending already: what lis_matrix_convert_coo2csr leaves in the SOURCE's
+ * arrays, and with them the bits of the source's next product, is whatever this exact scheme leaves (the two sides of a partition are disjoint: recursing into one
+ * and looping on the other makes the exchanges the reference's two recursive calls make) */
+void lisi_sort_iid(LIS_INT lo, LIS_INT hi, LIS_INT *i1, LIS_INT *i2, LIS_SCALAR *d1)
+{
+	while (lo < hi) {
+		const LIS_INT mid = (lo + hi) / 2, pv = i1[mid];
+		LIS_INT t; LIS_SCALAR u;
+		t = i1[mid]; i1[mid] = i1[hi]; i1[hi] = t;
+		t = i2[mid]; i2[mid] = i2[hi]; i2[hi] = t;
+		u = d1[mid]; d1[mid] = d1[hi]; d1[hi] = u;
+		LIS_INT a = lo, b = hi;
+		while (a <= b) {
+			while (i1[a] < pv) a++;
+			while (i1[b] > pv) b--;
+			if (a <= b) {
+				t = i1[a]; i1[a] = i1[b]; i1[b] = t;
+				t = i2[a]; i2[a] = i2[b]; i2[b] = t;
+				u = d1[a]; d1[a] = d1[b]; d1[b] = u;
+				a++; b--;
+			}
+		}
+		lisi_sort_iid(lo, b, i1, i2, d1);
+		lo = a;
+	}
+}
+
 LIS_INT lisi_convert_csr_to(LIS_MATRIX Ain, LIS_MATRIX Aout)
 {
 	switch (Aout->matrix_type) {
+	case LIS_MATRIX_COO: return csr2coo(Ain, Aout);
+	case LIS_MATRIX_DNS: return csr2dns(Ain, Aout);
 	case LIS_MATRIX_CSC: return csr2csc(Ain, Aout);
 	case LIS_MATRIX_ELL: return csr2ell(Ain, Aout);
 	case LIS_MATRIX_DIA: return csr2dia(Ain, Aout);
@@ -413,6 +476,30 @@ LIS_INT lisi_convert_to_csr(LIS_MATRIX A, LIS_MATRIX B)
 		/* a row's entries arrive block by block in stored block order, ascending column inside a block: the order
 		 * lis_matrix_convert_bsr2csr leaves (lis_matrix_bsr.c convert loop: bj outer, j inner), unsorted blocks included */
 		break; }
+	case LIS_MATRIX_COO:
+		/* ref lis_matrix_coo.c:810-833: the SOURCE's three arrays are sorted in place by row, then copied row by row.  The source stays sorted as that leaves it; its
+		 * HBM copy listed the triplets in the old order and goes (which also opens the watched arrays for the sort) */
+		for (LIS_INT k = 0; k < A->nnz && !err; k++)
+			if (A->row[k] < 0 || A->row[k] >= n) err = LISI_ERR(LIS_ERR_ILL_ARG, "COO matrix: row index %D of entry %D lies outside [0, %D)\n", A->row[k], k, n);
+		if (err) break;
+		if (MDEV(A)->ready) lisd_mat_free(A);
+		lisi_sort_iid(0, A->nnz - 1, A->row, A->col, A->value);
+		for (LIS_INT k = 0; k < A->nnz; k++) count[A->row[k]]++;
+		if ((err = csr_out_alloc(&c, n, count))) break;
+		memcpy(c.index, A->col, sizeof(LIS_INT) * (size_t)A->nnz);
+		memcpy(c.value, A->value, sizeof(LIS_SCALAR) * (size_t)A->nnz);
+		break;
+	case LIS_MATRIX_DNS:
+		/* ref lis_matrix_dns.c:846-895: value != 0 is kept, columns ascending */
+		#pragma omp parallel for schedule(static) num_threads(lisi_host_threads())
+		for (LIS_INT i = 0; i < n; i++) { LIS_INT cnt = 0; for (LIS_INT j = 0; j < A->np; j++) cnt += A->value[(size_t)j * n + i] != 0.0; count[i] = cnt; }
+		if ((err = csr_out_alloc(&c, n, count))) break;
+		#pragma omp parallel for schedule(static) num_threads(lisi_host_threads())
+		for (LIS_INT i = 0; i < n; i++) {
+			LIS_INT k = c.ptr[i];
+			for (LIS_INT j = 0; j < A->np; j++) { const LIS_SCALAR v = A->value[(size_t)j * n + i]; if (v != 0.0) { c.value[k] = v; c.index[k] = j; k++; } }
+		}
+		break;
 	default:
 		err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	}
@@ -452,6 +539,13 @@ LIS_INT lisi_matrix_deep_copy(LIS_MATRIX A, LIS_MATRIX B)
 		DUP(bptr, A->bptr, LIS_INT, (size_t)A->nr + 1); DUP(bindex, A->bindex, LIS_INT, A->bnnz);
 		DUP(value, A->value, LIS_SCALAR, (size_t)A->bnnz * A->bnr * A->bnc);
 		return finish(B, lis_matrix_set_bsr(A->bnr, A->bnc, A->bnnz, bptr, bindex, value, B));
+	case LIS_MATRIX_COO: {
+		LIS_INT *col = NULL;
+		DUP(row, A->row, LIS_INT, A->nnz); DUP(col, A->col, LIS_INT, A->nnz); DUP(value, A->value, LIS_SCALAR, A->nnz);
+		return finish(B, lis_matrix_set_coo(A->nnz, row, col, value, B)); }
+	case LIS_MATRIX_DNS:
+		DUP(value, A->value, LIS_SCALAR, n * (size_t)A->np);
+		return finish(B, lis_matrix_set_dns(value, B));
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	}
@@ -481,6 +575,8 @@ static LIS_INT convert_impl(LIS_MATRIX Ain, LIS_MATRIX Aout)
 	LISCHK(lisi_matrix_check(Ain, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisi_matrix_check(Aout, LISI_CHECK_NULL));
 	const LIS_INT want = Aout->matrix_type;
+	LISCHK(lisi_coo_dns_one_rank(Ain->matrix_type));        /* COO and DNS, as a source or as a target: one rank, refused before anything is touched */
+	LISCHK(lisi_coo_dns_one_rank(want));
 	if (MDEV(Ain)->device_only) {          /* born in HBM: ELL, DIA, CSC and BSR are built there; what they leave to the host (JAD, rows out of order for DIA / CSC,
 		                                        * block rows of more than 96 blocks) runs on a host copy of the arrays, made for this conversion */
 		int done = 0;

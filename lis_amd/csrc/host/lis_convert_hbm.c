@@ -1,17 +1,24 @@
 /*
  * lis_convert_hbm.c -- conversions in HBM (kernels/convert.hip).
  *
- * lis_matrix_convert(Ain, Aout) with Ain = a CSR matrix whose HBM copy exists: the target layout is built FROM that copy by kernels --
+ * lis_matrix_convert(Ain, Aout) with Ain = a CSR matrix whose HBM copy exists: the target layout (ELL, DIA, CSC, JAD, BSR, COO or DNS) is built FROM that copy by kernels --
  * the arrays the host routines of lis_convert.c build, bit for bit -- and becomes both Aout's HBM copy and the source of Aout's HOST
  * arrays.  Those the Lis API promises (A->index, A->value ...), but a program that only multiplies never reads them: they get address
  * space without access (lis_pages.c), bound to the device buffer that holds their contents, and come home on their first touch.
  * What the product of the new matrix runs on is decided by the code mat_upload decides it with (lis_upload.c: lisd_row_form_wanted,
  * lisd_row_form_adopt, lisd_try_bsr_row_form, lisd_ell_index_codes, lisd_fmt_find_plane): the constant-coefficient row form (value
- * records) for ELL / DIA / BSR where the values allow it, CSC and JAD as CSR rows in the reference's summation order, else the native arrays.
+ * records) for ELL / DIA / BSR where the values allow it, CSC, JAD and COO as CSR rows in the reference's summation order, else the native arrays (DNS always).
  *
  * lisd_convert_csr is a gate, one builder per target and a tail.  A builder allocates through the context's scope (TMP) and releases a buffer when d or a lazy host
  * array takes it; it returns wherever it likes, and the gate frees what is left in the scope -- after a failure also the lazy arrays and what d holds. */
 #include "lis_internal.h"
+
+/* what only the COO and DNS builders call is referenced weakly: tests/c/upload_cases.c links this file against stubs of the calls the five older builders make, and
+ * the library always holds the real ones */
+extern int liship_csr_to_coo(int n, const int *ptr, int *row, void *stream) __attribute__((weak));
+extern int liship_csr_to_dns_f64(int n, int np, const int *ptr, const int *index, const double *value, double *dns, void *stream) __attribute__((weak));
+extern LIS_INT lis_matrix_set_coo(LIS_INT nnz, LIS_INT *row, LIS_INT *col, LIS_SCALAR *value, LIS_MATRIX A) __attribute__((weak));
+extern LIS_INT lis_matrix_set_dns(LIS_SCALAR *value, LIS_MATRIX A) __attribute__((weak));
 
 #define CONV_TMP 16
 typedef struct {
@@ -235,9 +242,52 @@ static LIS_INT build_bsr(conv_t *c, int *built)
 	return LIS_SUCCESS;
 }
 
+/* ---- COO.  The triplets of csr2coo are the rows themselves: row[k] from the row starts, col and value copies of index and value.  The product's arrays are
+ * rows in stored order (a COO copy IS CSR rows, lis_upload.c): ONE copy of col / value serves as d->index / d->value and backs the host arrays, as the
+ * dense array does below; only row[] is extra, and the pages own it */
+static LIS_INT build_coo(conv_t *c, int *built)
+{
+	lisd_mat *d = c->d;
+	const lisd_mat *sd = c->sd;
+	const int n = c->n, nnz = c->nnz;
+	int *crow = NULL, *ccol = NULL; double *cval = NULL;
+	if (!liship_csr_to_coo || !lis_matrix_set_coo) return LIS_SUCCESS;          /* (linked without them: the host routine serves) */
+	TMP(crow, nnz); TMP(ccol, nnz); TMP(cval, nnz);
+	HIPCHK(liship_csr_to_coo(n, sd->ptr, crow, lisg.stream));
+	HIPCHK(liship_memcpy_d2d(ccol, sd->index, sizeof(int) * (size_t)nnz, lisg.stream));
+	HIPCHK(liship_memcpy_d2d(cval, sd->value, sizeof(double) * (size_t)nnz, lisg.stream));
+	HIPCHK(lisd_malloc((void **)&d->ptr, sizeof(int) * ((size_t)n + 1)));
+	HIPCHK(liship_memcpy_d2d(d->ptr, sd->ptr, sizeof(int) * ((size_t)n + 1), lisg.stream));
+	d->type = LIS_MATRIX_CSR; d->index = (int *)tmp_release(c, ccol); d->value = (double *)tmp_release(c, cval);
+	d->coo_in_order = 1;
+	LISCHK(lisd_csr_plan(&d->plan, n, d->ptr, d->index, d->value));
+	LISCHK(lazy_bind(c, sizeof(int) * (size_t)nnz, crow, 1));
+	LISCHK(lazy_bind(c, sizeof(int) * (size_t)nnz, ccol, 0));
+	LISCHK(lazy_bind(c, sizeof(double) * (size_t)nnz, cval, 0));
+	*built = 1;
+	return lis_matrix_set_coo(nnz, (LIS_INT *)c->lazy[0], (LIS_INT *)c->lazy[1], (LIS_SCALAR *)c->lazy[2], c->Aout);
+}
+
+/* ---- DNS: one array serves the product and backs the host array */
+static LIS_INT build_dns(conv_t *c, int *built)
+{
+	lisd_mat *d = c->d;
+	const lisd_mat *sd = c->sd;
+	const size_t count = (size_t)c->n * (size_t)c->np;
+	double *dns = NULL;
+	if (!liship_csr_to_dns_f64 || !lis_matrix_set_dns) return LIS_SUCCESS;      /* (linked without them: the host routine serves) */
+	TMP(dns, count);
+	HIPCHK(liship_csr_to_dns_f64(c->n, c->np, sd->ptr, sd->index, sd->value, dns, lisg.stream));
+	d->type = LIS_MATRIX_DNS; d->value = (double *)tmp_release(c, dns);
+	LISCHK(lazy_bind(c, sizeof(double) * count, dns, 0));
+	*built = 1;
+	return lis_matrix_set_dns((LIS_SCALAR *)c->lazy[0], c->Aout);
+}
+
 /* ---- the gate.  *done = 0: not a case for this path (the caller converts on the host) */
 static const struct { LIS_INT type; int needs_sorted_rows; LIS_INT (*build)(conv_t *c, int *built); } targets[] = {
 	{LIS_MATRIX_ELL, 0, build_ell}, {LIS_MATRIX_DIA, 1, build_dia}, {LIS_MATRIX_CSC, 1, build_csc}, {LIS_MATRIX_JAD, 0, build_jad}, {LIS_MATRIX_BSR, 0, build_bsr},
+	{LIS_MATRIX_COO, 0, build_coo}, {LIS_MATRIX_DNS, 0, build_dns},
 };
 #define TARGETS ((int)(sizeof(targets) / sizeof(targets[0])))
 

@@ -1764,7 +1764,11 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 			                nesolver == LIS_ESOLVER_GSI ? "gpi, gii" : "gpi, gii, grqi, gcr");
 		}
 	}
-	if (B != NULL && (A->is_splited || B->is_splited || !lisi_format_served(B->matrix_type) || B->np != B->n || A->np != A->n)) {
+	if (B != NULL && (lisi_format_coo_dns(A->matrix_type) || lisi_format_coo_dns(B->matrix_type) || lisi_format_coo_dns(estorage))) {
+		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;              /* (explicit: a COO copy looks like CSR in HBM, and lis_matrix_shift_matrix refuses both) */
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_gesolve: A and B in COO or DNS storage (or -estorage coo | dns) are not served: lis_matrix_shift_matrix does not take them (A, B and x are untouched)\n");
+	}
+	if (B != NULL && (A->is_splited || B->is_splited || !lisi_format_swept(B->matrix_type) || B->np != B->n || A->np != A->n)) {
 		esolver->retcode = LIS_ERR_NOT_IMPLEMENTED;
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_gesolve: A and B must be unsplit matrices in a served storage format without ghost columns (lis_matrix_shift_matrix)\n");
 	}

@@ -92,6 +92,7 @@ typedef struct {
 	/* scratch for the raw-array entry points lis_matvec_<fmt>(A, x[], y[]) */
 	double *sx, *sy; size_t scap;
 	/* split JAD matrix (lis_split.c): d->ptr/index/value/plan hold L, these hold U, the diagonal and a work vector */
+	int coo_in_order;          /* COO: the rows of the copy list the triplets in ascending k over the whole matrix (row[] non-decreasing: the in-place row form, a copy built in HBM from CSR rows), so the transposed copy is the CSR transposition of these rows */
 	int split_jad;
 	int *u_ptr, *u_index;
 	double *u_value, *dsplit, *jw;
@@ -303,11 +304,15 @@ LIS_INT lisc_allgather_host(const void *send, void *recv, size_t bytes);
 
 /* ---- matrix internals shared between files */
 LIS_INT lisi_matrix_check(LIS_MATRIX A, int level);
-int     lisi_format_served(LIS_INT type);                          /* one of the six storage formats whose products are served (lis_matvec.c) */
+int     lisi_format_served(LIS_INT type);                          /* one of the eight storage formats whose products are served (lis_matvec.c) */
+int     lisi_format_swept(LIS_INT type);                           /* ... of the six that lis_matvec_optimize times, lis_matrix_shift_matrix and lis_gesolve take */
+int     lisi_format_coo_dns(LIS_INT type);                         /* COO or DNS: one rank, never split */
+LIS_INT lisi_coo_dns_one_rank(LIS_INT type);                       /* LIS_ERR_NOT_IMPLEMENTED for COO / DNS in a job of several ranks */
 void    lisi_raw_product(LIS_MATRIX A, LIS_INT fmt, LIS_SCALAR x[], LIS_SCALAR y[], int transposed);   /* lis_matvec_<fmt> / lis_matvech_<fmt> on raw host arrays (lis_matvec.c) */
 int     lisi_host_threads(void);      /* threads the host-side conversions may use: affinity mask capped by the cgroup CPU quota, at most 32 */
 /* ---- split form (lis_split.c) */
 void    lisi_sortr_ii(LIS_INT lo, LIS_INT hi, LIS_INT *key, LIS_INT *tag);    /* the reference's descending quicksort (lis_convert.c) */
+void    lisi_sort_iid(LIS_INT lo, LIS_INT hi, LIS_INT *i1, LIS_INT *i2, LIS_SCALAR *d1);   /* the reference's ascending quicksort of triplets by i1 (lis_convert.c) */
 void    lisi_matrix_dlu_destroy(LIS_MATRIX A);
 LIS_INT lisi_split_rows(LIS_MATRIX A, LIS_INT *rows, LIS_INT **ptr, LIS_INT **idx, LIS_SCALAR **val, int *from_zero);
 LIS_INT lisi_matrix_bscale_bsr(LIS_MATRIX A, LIS_VECTOR B);                  /* -scale jacobi -storage bsr (lis_scale.c) */

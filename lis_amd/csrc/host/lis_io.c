@@ -403,7 +403,27 @@ fail:
 
 /* `array` files: nr*nc values, one per line, column-major (ref lis_input_mm.c:462-697), held by the reference as
  * LIS_MATRIX_DNS and converted to the requested type through CSR keeping value != 0, columns ascending
- * (lis_matrix_dns.c:823-915).  DNS itself is not a served format, so the CSR is built directly. */
+ * (lis_matrix_dns.c:823-915).  For any other target than DNS the CSR is built directly (mm_read_dense); a matrix whose type is set to DNS keeps the
+ * values as they are read (mm_read_dns: nr x nr values, the size line's nc is not looked at, as in mm_read_dense). */
+static LIS_INT mm_read_dns(slurp_t *s, const mm_head *h, LIS_MATRIX A)
+{
+	if (h->isbin) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "binary Matrix Market array input is not implemented\n");
+	LISCHK(lis_matrix_set_size(A, 0, h->nr));
+	if (A->my_rank == 0) { printf("matrix size = %d x %d (%d nonzero entries)\n\n", h->nr, h->nc, h->nr * h->nc); fflush(stdout); }
+	const LIS_INT n = A->n;
+	LIS_SCALAR *value = NULL;
+	LISCHK(lis_matrix_malloc_dns(n, n, &value));
+	for (LIS_INT j = 0; j < n; j++)
+		for (LIS_INT i = 0; i < n; i++) {                  /* the file is column-major, as the storage is */
+			char *b, *e; double v;
+			if (!next_line(s, &b, &e) || !scan_double(&b, &v)) { lis_free(value); return LISI_ERR(LIS_ERR_FILE_IO, "file i/o error\n"); }
+			value[(size_t)j * n + i] = v;
+		}
+	LIS_INT err = lis_matrix_set_dns(value, A);
+	if (err) { lis_free(value); return err; }
+	return lis_matrix_assemble(A);
+}
+
 static LIS_INT mm_read_dense(slurp_t *s, const mm_head *h, LIS_MATRIX A)
 {
 	if (h->isbin) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "binary Matrix Market array input is not implemented\n");
@@ -588,9 +608,8 @@ LIS_INT lis_input(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, char *filename)
 	memset(&h, 0, sizeof(h));
 	err = mm_banner(&s, "matrix", &h);
 	if (!err) err = mm_size(&s, &h);
-	if (!err && !h.coordinate && want == LIS_MATRIX_DNS)
-		err = LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "dense storage (LIS_MATRIX_DNS) is not served by liblis_amd\n");
-	if (!err) err = h.coordinate ? mm_read_csr(&s, &h, A, b, x) : mm_read_dense(&s, &h, A);
+	if (!err && !h.coordinate && want == LIS_MATRIX_DNS) err = lisi_coo_dns_one_rank(want);
+	if (!err) err = h.coordinate ? mm_read_csr(&s, &h, A, b, x) : (want == LIS_MATRIX_DNS ? mm_read_dns(&s, &h, A) : mm_read_dense(&s, &h, A));
 	free(s.buf);
 	if (err) return err;
 	err = lisi_matrix_retype(A, want, 0);

@@ -198,6 +198,21 @@ LIS_INT lis_matrix_malloc_jad(LIS_INT n, LIS_INT nnz, LIS_INT maxnzr, LIS_INT **
 	ALLOC_OR_FAIL(*index, LIS_INT, nnz); ALLOC_OR_FAIL(*value, LIS_SCALAR, nnz);
 	return LIS_SUCCESS;
 }
+LIS_INT lis_matrix_malloc_coo(LIS_INT nnz, LIS_INT **row, LIS_INT **col, LIS_SCALAR **value)
+{	/* ref lis_matrix_coo.c:169-201 */
+	*row = NULL; *col = NULL; *value = NULL;
+	ALLOC_OR_FAIL(*row, LIS_INT, nnz); ALLOC_OR_FAIL(*col, LIS_INT, nnz); ALLOC_OR_FAIL(*value, LIS_SCALAR, nnz);
+	return LIS_SUCCESS;
+}
+LIS_INT lis_matrix_malloc_dns(LIS_INT n, LIS_INT np, LIS_SCALAR **value)
+{	/* ref lis_matrix_dns.c:107-122; n * np in size_t (the reference multiplies in LIS_INT) */
+	*value = NULL;
+	if (n < 0 || np < 0) return LISI_ERR(LIS_ERR_ILL_ARG, "n(=%D) or np(=%D) are less than 0\n", n, np);
+	const size_t count = (size_t)n * (size_t)np;
+	*value = (LIS_SCALAR *)matrix_array(sizeof(LIS_SCALAR) * (count ? count : 1));
+	if (!*value) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D x %D\n", n, np);
+	return LIS_SUCCESS;
+}
 
 /* the reference's quirk: set_<fmt> on a matrix whose status is not NULL returns success WITHOUT
  * adopting the arrays (lis_matrix_csr.c:88-91) */
@@ -259,6 +274,22 @@ LIS_INT lis_matrix_set_jad(LIS_INT nnz, LIS_INT maxnzr, LIS_INT *perm, LIS_INT *
 	SET_GUARD(A);
 	A->row = perm; A->ptr = ptr; A->index = index; A->value = value;
 	A->is_copy = LIS_FALSE; A->status = -LIS_MATRIX_JAD; A->nnz = nnz; A->maxnzr = maxnzr;
+	return LIS_SUCCESS;
+}
+
+LIS_INT lis_matrix_set_coo(LIS_INT nnz, LIS_INT *row, LIS_INT *col, LIS_SCALAR *value, LIS_MATRIX A)
+{	/* ref lis_matrix_coo.c:77-107 */
+	SET_GUARD(A);
+	A->row = row; A->col = col; A->value = value;
+	A->is_copy = LIS_FALSE; A->status = -LIS_MATRIX_COO; A->nnz = nnz;
+	return LIS_SUCCESS;
+}
+
+LIS_INT lis_matrix_set_dns(LIS_SCALAR *value, LIS_MATRIX A)
+{	/* ref lis_matrix_dns.c:80-104: n x np values, column-major; nnz stays what it was */
+	SET_GUARD(A);
+	A->value = value;
+	A->is_copy = LIS_FALSE; A->status = -LIS_MATRIX_DNS;
 	return LIS_SUCCESS;
 }
 
@@ -495,9 +526,10 @@ LIS_INT lis_matrix_get_diagonal(LIS_MATRIX A, LIS_VECTOR D)
 	}
 	const LIS_INT n = A->n;
 	LISCHK(lisp_fill_matrix(A));
-	LISCHK(lisd_vec_host_write(D, (size_t)(D->np + D->pad) > (size_t)n));   /* the host array is about to be written (entries beyond n keep what they hold) */
+	const int coo_keeps = A->matrix_type == LIS_MATRIX_COO && !A->is_splited;    /* COO writes only the rows that store an (i,i): the others keep what D held (lis_matrix_coo.c:343-349) */
+	LISCHK(lisd_vec_host_write(D, coo_keeps || (size_t)(D->np + D->pad) > (size_t)n));   /* the host array is about to be written (entries beyond n keep what they hold) */
 	LIS_SCALAR *out = D->value;
-	for (LIS_INT i = 0; i < n; i++) out[i] = 0.0;
+	if (!coo_keeps) for (LIS_INT i = 0; i < n; i++) out[i] = 0.0;
 	if (A->is_splited) {                /* the split form holds the diagonal itself (ref lis_matrix_csr.c:532-545, lis_matrix_bsr.c get_diagonal) */
 		if (A->matrix_type == LIS_MATRIX_BSR) {
 			const size_t bs = (size_t)A->bnr * A->bnc;
@@ -538,6 +570,12 @@ LIS_INT lis_matrix_get_diagonal(LIS_MATRIX A, LIS_VECTOR D)
 				}
 			}
 		break; }
+	case LIS_MATRIX_COO:        /* ref lis_matrix_coo.c:343-349: the LAST stored (i,i) wins; a row without one keeps what d[i] held */
+		for (LIS_INT k = 0; k < A->nnz; k++) if (A->row[k] == A->col[k]) out[A->row[k]] = A->value[k];
+		break;
+	case LIS_MATRIX_DNS:        /* ref lis_matrix_dns.c:223-241: value[i*n + i] */
+		for (LIS_INT i = 0; i < n; i++) out[i] = A->value[(size_t)i * n + i];
+		break;
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	}

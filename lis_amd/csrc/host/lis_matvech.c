@@ -126,7 +126,10 @@ LIS_INT lisd_mat_ready_t(LIS_MATRIX A)
 	 * through the reverse exchange -- lisd_spmv_t / lisc_reduce_device, the reference's LIS_MATVEC_REDUCE around lis_matvech_<fmt>, src/matvec/lis_matvec.c:191-349) */
 	if (d->t_ready) return LIS_SUCCESS;
 	LISCHK(lisd_mat_ready(A));
-	if (!(A->matrix_type == LIS_MATRIX_CSR && d->type == LIS_MATRIX_CSR)) LISCHK(lisp_fill_matrix(A));   /* the host arrays are read below (and handed to the runtime) */
+	if (d->type == LIS_MATRIX_DNS) { d->t_rows = A->np; d->t_ready = 1; return LIS_SUCCESS; }      /* dense: the transposed kernel streams the same array (lisd_spmv_t) */
+	/* the rows of the copy are the walk itself: a CSR matrix, and a COO matrix whose triplets are in row order (stored order = position in the rows) */
+	const int rows_are_walk = d->type == LIS_MATRIX_CSR && (A->matrix_type == LIS_MATRIX_CSR || (A->matrix_type == LIS_MATRIX_COO && d->coo_in_order));
+	if (!rows_are_walk) LISCHK(lisp_fill_matrix(A));   /* the host arrays are read below (and handed to the runtime) */
 	const LIS_INT type = A->matrix_type, n = A->n;
 	/* rows of A^T = local columns.  BSR in a multi-rank job: the ghost block columns start on a fresh block column, i.e. pad entries behind the owned ones
 	 * (lis_matrix_bsr.c:425-428; the halo lands at x[n + pad ...), lis_comm.c), so the ghost rows of A^T reach np + pad -- with np alone the walk dropped the
@@ -166,8 +169,32 @@ LIS_INT lisd_mat_ready_t(LIS_MATRIX A)
 		LISCHK(upload((void **)&d->t_ptr, A->ptr, sizeof(int) * ((size_t)np + 1)));
 		LISCHK(upload((void **)&d->t_index, A->index, sizeof(int) * (size_t)A->nnz));
 		LISCHK(upload((void **)&d->t_value, A->value, sizeof(double) * (size_t)A->nnz));
-	} else if (type == LIS_MATRIX_CSR && d->type == LIS_MATRIX_CSR) {
-		/* CSR: the HBM copy is transposed in HBM (transpose.hip): no host pass, works for matrices born on the device */
+	} else if (type == LIS_MATRIX_COO && !rows_are_walk) {
+		/* COO: lis_matvech_coo walks the triplets in stored order, y[col[k]] += value[k] * x[row[k]] (lis_matvec_coo.c:116-128) -- a stable grouping by COLUMN, made
+		 * in HBM like the row form (liship_group_by_key_f64), from the triplets, which go up once more (the row form released them).  Triplets in row order never
+		 * get here: the branch below transposes their rows */
+		int *drow = NULL, *dcol = NULL, flags = 0; double *dval = NULL;
+		LIS_INT err = lisd_upload_i(&drow, A->row, (size_t)A->nnz);
+		if (!err) err = lisd_upload_i(&dcol, A->col, (size_t)A->nnz);
+		if (!err) err = lisd_upload_d(&dval, A->value, (size_t)A->nnz);
+		d->t_nnz = A->nnz;
+		int rc = 0;
+		if (!err) rc = lisd_malloc((void **)&d->t_ptr, sizeof(int) * ((size_t)np + 1) + 16);
+		if (!err && !rc) rc = lisd_malloc((void **)&d->t_index, sizeof(int) * (size_t)A->nnz + 16);
+		if (!err && !rc) rc = lisd_malloc((void **)&d->t_value, sizeof(double) * (size_t)A->nnz + 16);
+		if (!err && !rc) rc = liship_key_facts(np, A->nnz, dcol, &flags, lisg.stream);
+		if (!err && !rc && (flags & 2)) err = LISI_ERR(LIS_ERR_ILL_ARG, "COO matrix: a column index lies outside [0, %D)\n", np);
+		if (!err && !rc) rc = liship_group_by_key_f64(np, A->nnz, dcol, drow, dval, d->t_ptr, d->t_index, d->t_value, lisg.stream);
+		if (!err && rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
+		(void)liship_stream_synchronize(lisg.stream);                /* (a copy may still be queued into the triplets after a failure) */
+		(void)liship_free(drow); (void)liship_free(dcol); (void)liship_free(dval);
+		if (err) {                                                   /* nothing half-made stays behind: the next lis_matvech starts over */
+			(void)liship_free(d->t_ptr); (void)liship_free(d->t_index); (void)liship_free(d->t_value);
+			d->t_ptr = NULL; d->t_index = NULL; d->t_value = NULL; d->t_nnz = 0;
+			return err;
+		}
+	} else if (rows_are_walk) {
+		/* CSR (and COO in row order): the HBM copy is transposed in HBM (transpose.hip): no host pass, works for matrices born on the device */
 		int *work = NULL;
 		d->t_nnz = d->nnz;
 		HIPCHK(lisd_malloc((void **)&d->t_ptr, sizeof(int) * ((size_t)np + 1) + 16));
@@ -233,6 +260,11 @@ LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy)
 {
 	lisd_mat *d = MDEV(A);
 	LISCHK(lisd_mat_ready_t(A));
+	if (d->type == LIS_MATRIX_DNS) {
+		/* dense: the row chunks of the reference's OpenMP branch (lis_matvec_dns.c:87-130), one chunk by default, T in the reference-order mode */
+		HIPCHK(liship_spmv_dns_t_f64(A->n, A->np, lisg.ref_reductions > 1 ? lisg.ref_reductions : 1, d->value, dx, dy, lisg.stream));
+		return LIS_SUCCESS;
+	}
 	if (lisg.ref_reductions > 1 && A->matrix_type == LIS_MATRIX_CSR)
 		/* reference-order mode at T > 1: the OpenMP build's per-thread scatter buffers group a column's terms by row chunk (lis_matvec_csr.c:207-236).
 		 * CSR here, ELL below; DIA, JAD and BSR keep the one-thread order (their threaded walks group differently again) */
@@ -252,6 +284,7 @@ LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy)
 LIS_INT lis_matvech(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 {	/* ref src/matvec/lis_matvec.c:191-349; Y grows to np+pad like LIS_MATVEC_REDUCE0 (lis_matvec.h:60-72) */
 	if (!lisi_format_served(A->matrix_type)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
+	LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
 	LISCHK(lisd_mat_ready_t(A));
 	if (A->np + A->pad > Y->np + Y->pad) { Y->np = A->np; Y->pad = A->pad; }
 	double *dx, *dy;
@@ -270,3 +303,5 @@ void lis_matvech_ell(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_pr
 void lis_matvech_dia(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_DIA, x, y, 1); }
 void lis_matvech_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_JAD, x, y, 1); }
 void lis_matvech_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_BSR, x, y, 1); }
+void lis_matvech_coo(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_COO, x, y, 1); }
+void lis_matvech_dns(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_DNS, x, y, 1); }

@@ -8,7 +8,7 @@
 #include "lis_internal.h"
 
 /* The launchers of one kernel family; all return HIP codes.  The table keys on the HBM copy (d->type, d->split_jad), never on
- * A->matrix_type: CSC and plain JAD uploads, and the row forms of ELL / DIA / BSR, are CSR here. */
+ * A->matrix_type: CSC, COO and plain JAD uploads, and the row forms of ELL / DIA / BSR, are CSR here. */
 #define PRODUCT lisd_mat *d, LIS_MATRIX A, double *x, double *y                 /* y = A x: the HBM copy, its matrix, device pointers */
 #define DOTS const double *w, int want_sumsq, double *result                     /* result[0] = <w,y>, result[1] = <y,y> when want_sumsq (HBM) */
 typedef struct {
@@ -79,12 +79,18 @@ static int split_jad_whole(PRODUCT)
 	return rc;
 }
 
+/* dense: no row ranges (several ranks are refused), no fused dot (the dispatcher runs the product and one reduction pass).  The launcher is referenced weakly:
+ * tests/c/product_cases.c links this file alone against stubs of the launchers of the six formats it walks, and the library always holds the real one */
+extern int liship_spmv_dns_f64(int n, int np, const double *value, const double *x, double *y, void *stream) __attribute__((weak));
+static int dns_whole(PRODUCT) { return liship_spmv_dns_f64 ? liship_spmv_dns_f64(d->n, d->np, d->value, x, y, lisg.stream) : LISHIP_ERR_ARG; }
+
 static const fmt_ops csr_ops = {0, csr_whole, csr_rows, csr_dot, csr_whole};
 static const fmt_ops ell_ops = {0, ell_whole, ell_rows, ell_dot, ell_index};       /* (no second attempt with the codes, no strips again) */
 static const fmt_ops dia_ops = {0, dia_whole, dia_rows, dia_dot, dia_launch};
 static const fmt_ops jad_ops = {0, jad_whole, NULL, NULL, NULL};
 static const fmt_ops bsr_ops = {1, bsr_whole, bsr_rows, bsr_dot, bsr_whole};
 static const fmt_ops split_jad_ops = {0, split_jad_whole, NULL, NULL, NULL};
+static const fmt_ops dns_ops = {0, dns_whole, NULL, NULL, NULL};
 
 static const fmt_ops *ops_of(const lisd_mat *d)
 {
@@ -95,6 +101,7 @@ static const fmt_ops *ops_of(const lisd_mat *d)
 	case LIS_MATRIX_DIA: return &dia_ops;
 	case LIS_MATRIX_JAD: return &jad_ops;
 	case LIS_MATRIX_BSR: return &bsr_ops;
+	case LIS_MATRIX_DNS: return &dns_ops;
 	default: return NULL;
 	}
 }

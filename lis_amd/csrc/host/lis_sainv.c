@@ -228,9 +228,27 @@ static LIS_INT factor_build(LIS_MATRIX A, double tol, lisd_sainv **out)
 	const double t0 = lis_wtime();
 	lisd_sainv *s = (lisd_sainv *)calloc(1, sizeof(lisd_sainv));
 	if (!s) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)sizeof(lisd_sainv));
+	int *cp = NULL, *ci = NULL; double *cv = NULL;
 	if (A->matrix_type == LIS_MATRIX_CSR) {
 		if ((err = lisp_fill_matrix(A))) goto out;
 		ptr = A->ptr; index = A->index; value = A->value;
+	} else if (A->matrix_type == LIS_MATRIX_COO) {
+		/* COO: lis_matrix_convert would sort A's own arrays in place (lis_convert.c) and drop the HBM copy this factor is about to be cached on.  The rows are
+		 * read off by a STABLE grouping of the triplets instead, A untouched: for a matrix that -storage coo made of CSR rows these ARE those rows, entry for
+		 * entry, which is what the reference builds its factor from (it creates the preconditioner before it converts: lis_solver.c:384, :749) */
+		if ((err = lisp_fill_matrix(A))) goto out;
+		const LIS_INT nnz = A->nnz;
+		cp = (int *)calloc((size_t)n + 2, sizeof(int));
+		ci = (int *)malloc(sizeof(int) * (size_t)(nnz > 0 ? nnz : 1));
+		cv = (double *)malloc(sizeof(double) * (size_t)(nnz > 0 ? nnz : 1));
+		if (!cp || !ci || !cv) { err = LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", nnz); goto out; }
+		for (LIS_INT k = 0; k < nnz; k++) {
+			if (A->row[k] < 0 || A->row[k] >= n) { err = LISI_ERR(LIS_ERR_ILL_ARG, "COO matrix: a row index lies outside [0, %D)\n", (LIS_INT)n); goto out; }
+			cp[A->row[k] + 2]++;
+		}
+		for (int r = 0; r < n; r++) cp[r + 2] += cp[r + 1];            /* cp[r + 1]: where row r's next entry goes; after the fill: where row r ends */
+		for (LIS_INT k = 0; k < nnz; k++) { const int at = cp[A->row[k] + 1]++; ci[at] = A->col[k]; cv[at] = A->value[k]; }
+		ptr = cp; index = ci; value = cv;
 	} else {
 		if ((err = lis_matrix_duplicate(A, &B)) || (err = lis_matrix_set_type(B, LIS_MATRIX_CSR)) || (err = lis_matrix_convert(A, B))) goto out;
 		ptr = B->ptr; index = B->index; value = B->value;
@@ -248,6 +266,7 @@ static LIS_INT factor_build(LIS_MATRIX A, double tol, lisd_sainv **out)
 	lisg.sainv_builds++;
 out:
 	if (B) lis_matrix_destroy(B);
+	free(cp); free(ci); free(cv);
 	free(wp); free(wi); free(wv); free(zp); free(zi); free(zv); free(dd);
 	if (err) { lisd_sainv_free(s); return err; }
 	*out = s;

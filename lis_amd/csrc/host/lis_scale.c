@@ -7,7 +7,7 @@
  * (the truth in both residency modes) and drops the HBM copy, which is rebuilt on the next product.
  * The rounding of every entry is the reference's, including its per-format association:
  *     jacobi      v *= d[row]                                   (all formats)
- *     symm_diag   CSR: (v*d[row])*d[col]   CSC: (v*d[col])*d[row]   ELL/DIA/JAD/BSR: v*(d[row]*d[col])
+ *     symm_diag   CSR: (v*d[row])*d[col]   CSC: (v*d[col])*d[row]   ELL/DIA/JAD/BSR/DNS: v*(d[row]*d[col])   COO: v*(d[row]*d[row]), the reference's own
  * with d = 1/diag (jacobi) or 1/sqrt|diag| (symm_diag); b is scaled by d; A and b stay scaled afterwards
  * (A->is_scaled, B->is_scaled), exactly as the reference leaves them.
  */
@@ -119,6 +119,21 @@ static LIS_INT scale_values(LIS_MATRIX A, const double *d, int symm)
 					}
 			}
 		break; }
+	case LIS_MATRIX_COO:        /* ref lis_matrix_coo.c:426-432, :456-461: the symmetric form multiplies by d[row]*d[ROW] -- the reference's own, restated */
+		for (LIS_INT k = 0; k < A->nnz; k++) {
+			const LIS_INT i = A->row[k];
+			if (symm) A->value[k] *= d[i] * d[i];
+			else A->value[k] *= d[i];
+		}
+		break;
+	case LIS_MATRIX_DNS:        /* ref lis_matrix_dns.c:453-494 */
+		for (LIS_INT j = 0; j < A->np; j++)
+			for (LIS_INT i = 0; i < n; i++) {
+				const size_t k = (size_t)j * n + i;
+				if (symm) A->value[k] *= d[i] * d[j];
+				else A->value[k] *= d[i];
+			}
+		break;
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	}

@@ -12,6 +12,8 @@
  *                               end of index[]; here nothing is shifted
  *   JAD  lis_matrix_jad.c:490   entries with index == row[position] in jagged-diagonal order until n of them were found (one chunk: the serial branch)
  *   BSR  lis_matrix_bsr.c:748   the diagonal entries of the blocks that cover rows i .. of each block row, the first covering block first
+ *   COO  lis_matrix_coo.c:357   EVERY stored entry with row == col, duplicates each
+ *   DNS  lis_matrix_dns.c:244   value[i n + i], every row
  * A split matrix (is_splited) shifts A->D only (for BSR the diagonals of its blocks), every row, whether the row had a diagonal entry or not.
  * value -= sigma rounds: shift(s) then shift(-s) does not give the bits back.  The reference has that drift and so has this library.
  *
@@ -22,7 +24,7 @@
  *                               was derived from the old values and makes the plan again from the HBM arrays.  The host arrays, where they exist, get the same edit on
  *                               the host inside lisd_mat_host_edit_begin / _end, so that the write watch (lis_pages.c) does not take it for the program's and throw the
  *                               copy away.  No matrix array crosses the bus.  The plan rebuild costs 10 ms per shift at 256^3, the host edit ~300 ms.
- *   the other five formats      the host arrays are edited as above and the HBM copy is dropped (what lis_amd_matrix_host_modified does): the next product uploads.
+ *   the other seven formats     the host arrays are edited as above and the HBM copy is dropped (what lis_amd_matrix_host_modified does): the next product uploads.
  *   HBM-only and not CSR        refused (such a matrix has no host arrays to edit).
  */
 #include "lis_internal.h"
@@ -74,6 +76,12 @@ static void shift_host(LIS_MATRIX A, LIS_SCALAR sigma)
 			}
 		}
 		break; }
+	case LIS_MATRIX_COO:        /* ref lis_matrix_coo.c:377-383: every stored (i,i), duplicates each */
+		for (LIS_INT k = 0; k < A->nnz; k++) if (A->row[k] == A->col[k]) A->value[k] -= sigma;
+		break;
+	case LIS_MATRIX_DNS:        /* ref lis_matrix_dns.c:268-271: value[i*n + i] */
+		for (LIS_INT i = 0; i < n; i++) A->value[(size_t)i * n + i] -= sigma;
+		break;
 	default: break;
 	}
 }
@@ -237,8 +245,11 @@ LIS_INT lis_matrix_shift_matrix(LIS_MATRIX A, LIS_MATRIX B, LIS_SCALAR sigma)
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisi_matrix_check(B, LISI_CHECK_ASSEMBLED));
 	if (A->n != B->n || A->gn != B->gn) return LISI_ERR(LIS_ERR_ILL_ARG, "matrix A (n = %D) and matrix B (n = %D) differ in size\n", A->n, B->n);
-	if (!lisi_format_served(A->matrix_type) || !lisi_format_served(B->matrix_type))
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", lisi_format_served(A->matrix_type) ? B->matrix_type : A->matrix_type);
+	if (lisi_format_coo_dns(A->matrix_type) || lisi_format_coo_dns(B->matrix_type))      /* (a COO copy looks like CSR in HBM: the gate reads the matrix, not the copy) */
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_matrix_shift_matrix: %s storage is not shifted by a matrix -- convert to one of CSR, CSC, DIA, ELL, JAD, BSR first (A and B are untouched)\n",
+		                (lisi_format_coo_dns(A->matrix_type) ? A->matrix_type : B->matrix_type) == LIS_MATRIX_COO ? "COO" : "DNS");
+	if (!lisi_format_swept(A->matrix_type) || !lisi_format_swept(B->matrix_type))
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", lisi_format_swept(A->matrix_type) ? B->matrix_type : A->matrix_type);
 	if (lisg.nprocs > 1 || A->nprocs > 1 || A->np != A->n || B->np != B->n)
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_matrix_shift_matrix is served on one rank (this job has %D)\n", (LIS_INT)lisg.nprocs);
 	if (A->is_splited || B->is_splited) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_matrix_shift_matrix: a split matrix (lis_matrix_split, -p ssor | ilu | is ...) is not shifted by a matrix\n");

@@ -197,6 +197,8 @@ LIS_INT lisi_ssor_create(LIS_SOLVER solver, LIS_PRECON precon)
 	LIS_INT bnr, bnc;
 	const LIS_INT result = lisi_storage_result(A, storage, solver->options[LIS_OPTIONS_STORAGE_BLOCK], &bnr, &bnc);   /* what A is after lis_matrix_convert_self */
 	/* refusals first: A is left as it was */
+	if (result == LIS_MATRIX_COO)
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ssor is served for CSR and BSR storage only; on COO storage the reference itself fails (lis_matrix_solve: not implemented, a NaN residual) (A is untouched)\n");
 	if (result != LIS_MATRIX_CSR && result != LIS_MATRIX_BSR)
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ssor is served for CSR and BSR storage only (A is untouched)\n");
 	if (lisg.nprocs > 1) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p ssor is served on one rank only (A is untouched)\n");

@@ -8,9 +8,19 @@
  *             column: the reference's serial CSC loop (src/matvec/lis_matvec_csc.c:128-144) adds the
  *             terms of output row i in exactly that order
  *   ELL/DIA   column-major [maxnzr|nnd][n];  JAD  perm/ptr/index/value (one chunk);  BSR  bptr/bindex/value
+ *   COO       kept as CSR rows that list a row's triplets in ascending k -- the order in which the reference's serial walk
+ *             (src/matvec/lis_matvec_coo.c:75-87) adds them to y[row[k]] --, built IN HBM from the uploaded row / col / value (kernels/coo.hip):
+ *             row[] non-decreasing: ptr[] from the row starts, col[] and value[] serve as index[] and value[] where they lie (d->row keeps the
+ *             uploaded row[]); otherwise a stable grouping by row, after which the uploaded triplets are released
+ *   DNS       value[np][n] column-major as the host holds it; the native kernel pair of kernels/dns.hip
  */
 #include <stdio.h>
 #include "lis_internal.h"
+
+/* what only the COO and DNS arms call is referenced weakly: tests/c/upload_cases.c links this file against stubs of the calls the six older formats make, and the
+ * library always holds the real ones */
+extern LIS_INT lisi_coo_dns_one_rank(LIS_INT type) __attribute__((weak));
+extern int liship_coo_rows_f64(int n, int nnz, const int *row, const int *col, const double *value, int *ptr, int **index, double **out_value, void *stream) __attribute__((weak));
 
 /* a fresh HBM array holding src[0 .. count), queued on the library's stream; the array is the caller's from the allocation on, whatever the copy answers */
 LIS_INT lisd_upload_i(int **dst, const int *src, size_t count)
@@ -468,6 +478,8 @@ static int host_arrays(LIS_MATRIX A, const void *arr[6], size_t bytes[6])
 	case LIS_MATRIX_DIA: ARR(A->index, 4 * (size_t)A->nnd); ARR(A->value, 8 * n * (size_t)A->nnd); break;
 	case LIS_MATRIX_JAD: ARR(A->row, 4 * n); ARR(A->ptr, 4 * ((size_t)A->maxnzr + 1)); ARR(A->index, 4 * (size_t)A->nnz); ARR(A->value, 8 * (size_t)A->nnz); break;
 	case LIS_MATRIX_BSR: ARR(A->bptr, 4 * ((size_t)A->nr + 1)); ARR(A->bindex, 4 * (size_t)A->bnnz); ARR(A->value, 8 * (size_t)A->bnnz * (size_t)A->bnr * (size_t)A->bnc); break;
+	case LIS_MATRIX_COO: ARR(A->row, 4 * (size_t)A->nnz); ARR(A->col, 4 * (size_t)A->nnz); ARR(A->value, 8 * (size_t)A->nnz); break;
+	case LIS_MATRIX_DNS: ARR(A->value, 8 * n * (size_t)A->np); break;
 	default: break;
 	}
 #undef ARR
@@ -481,6 +493,29 @@ static unsigned long long host_arrays_hash(LIS_MATRIX A)
 	unsigned long long h = 0;
 	for (int i = 0; i < k; i++) h = (h * 0x9E3779B97F4A7C15ull) ^ hash_words(arr[i], bytes[i]);
 	return h;
+}
+
+/* COO: the triplets go up as they are and the row form is made of them in HBM (liship_coo_rows_f64): no host pass over the entries.  In place (rows grouped
+ * already): d->index / d->value ARE the uploaded col / value, d->row keeps the uploaded row[] until the copy goes, and the transposed copy is the transposition of
+ * these rows (d->coo_in_order, lis_matvech.c); grouped: the uploaded triplets are released, d->row stays NULL, the transposed copy groups the triplets by column */
+static LIS_INT upload_coo_as_csr(LIS_MATRIX A, lisd_mat *d)
+{
+	const int n = A->n, nnz = A->nnz;
+	int *drow = NULL, *dcol = NULL, *gidx = NULL; double *dval = NULL, *gval = NULL;
+	LIS_INT err = lisd_upload_i(&drow, A->row, (size_t)nnz);
+	if (!err) err = lisd_upload_i(&dcol, A->col, (size_t)nnz);
+	if (!err) err = lisd_upload_d(&dval, A->value, (size_t)nnz);
+	if (!err) { const int rc = lisd_malloc((void **)&d->ptr, sizeof(int) * ((size_t)n + 5)); if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
+	if (!err) {
+		const int rc = liship_coo_rows_f64(n, nnz, drow, dcol, dval, d->ptr, &gidx, &gval, lisg.stream);
+		if (rc == LISHIP_ERR_ARG) err = LISI_ERR(LIS_ERR_ILL_ARG, "COO matrix: a row index lies outside [0, %D)\n", (LIS_INT)n);
+		else if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
+	}
+	if (err) { (void)liship_free(drow); (void)liship_free(dcol); (void)liship_free(dval); return err; }
+	d->index = gidx; d->value = gval;
+	if (gidx == dcol) { d->row = drow; d->coo_in_order = 1; }
+	else { (void)liship_free(drow); (void)liship_free(dcol); (void)liship_free(dval); }
+	return LIS_SUCCESS;
 }
 
 static LIS_INT mat_upload(LIS_MATRIX A);
@@ -559,6 +594,17 @@ static LIS_INT mat_upload(LIS_MATRIX A)
 			LISCHK(lisd_try_bsr_row_form(A->n, A->np, A->bnr, A->bnc, A->is_splited, d, d->bptr, d->bindex, native, A->bnnz, lisd_few_distinct_values(A->value, (size_t)A->bnnz * (size_t)A->bnr * (size_t)A->bnc), &taken));
 			if (taken) { (void)liship_free(native); (void)liship_free(d->bptr); (void)liship_free(d->bindex); d->bptr = NULL; d->bindex = NULL; }
 		}
+		break;
+	case LIS_MATRIX_COO:
+		if (!lisi_coo_dns_one_rank || !liship_coo_rows_f64) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "COO storage: this build holds no row-form builder\n");
+		LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
+		LISCHK(upload_coo_as_csr(A, d));
+		d->type = LIS_MATRIX_CSR;
+		LISCHK(lisd_csr_plan(&d->plan, A->n, d->ptr, d->index, d->value));
+		break;
+	case LIS_MATRIX_DNS:
+		if (lisi_coo_dns_one_rank) LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
+		LISCHK(lisd_upload_d(&d->value, A->value, n * (size_t)A->np));
 		break;
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);

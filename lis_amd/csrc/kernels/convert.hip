@@ -367,3 +367,43 @@ extern "C" int liship_csr_to_jad(int n, const int *perm, const int *jptr, const 
     if (n > 0) { csr_to_jad<<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, perm, jptr, ptr, idx, val, jidx, jval); LAUNCH_CHECK(); }
     return 0;
 }
+
+// ---- COO and DNS from CSR rows (src/matrix/lis_matrix_coo.c:753-763, lis_matrix_dns.c:784-797).  One lane per row: a row's entries are few and the
+// duplicate (i, j) entries of a row must reach the dense array in stored order (the last one wins), which one lane's program order gives.
+namespace {
+__global__ __launch_bounds__(BLOCK)
+void csr_to_coo_rows(int n, const int *__restrict__ ptr, int *__restrict__ row)
+{
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    for (int k = ptr[i]; k < ptr[i + 1]; k++) row[k] = (int)i;
+}
+__global__ __launch_bounds__(BLOCK)
+void csr_to_dns(int n, int np, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ val, double *__restrict__ dns)
+{
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    for (int k = ptr[i]; k < ptr[i + 1]; k++) {
+        const int j = idx[k];
+        if (j >= 0 && j < np) dns[(size_t)j * (size_t)n + (size_t)i] = val[k];
+    }
+}
+} // namespace
+
+// row[k] = the row of entry k; col and value of the triplets are index and value themselves (the caller copies them)
+extern "C" int liship_csr_to_coo(int n, const int *ptr, int *row, void *stream)
+{
+    if (n < 0) return LISHIP_ERR_ARG;
+    if (n > 0) { csr_to_coo_rows<<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, ptr, row); LAUNCH_CHECK(); }
+    return 0;
+}
+// dns: n * np doubles, column-major, zero-filled here first
+extern "C" int liship_csr_to_dns_f64(int n, int np, const int *ptr, const int *idx, const double *val, double *dns, void *stream)
+{
+    if (n < 0 || np < 0) return LISHIP_ERR_ARG;
+    if (n == 0 || np == 0) return 0;
+    HIP_TRY(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n * (size_t)np, as_stream(stream)));
+    csr_to_dns<<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, np, ptr, idx, val, dns);
+    LAUNCH_CHECK();
+    return 0;
+}

@@ -209,6 +209,133 @@ extern "C" int liship_csr_transpose_f64(int nrows, int ncols, int nnz, const int
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// ---- the same method keyed by an arbitrary key[k]: a STABLE grouping of entries 0 .. nnz-1 by key --------------------------
+// Segment c of the result lists the entries k with key[k] == c in ascending k: tidx = src[k], tval = val[k].  With key = row, src = col
+// it makes CSR rows out of triplets in stored order (the sums of lis_matvec_coo, src/matvec/lis_matvec_coo.c:75-87); with key = col,
+// src = row the transposed operator of lis_matvech_coo (:116-128).  Count, scan, scatter positions, order each segment's positions
+// ascending, gather -- the kernels above, with one lane per ENTRY where the transpose has one per row, and src[k] travelling with the
+// position as the row does there (order_and_fill / order_mid never look at ptr when the rows came along).
+namespace {
+// bit 0: key[] is not non-decreasing; bit 1: a key lies outside [0, nkeys)
+__global__ __launch_bounds__(BLOCK)
+void check_keys(int nnz, int nkeys, const int *__restrict__ key, int *__restrict__ flags)
+{
+    const long long k = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= nnz) return;
+    const int c = key[k];
+    int f = (c < 0 || c >= nkeys) ? 2 : 0;
+    if (k > 0 && key[k - 1] > c) f |= 1;
+    if (f) atomicOr(flags, f);
+}
+
+__global__ __launch_bounds__(BLOCK)
+void count_keys(int nnz, int nkeys, const int *__restrict__ key, int *__restrict__ count)
+{
+    const long long k = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= nnz) return;
+    const int c = key[k];
+    if (c >= 0 && c < nkeys) atomicAdd(&count[c], 1);      // (a key outside the range is the caller's error: it is left out, never written through)
+}
+
+__global__ __launch_bounds__(BLOCK)
+void scatter_by_key(int nnz, int nkeys, const int *__restrict__ key, const int *__restrict__ src, const int *__restrict__ tptr,
+                    int *__restrict__ fill, int *__restrict__ pos, int *__restrict__ carried)
+{
+    const long long k = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= nnz) return;
+    const int c = key[k];
+    if (c < 0 || c >= nkeys) return;
+    const int at = tptr[c] + atomicAdd(&fill[c], 1);
+    pos[at] = (int)k;
+    carried[at] = src[k];
+}
+
+// ptr[r] = first k with key[k] >= r, for a non-decreasing key[]: the row starts of triplets that are grouped already
+__global__ __launch_bounds__(BLOCK)
+void starts_of_sorted_keys(int nkeys, int nnz, const int *__restrict__ key, int *__restrict__ ptr)
+{
+    const long long r = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (r > nkeys) return;
+    int lo = 0, hi = nnz;                            // first k in [0, nnz] with key[k] >= r
+    while (lo < hi) { const int m2 = lo + ((hi - lo) >> 1); if (key[m2] < (int)r) lo = m2 + 1; else hi = m2; }
+    ptr[r] = lo;
+}
+
+int scan_counts(int m, const int *count, int *out, hipStream_t st)      // out[0 .. m] = exclusive scan of count[0 .. m)
+{
+    const int ntiles = (m + TILE - 1) / TILE;
+    if (ntiles == 0) { HIP_TRY(hipMemsetAsync(out, 0, sizeof(int), st)); return 0; }
+    long long *sums = nullptr;
+    HIP_TRY(hipMalloc(&sums, sizeof(long long) * (size_t)ntiles));
+    tile_sums<<<ntiles, BLOCK, 0, st>>>(m, count, sums);
+    scan_tile_sums<<<1, 1024, 0, st>>>(ntiles, sums);
+    scan_tiles<<<ntiles, BLOCK, 0, st>>>(m, count, sums, out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(sums);
+    return (int)e;
+}
+} // namespace
+
+// flags_host: bit 0 key[] is not non-decreasing, bit 1 a key outside [0, nkeys) (one synchronize)
+extern "C" int liship_key_facts(int nkeys, int nnz, const int *key, int *flags_host, void *stream)
+{
+    if (nkeys < 0 || nnz < 0 || !flags_host) return LISHIP_ERR_ARG;
+    *flags_host = 0;
+    if (nnz == 0) return 0;
+    hipStream_t st = as_stream(stream);
+    int *flags = nullptr;
+    HIP_TRY(hipMalloc(&flags, sizeof(int)));
+    hipError_t e = hipMemsetAsync(flags, 0, sizeof(int), st);
+    if (e == hipSuccess) { check_keys<<<(unsigned)(((long long)nnz + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>(nnz, nkeys, key, flags); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(flags_host, flags, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(flags);
+    return (int)e;
+}
+
+// ptr[0 .. nkeys] of a non-decreasing key[0 .. nnz)
+extern "C" int liship_sorted_key_starts(int nkeys, int nnz, const int *key, int *ptr, void *stream)
+{
+    if (nkeys < 0 || nnz < 0) return LISHIP_ERR_ARG;
+    starts_of_sorted_keys<<<(unsigned)(((long long)nkeys + 1 + BLOCK - 1) / BLOCK), BLOCK, 0, as_stream(stream)>>>(nkeys, nnz, key, ptr);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// tptr: nkeys + 1 ints, tidx / tval: nnz entries.  Every key must lie in [0, nkeys) (liship_key_facts).  Scratch of nkeys + 2 nnz ints is the routine's own.
+extern "C" int liship_group_by_key_f64(int nkeys, int nnz, const int *key, const int *src, const double *val,
+                                       int *tptr, int *tidx, double *tval, void *stream)
+{
+    if (nkeys < 0 || nnz < 0) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    if (nnz == 0) { HIP_TRY(hipMemsetAsync(tptr, 0, sizeof(int) * ((size_t)nkeys + 1), st)); return 0; }
+    if (nkeys == 0) return LISHIP_ERR_ARG;
+    int *work = nullptr;
+    HIP_TRY(hipMalloc(&work, sizeof(int) * ((size_t)nkeys + 2 * (size_t)nnz)));
+    int *count = work, *pos = work + nkeys, *carried = pos + nnz;
+    const unsigned kblocks = (unsigned)(((long long)nnz + BLOCK - 1) / BLOCK), cblocks = (unsigned)((nkeys + BLOCK - 1) / BLOCK);
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(int) * (size_t)nkeys, st);
+    if (e == hipSuccess) { count_keys<<<kblocks, BLOCK, 0, st>>>(nnz, nkeys, key, count); e = hipGetLastError(); }
+    if (e == hipSuccess) e = (hipError_t)scan_counts(nkeys, count, tptr, st);
+    if (e == hipSuccess) e = hipMemsetAsync(count, 0, sizeof(int) * (size_t)nkeys, st);
+    if (e == hipSuccess) { scatter_by_key<<<kblocks, BLOCK, 0, st>>>(nnz, nkeys, key, src, tptr, count, pos, carried); e = hipGetLastError(); }
+    const bool mid = (long long)nnz > 8ll * nkeys;       // (short segments on average: none worth a wavefront, as for the transpose)
+    if (e == hipSuccess) { order_and_fill<<<cblocks, BLOCK, 0, st>>>(nkeys, 0, nullptr, val, tptr, pos, carried, tidx, tval, mid ? 1 : 0); e = hipGetLastError(); }
+    if (e == hipSuccess && mid) { order_mid<<<(nkeys + BLOCK / WAVE - 1) / (BLOCK / WAVE), BLOCK, 0, st>>>(nkeys, val, tptr, pos, carried, tidx, tval); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(work);
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+// the borders of the ordering kernels: {longest segment sorted by insertion, first and last length a wavefront ranks in LDS when nnz > 8 nkeys} -- what the tests aim at
+extern "C" int liship_group_by_key_borders(int out[3])
+{
+    if (!out) return LISHIP_ERR_ARG;
+    out[0] = 32; out[1] = MID_FROM; out[2] = MID_TO;
+    return 0;
+}
+
 // ---- A^T x in the reference's order for OMP_NUM_THREADS = T > 1 (parity mode, liship_set_reference_reductions) ----------------
 // The OpenMP build of lis_matvech_csr gives thread k the source rows LIS_GET_ISIE(k, T, n), lets it scatter into a buffer of its own
 // from 0.0, and then forms y[c] = ((0.0 + w[0][c]) + w[1][c]) + ... (src/matvec/lis_matvec_csr.c:207-236).  On the transposed rows
