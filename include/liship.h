@@ -412,7 +412,7 @@ int  liship_mgs_step_f64(int n, const double *hprev, const double *vprev, double
  * workgroup reads its tile of every vector once (kernels/eigen.hip).  vecs and pairs are HOST arrays (of device pointers / of indices into vecs); a pair may
  * name one vector twice, and two results may name the same pair.  Every sum is formed EXACTLY as liship_dot_f64 forms that pair alone -- the tree above, the
  * 16 B or the 8 B lane mapping chosen from that pair's own two arrays, or the T chunks of liship_set_reference_reductions(T) -- so a loop may take its
- * Gram block here or as K separate dots and find the same bits (the eigensolvers' CG and CR, host/lis_esolver.c; tests/test_multidot_gpu.py).  When some vector
+ * Gram block here or as K separate dots and find the same bits (the eigensolvers' CG and CR, host/lis_esolver_single.c; tests/test_multidot_gpu.py).  When some vector
  * is only 8 B aligned, the tiles are swept a second time for the pairs that involve one (the second sweep reads from cache).  In the reference-order mode
  * the K sums are K passes (one lane adds a chunk there: nothing to share).  Announce no liship_krylov_chain step before this call: the one pass
  * leaves it pending, where liship_dot_f64 would run it. */

@@ -389,6 +389,7 @@ LIS_INT lisi_matrix_deep_copy(LIS_MATRIX Ain, LIS_MATRIX Aout);
 /* args (lis_initialize / lis_solver_set_option share the tokenizer) */
 int lisi_tokenize(const char *text, char ***tokens);
 void lisi_tokens_free(char **tokens, int n);
+LIS_INT lisi_each_option(char **tok, int n, LIS_INT (*set_one)(const char *name, const char *val, void *object), void *object);
 extern int lisi_cmd_argc; extern char **lisi_cmd_argv;
 
 #endif

@@ -1,6 +1,6 @@
 /*
  * lis_shift.c -- lis_matrix_shift_diagonal(A, sigma): A <- A - sigma I (reference src/matrix/lis_matrix_ops.c:781-829 and the
- * per-format routines it dispatches to).  The one matrix operation every eigensolver calls (lis_esolver.c): once around a whole solve
+ * per-format routines it dispatches to).  The one matrix operation every eigensolver calls (eshift, lis_eloop.h): once around a whole solve
  * for -shift, twice per iteration for the Rayleigh quotient iteration.  Its generalized form, lis_matrix_shift_matrix(A, B, sigma):
  * A <- A - sigma B (lis_matrix_ops.c:833-856), stands in the second half of this file.
  *

@@ -14,7 +14,6 @@
  * b and x cross PCIe once on entry, x once on exit.  Scalars (alpha, beta, rho, Givens rotations, the
  * Hessenberg matrix) stay on the host exactly as in the reference.
  */
-#include <ctype.h>
 #include <stdio.h>
 #include "lis_internal.h"
 
@@ -150,8 +149,9 @@ static LIS_INT pick(const char *val, const char **keys, int nkeys, int base, LIS
 	return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter %s is not correct\n", what);
 }
 
-static LIS_INT set_one(const char *name, const char *val, LIS_SOLVER s)
+static LIS_INT set_one(const char *name, const char *val, void *object)
 {
+	LIS_SOLVER s = (LIS_SOLVER)object;
 	static const struct { const char *name; int slot; } table[] = {   /* ref lis_solver.c:175-197 */
 		{"-maxiter", LIS_OPTIONS_MAXITER}, {"-tol", LIS_PARAMS_RESID}, {"-print", LIS_OPTIONS_OUTPUT}, {"-scale", LIS_OPTIONS_SCALE},
 		{"-ssor_omega", LIS_PARAMS_SSOR_OMEGA}, {"-ilu_fill", LIS_OPTIONS_FILL}, {"-ilu_relax", LIS_PARAMS_RELAX},
@@ -194,18 +194,9 @@ static LIS_INT set_one(const char *name, const char *val, LIS_SOLVER s)
 
 static LIS_INT set_from_tokens(char **tok, int n, LIS_SOLVER s)
 {
-	for (int i = 0; i + 1 < n; i++) {
-		if (tok[i][0] != '-' || (tok[i][1] >= '0' && tok[i][1] <= '9')) continue;
-		char name[64], val[256];
-		size_t k;
-		for (k = 0; tok[i][k] && k + 1 < sizeof(name); k++) name[k] = (char)tolower((unsigned char)tok[i][k]);
-		name[k] = 0;
-		for (k = 0; tok[i + 1][k] && k + 1 < sizeof(val); k++) val[k] = (char)tolower((unsigned char)tok[i + 1][k]);
-		val[k] = 0;
-		LIS_INT err = set_one(name, val, s);
-		if (err) { s->retcode = err; return err; }
-	}
-	return LIS_SUCCESS;
+	const LIS_INT err = lisi_each_option(tok, n, set_one, s);
+	if (err) s->retcode = err;
+	return err;
 }
 
 LIS_INT lis_solver_set_option(char *text, LIS_SOLVER solver)

@@ -5,6 +5,7 @@
  * lis_memory.c, lis_error.c:161-191, lis_time.c); none of it is on the hot path.
  */
 #define _GNU_SOURCE
+#include <ctype.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <sys/time.h>
@@ -215,6 +216,24 @@ void lisi_tokens_free(char **tokens, int n)
 {
 	for (int i = 0; i < n; i++) free(tokens[i]);
 	free(tokens);
+}
+
+/* the pairs lis_text2args / lis_initialize keep (src/system/lis_args.c): "-name value", both lower-cased, handed to set_one one by one; a "-<digit>"
+ * is a value, not a name.  The first error ends the walk and is returned: what else happens then is the caller's (lis_solver.c, lis_esolver.c) */
+LIS_INT lisi_each_option(char **tok, int n, LIS_INT (*set_one)(const char *name, const char *val, void *object), void *object)
+{
+	for (int i = 0; i + 1 < n; i++) {
+		if (tok[i][0] != '-' || (tok[i][1] >= '0' && tok[i][1] <= '9')) continue;
+		char name[64], val[256];
+		size_t k;
+		for (k = 0; tok[i][k] && k + 1 < sizeof(name); k++) name[k] = (char)tolower((unsigned char)tok[i][k]);
+		name[k] = 0;
+		for (k = 0; tok[i + 1][k] && k + 1 < sizeof(val); k++) val[k] = (char)tolower((unsigned char)tok[i + 1][k]);
+		val[k] = 0;
+		const LIS_INT err = set_one(name, val, object);
+		if (err) return err;
+	}
+	return LIS_SUCCESS;
 }
 
 /* ------------------------------------------------------------------ init / finalize */

@@ -1,4 +1,4 @@
-"""Whole eigensolves on the GPU (host/lis_esolver.c) against the reference's bits.
+"""Whole eigensolves on the GPU (host/lis_esolver.c, host/lis_esolver_single.c) against the reference's bits.
 
 Reference-order mode: with lis_amd_set_reference_reductions(T) an esolve must reproduce oracle/_ref at T threads IN EVERY BIT -- iteration count, status,
 every entry of the residual history, the eigenvalue, the final residual, the eigenvector.  Fixtures: tests/golden/esolve_bits.{json,npz}, written by

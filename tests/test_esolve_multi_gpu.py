@@ -1,4 +1,4 @@
-"""Eigensolves of several pairs on the GPU (-e si | li | ai, host/lis_esolver.c) against the reference's bits.
+"""Eigensolves of several pairs on the GPU (-e si | li | ai, host/lis_esolver_multi.c) against the reference's bits.
 
 Reference-order mode: with lis_amd_set_reference_reductions(T) a solve must reproduce oracle/_ref at T threads IN EVERY BIT of every mode -- eigenvalue,
 residual and count per mode, the status, every entry of the residual history, x and every eigenvector -- read from the struct and through the getters.

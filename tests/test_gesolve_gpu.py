@@ -1,4 +1,4 @@
-"""Whole generalized eigensolves on the GPU (host/lis_esolver.c: -e gpi | gii | grqi | gcr through lis_gesolve with a matrix B) against the reference's bits.
+"""Whole generalized eigensolves on the GPU (host/lis_esolver_single.c: -e gpi | gii | grqi | gcr through lis_gesolve with a matrix B) against the reference's bits.
 
 Reference-order mode: with lis_amd_set_reference_reductions(T) a gesolve must reproduce oracle/_ref at T threads IN EVERY BIT -- iteration count, status, the
 eigenvalue, the final residual, every entry of the residual history, the eigenvector, and A's arrays after the solve (the shifts of -e grqi and of -shift

@@ -1,4 +1,4 @@
-"""Several pairs of the generalized problem on the GPU (-e gsi | gli | gai through lis_gesolve, host/lis_esolver.c) against the reference's bits.
+"""Several pairs of the generalized problem on the GPU (-e gsi | gli | gai through lis_gesolve, host/lis_esolver_multi.c) against the reference's bits.
 
 Reference-order mode: with lis_amd_set_reference_reductions(T) a solve must reproduce oracle/_ref at T threads IN EVERY BIT of every mode -- eigenvalue,
 residual and count per mode, the status, every entry of the residual history, x, every eigenvector and A's arrays after the solve (the shift of -shift and the
