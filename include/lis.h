@@ -5,9 +5,9 @@
  * convention and -- for the structs -- the byte layout of anishida/lis 2.1.11 (reference
  * include/lis.h; the line each item mirrors is cited as "ref:NNN").  A program written against the
  * reference header compiles against this one and links against liblis_amd.so instead of liblis.
- * Only the slice on the hot path and the rows next to it are provided (eight storage
- * formats -- CSR, CSC, DIA, ELL, JAD, BSR, COO, DNS --, A x and A^T x, the Krylov solvers, none / Jacobi / SSOR / ILU(k) preconditioning, scaling, Matrix Market / Harwell-Boeing
- * files); anything else is absent, and what exists in the enumerations but is not served (MSR/BSC/VBR
+ * Only the slice on the hot path and the rows next to it are provided (nine storage
+ * formats -- CSR, CSC, DIA, ELL, JAD, BSR, VBR, COO, DNS --, A x and A^T x, the Krylov solvers, none / Jacobi / SSOR / ILU(k) preconditioning, scaling, Matrix Market / Harwell-Boeing
+ * files); anything else is absent, and what exists in the enumerations but is not served (MSR/BSC
  * storage, Gauss-Seidel / SOR, the preconditioners after ILU(k) and SSOR: iluc, ilut, ...) returns LIS_ERR_NOT_IMPLEMENTED at run time
  * exactly where the reference would dispatch to it.
  *
@@ -517,6 +517,7 @@ void lis_matvec_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);   /* src/matv
 void lis_matvec_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);   /* src/matvec/lis_matvec_bsr.c:57 */
 void lis_matvec_coo(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);   /* src/matvec/lis_matvec_coo.c:50 */
 void lis_matvec_dns(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);   /* src/matvec/lis_matvec_dns.c:50 */
+void lis_matvec_vbr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);   /* src/matvec/lis_matvec_vbr.c:52 */
 /* y = A^T x (A^H; real build).  The reference scatters; here A^T is kept as a second CSR whose rows list the
  * contributions in the reference's scatter order, so the result has the reference's bits (1 thread). */
 void lis_matvech_csr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);  /* src/matvec/lis_matvec_csr.c:113 */
@@ -527,6 +528,7 @@ void lis_matvech_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);  /* src/matv
 void lis_matvech_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);  /* src/matvec/lis_matvec_bsr.c:860 */
 void lis_matvech_coo(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);  /* src/matvec/lis_matvec_coo.c:91 */
 void lis_matvech_dns(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);  /* src/matvec/lis_matvec_dns.c:87 (its OpenMP branch: row chunks, lis_amd_set_reference_reductions) */
+void lis_matvech_vbr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]);  /* src/matvec/lis_matvec_vbr.c:148 (its OpenMP branch: chunks of block rows, lis_amd_set_reference_reductions) */
 
 /* ---- vectors, ref:824-859 (src/vector/lis_vector.c, lis_vector_ops.c, lis_vector_opv.c) ---------- */
 LIS_INT lis_vector_create(LIS_Comm comm, LIS_VECTOR *vec);
@@ -627,6 +629,12 @@ LIS_INT lis_matrix_set_coo(LIS_INT nnz, LIS_INT *row, LIS_INT *col, LIS_SCALAR *
 /* DNS: n x np values, column-major (value[j*n + i]); the element count is formed in size_t */
 LIS_INT lis_matrix_malloc_dns(LIS_INT n, LIS_INT np, LIS_SCALAR **value);
 LIS_INT lis_matrix_set_dns(LIS_SCALAR *value, LIS_MATRIX A);
+/* VBR: nr block rows row[0..nr] and nc block columns col[0..nc] of any heights and widths; block row bi holds the blocks bptr[bi] .. bptr[bi+1], block bc lies in
+ * block column bindex[bc] and stores its (row[bi+1]-row[bi]) x (col[bj+1]-col[bj]) values column-major from value[ptr[bc]], zeros included.  One rank only.
+ * lis_matrix_convert of a CSR source into VBR without row[] / col[] from lis_matrix_set_blocksize SORTS THE SOURCE'S ROWS IN PLACE, as the reference does
+ * (src/matrix/lis_matrix_vbr.c:523), and cuts the blocks at every start and end of a run of consecutive columns. */
+LIS_INT lis_matrix_malloc_vbr(LIS_INT n, LIS_INT nnz, LIS_INT nr, LIS_INT nc, LIS_INT bnnz, LIS_INT **row, LIS_INT **col, LIS_INT **ptr, LIS_INT **bptr, LIS_INT **bindex, LIS_SCALAR **value);
+LIS_INT lis_matrix_set_vbr(LIS_INT nnz, LIS_INT nr, LIS_INT nc, LIS_INT bnnz, LIS_INT *row, LIS_INT *col, LIS_INT *ptr, LIS_INT *bptr, LIS_INT *bindex, LIS_SCALAR *value, LIS_MATRIX A);
 
 /* ---- matrix-vector product, ref:920 (src/matvec/lis_matvec.c:55) ------------------------------- */
 LIS_INT lis_matvec(LIS_MATRIX A, LIS_VECTOR x, LIS_VECTOR y);

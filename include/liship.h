@@ -598,6 +598,11 @@ int  liship_spmv_csr_transposed_chunked_f64(int rows, int nsrc, int T, const int
  * stored order.  What lis_matvech_ell's T threads form (src/matvec/lis_matvec_ell.c:182-222: the scatter walks slot after slot); T sweeps over a row. */
 int  liship_spmv_csr_transposed_chunked_unordered_f64(int rows, int nsrc, int T, const int *tptr, const int *tidx, const double *tval,
                                                       const double *x, double *y, void *stream);
+/* ... and for chunks with explicit borders: chunk k owns the source rows borders[k] .. borders[k + 1] (T + 1 ascending ints in HBM, borders[0] = 0), the entries of a
+ * transposed row never step back to an earlier chunk.  lis_matvech_vbr's T threads own chunks of BLOCK ROWS (src/matvec/lis_matvec_vbr.c:284-300):
+ * borders[k] = row[first block row of LIS_GET_ISIE(k, T, nr)]. */
+int  liship_spmv_csr_transposed_bordered_f64(int rows, int T, const int *borders, const int *tptr, const int *tidx, const double *tval,
+                                             const double *x, double *y, void *stream);
 int  liship_csr_transpose_f64(int nrows, int ncols, int nnz, const int *ptr, const int *index, const double *value,
                               int *tptr, int *tindex, double *tvalue, int *work, void *stream);
 /* ---- the same method keyed by an arbitrary key (kernels/transpose.hip): a STABLE grouping of the entries 0 .. nnz-1.  Segment c of the result lists the entries
@@ -623,6 +628,34 @@ int  liship_coo_rows_f64(int n, int nnz, const int *row, const int *col, const d
 int  liship_dns_tile_info(int info[4]);
 int  liship_spmv_dns_f64(int n, int np, const double *value, const double *x, double *y, void *stream);
 int  liship_spmv_dns_t_f64(int n, int np, int T, const double *value, const double *x, double *y, void *stream);
+/* ---- VBR (kernels/vbr.hip): nr block rows row[0 .. nr], nc block columns col[0 .. nc], block row bi = the blocks bptr[bi] .. bptr[bi+1], block bc in block
+ * column bindex[bc], its (row[bi+1]-row[bi]) x (col[bj+1]-col[bj]) values column-major from value[ptr[bc]].
+ *   liship_vbr_check       *flags_host = 0, or the LISHIP_VBR_BAD_* bits of what is wrong: row[] / col[] not strictly ascending from 0 to n / np, bptr[] not
+ *                          ascending from 0 to bnnz, ptr[] not ascending inside [0, nnz], a bindex outside [0, nc), a block whose ptr[bc+1] - ptr[bc] is not its
+ *                          size.  Reads nothing beyond the arrays' lengths whatever they hold; synchronizes the stream.  Arrays that pass cannot send a
+ *                          lane of the two kernels below out of bounds
+ *   liship_vbr_block_rows  brow[i] = the block row of row i, n ints (of a checked row[])
+ *   liship_spmv_vbr_f64    y[i] = the chain from +0.0 over the row's blocks in stored order, a block's columns ascending, of value * x[j], every product
+ *                          rounded before it is added, zeros multiplied too (lis_matvec_vbr); a row without blocks gives +0.0; y by non-temporal stores
+ * One lane per row.  liship_vbr_tile_info: {rows of y per workgroup, columns of a block whose values are loaded ahead of their adds}. */
+#define LISHIP_VBR_BAD_ROW    1
+#define LISHIP_VBR_BAD_COL    2
+#define LISHIP_VBR_BAD_BPTR   4
+#define LISHIP_VBR_BAD_PTR    8
+#define LISHIP_VBR_BAD_BINDEX 16
+#define LISHIP_VBR_BAD_SIZE   32
+int  liship_vbr_tile_info(int info[2]);
+int  liship_vbr_check(int n, int np, int nnz, int nr, int nc, int bnnz, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex,
+                      int *flags_host, void *stream);
+int  liship_vbr_block_rows(int n, int nr, const int *row, int *brow, void *stream);
+int  liship_spmv_vbr_f64(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, const double *value,
+                         const double *x, double *y, void *stream);
+/* value[] of a checked copy edited where it lies, one launch each: A - sigma I on the entries the reference's diagonal search finds (lis_matrix_shift_diagonal_vbr: the
+ * diagonal on uniform blocks, other entries or none on variable ones), and the scalings value*d[i] (symm = 0) and value*d[i]*d[j] in that order (symm = 1), d: n doubles */
+int  liship_vbr_shift_diagonal_f64(int n, int nr, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, double *value, double sigma,
+                                   void *stream);
+int  liship_vbr_scale_f64(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, double *value, const double *d,
+                          int symm, void *stream);
 /* ---- preconditioners applied as products (kernels/sainv.hip): row sums over a packed CSR {ptr, idx, val}, each sum formed from +0.0 in STORED
  * order by one lane whatever the row's length, the epilogue in the same kernel.  The transposed forms (liship_csr_transpose_f64: terms by source
  * row) are summed in T chunks of the nsrc source rows, LIS_GET_ISIE(k, T, nsrc), the chunk sums added in chunk order from +0.0 (T <= 1: one chain).

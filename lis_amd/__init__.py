@@ -221,6 +221,13 @@ _LISHIP = {
     "liship_dns_tile_info": (_ci, [C.POINTER(_ci)]),
     "liship_spmv_dns_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
     "liship_spmv_dns_t_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "liship_spmv_csr_transposed_bordered_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_vbr_tile_info": (_ci, [C.POINTER(_ci)]),
+    "liship_vbr_check": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_vbr_block_rows": (_ci, [_ci, _ci, _vp, _vp, _vp]),
+    "liship_spmv_vbr_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_vbr_shift_diagonal_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cd, _vp]),
+    "liship_vbr_scale_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),
     "liship_csr_to_coo": (_ci, [_ci, _vp, _vp, _vp]),
     "liship_csr_to_dns_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp]),
     "liship_gather_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),

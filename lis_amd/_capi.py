@@ -16,13 +16,13 @@ P_DBL = C.POINTER(C.c_double)
 # constants (lis.h:175-260, 1052-1063 of the reference)
 LIS_MATRIX_CSR, LIS_MATRIX_CSC, LIS_MATRIX_MSR, LIS_MATRIX_DIA, LIS_MATRIX_ELL = 1, 2, 3, 4, 5
 LIS_MATRIX_JAD, LIS_MATRIX_BSR = 6, 7
-LIS_MATRIX_COO, LIS_MATRIX_DNS = 10, 11
+LIS_MATRIX_VBR, LIS_MATRIX_COO, LIS_MATRIX_DNS = 9, 10, 11
 LIS_INS_VALUE, LIS_ADD_VALUE = 0, 1
 LIS_SUCCESS, LIS_ERR_ILL_ARG, LIS_BREAKDOWN, LIS_ERR_OUT_OF_MEMORY = 0, 1, 2, 3
 LIS_MAXITER, LIS_ERR_NOT_IMPLEMENTED = 4, 5
 LIS_COMM_WORLD = 1
 LIS_MATRIX_LOWER, LIS_MATRIX_UPPER, LIS_MATRIX_SSOR = 0, 1, 2
-FORMAT_ID = {"csr": 1, "csc": 2, "dia": 4, "ell": 5, "jad": 6, "bsr": 7, "coo": 10, "dns": 11}
+FORMAT_ID = {"csr": 1, "csc": 2, "dia": 4, "ell": 5, "jad": 6, "bsr": 7, "vbr": 9, "coo": 10, "dns": 11}
 
 
 class _Header(C.Structure):
@@ -202,6 +202,8 @@ _PROTOS = {
     "lis_matrix_set_coo": (LIS_INT, [LIS_INT, P_INT, P_INT, P_DBL, PM]),
     "lis_matrix_malloc_dns": (LIS_INT, [LIS_INT, LIS_INT, C.POINTER(P_DBL)]),
     "lis_matrix_set_dns": (LIS_INT, [P_DBL, PM]),
+    "lis_matrix_malloc_vbr": (LIS_INT, [LIS_INT] * 5 + [C.POINTER(P_INT)] * 5 + [C.POINTER(P_DBL)]),
+    "lis_matrix_set_vbr": (LIS_INT, [LIS_INT] * 4 + [P_INT] * 5 + [P_DBL, PM]),
     "lis_matrix_unset": (LIS_INT, [PM]),
     # matvec (lis.h:920)
     "lis_matvec": (LIS_INT, [PM, PV, PV]),

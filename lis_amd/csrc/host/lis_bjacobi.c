@@ -122,7 +122,7 @@ LIS_INT lisi_bjacobi_create(LIS_SOLVER solver, LIS_PRECON precon)
 	if (solver->options[LIS_OPTIONS_SCALE] != LIS_SCALE_NONE) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi together with -scale is not served (A is untouched)\n");
 	if (solver->options[LIS_OPTIONS_ADDS]) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi with -adds true is not served (A is untouched)\n");
 	if (result == LIS_MATRIX_VBR) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on VBR storage is not served (A is untouched)\n");
-	if (lisi_format_coo_dns(result)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on %s storage is not served: such a matrix is never split (A is untouched)\n", result == LIS_MATRIX_COO ? "COO" : "DNS");
+	if (lisi_format_one_rank(result)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on %s storage is not served: such a matrix is never split (A is untouched)\n", lisi_format_name(result));
 	if (result == LIS_MATRIX_BSR && bnr != bnc)
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "-p bjacobi on %D x %D blocks is not served: a BSR matrix is split for square blocks only (A is untouched)\n", bnr, bnc);
 	if (result == LIS_MATRIX_BSR && MDEV(A)->device_only)

@@ -1,11 +1,11 @@
 /*
- * lis_convert.c -- lis_matrix_convert / lis_matrix_copy: the storage layouts of the eight served formats.
+ * lis_convert.c -- lis_matrix_convert / lis_matrix_copy: the storage layouts of the nine served formats.
  *
  * One-off host work that DEFINES the data layout each SpMV kernel streams, and with it the summation
  * order of every row.  Layouts are the reference's at one OpenMP thread (its DIA and JAD layouts are
  * blocked by the producer's thread count): csr2ell src/matrix/lis_matrix_ell.c:958-1070,
  * csr2dia lis_matrix_dia.c:1191-1304, csr2jad lis_matrix_jad.c:1591-1770, csr2bsr lis_matrix_bsr.c:351-552,
- * csr2csc lis_matrix_csc.c:904-1087, csr2coo / coo2csr lis_matrix_coo.c:737-851, csr2dns / dns2csr lis_matrix_dns.c:744-915; dispatcher lis_matrix_ops.c:128-322.
+ * csr2csc lis_matrix_csc.c:904-1087, csr2coo / coo2csr lis_matrix_coo.c:737-851, csr2dns / dns2csr lis_matrix_dns.c:744-915, csr2vbr / vbr2csr lis_matrix_vbr.c:262-872; dispatcher lis_matrix_ops.c:128-322.
  */
 #include "lis_internal.h"
 #ifdef _OPENMP
@@ -373,9 +373,139 @@ void lisi_sort_iid(LIS_INT lo, LIS_INT hi, LIS_INT *i1, LIS_INT *i2, LIS_SCALAR 
 	}
 }
 
+/* ascending sort of i1[lo .. hi] carrying d1[]: the reference's lis_sort_id restated (src/system/lis_sort.c:90-118, the scheme of lisi_sort_iid).  Unstable: where a
+ * row stores a column twice, which of the two values comes last -- and so which one a VBR block keeps -- is whatever this exact scheme leaves */
+void lisi_sort_id(LIS_INT lo, LIS_INT hi, LIS_INT *i1, LIS_SCALAR *d1)
+{
+	while (lo < hi) {
+		const LIS_INT mid = (lo + hi) / 2, pv = i1[mid];
+		LIS_INT t; LIS_SCALAR u;
+		t = i1[mid]; i1[mid] = i1[hi]; i1[hi] = t;
+		u = d1[mid]; d1[mid] = d1[hi]; d1[hi] = u;
+		LIS_INT a = lo, b = hi;
+		while (a <= b) {
+			while (i1[a] < pv) a++;
+			while (i1[b] > pv) b--;
+			if (a <= b) {
+				t = i1[a]; i1[a] = i1[b]; i1[b] = t;
+				u = d1[a]; d1[a] = d1[b]; d1[b] = u;
+				a++; b--;
+			}
+		}
+		lisi_sort_id(lo, b, i1, d1);
+		lo = a;
+	}
+}
+
+/* CSR -> VBR (ref lis_matrix_vbr.c:501-742).  Block rows and columns: the arrays lis_matrix_set_blocksize left on the TARGET, or -- without them -- found here:
+ * the SOURCE's rows are sorted in place (lis_matrix_sort_csr, :523; its HBM copy goes when that moves anything), and every start and every end of a run of
+ * consecutive columns in any row cuts rows and columns alike (lis_matrix_get_vbr_rowcol, :262-334).  The blocks of a block row come in order of FIRST APPEARANCE
+ * while its rows are walked in order, are column-major bnr x bnc, zero-filled first; of a column stored twice the later value stays */
+static LIS_INT csr2vbr(LIS_MATRIX A, LIS_MATRIX B)
+{
+	const LIS_INT n = A->n, np = A->np;
+	LIS_INT err = 0, nr = B->conv_bnr, nc = B->conv_bnc;
+	LIS_INT *row = NULL, *col = NULL, *ptr = NULL, *bptr = NULL, *bindex = NULL, *of_col = NULL, *seen = NULL, *touched = NULL, *cut = NULL;
+	LIS_SCALAR *value = NULL;
+	if (B->conv_row && B->conv_col) {
+		/* what the arrays must be for the walk below to stay inside its arrays (the reference reads them unchecked) */
+		if (B->conv_row[0] != 0 || B->conv_row[nr] != n || B->conv_col[0] != 0 || B->conv_col[nc] != np)
+			return LISI_ERR(LIS_ERR_ILL_ARG, "lis_matrix_set_blocksize: row[] must run from 0 to n = %D in %D block rows, col[] from 0 to %D in %D block columns\n", n, nr, np, nc);
+		for (LIS_INT i = 0; i < nr; i++) if (B->conv_row[i + 1] <= B->conv_row[i]) return LISI_ERR(LIS_ERR_ILL_ARG, "lis_matrix_set_blocksize: row[] does not ascend strictly at %D\n", i);
+		for (LIS_INT i = 0; i < nc; i++) if (B->conv_col[i + 1] <= B->conv_col[i]) return LISI_ERR(LIS_ERR_ILL_ARG, "lis_matrix_set_blocksize: col[] does not ascend strictly at %D\n", i);
+		NEW(row, LIS_INT, nr + 1); NEW(col, LIS_INT, nc + 1);
+		memcpy(row, B->conv_row, sizeof(LIS_INT) * ((size_t)nr + 1));
+		memcpy(col, B->conv_col, sizeof(LIS_INT) * ((size_t)nc + 1));
+	} else {
+		if (!A->is_sorted) {
+			int moved = 0;
+			for (LIS_INT i = 0; i < n; i++) {
+				int ascending = 1;
+				for (LIS_INT k = A->ptr[i] + 1; k < A->ptr[i + 1]; k++) ascending &= A->index[k] > A->index[k - 1];
+				if (!ascending) { lisi_sort_id(A->ptr[i], A->ptr[i + 1] - 1, A->index, A->value); moved = 1; }      /* (a strictly ascending row is left as it is by any sort) */
+			}
+			A->is_sorted = LIS_TRUE;
+			if (moved && MDEV(A)->ready) lisd_mat_free(A);            /* its HBM copy had the old order */
+		}
+		NEW(cut, LIS_INT, n + 1);
+		memset(cut, 0, sizeof(LIS_INT) * ((size_t)n + 1));
+		for (LIS_INT i = 0; i < n; i++)
+			if (A->ptr[i] < A->ptr[i + 1]) {
+				LIS_INT jj = A->index[A->ptr[i]];
+				if (jj < 0 || jj >= n) { err = LISI_ERR(LIS_ERR_ILL_ARG, "CSR matrix: column %D of row %D lies outside [0, %D)\n", jj, i, n); goto fail; }
+				cut[jj] = 1;
+				for (LIS_INT j = A->ptr[i] + 1; j < A->ptr[i + 1]; j++) {
+					const LIS_INT kk = A->index[j - 1];
+					jj = A->index[j];
+					if (jj < 0 || jj >= n) { err = LISI_ERR(LIS_ERR_ILL_ARG, "CSR matrix: column %D of row %D lies outside [0, %D)\n", jj, i, n); goto fail; }
+					if (kk != jj - 1) { cut[jj] = 1; cut[kk + 1] = 1; }
+				}
+				cut[jj + 1] = 1;
+			}
+		LIS_INT k = 0;
+		cut[0] = 0;
+		for (LIS_INT i = 1; i < n + 1; i++) if (cut[i] != 0) { k++; cut[k] = i; }
+		/* (a matrix whose last column is never stored ends its blocks before n: the reference then leaves the rows behind the last cut out of every block row;
+		 * here the last block row and column reach n and np, so that every row of A lies in a block row) */
+		if (k == 0 || cut[k] != n) { k++; cut[k] = n; }
+		nr = nc = k;
+		NEW(row, LIS_INT, nr + 1); NEW(col, LIS_INT, nc + 1);
+		memcpy(row, cut, sizeof(LIS_INT) * ((size_t)k + 1));
+		memcpy(col, cut, sizeof(LIS_INT) * ((size_t)k + 1));
+		col[nc] = np;
+		free(cut); cut = NULL;
+	}
+	NEW(bptr, LIS_INT, nr + 1); NEW(of_col, LIS_INT, np); NEW(seen, LIS_INT, nc); NEW(touched, LIS_INT, nc);
+	for (LIS_INT bj = 0; bj < nc; bj++) for (LIS_INT j = col[bj]; j < col[bj + 1]; j++) of_col[j] = bj;
+	for (LIS_INT i = 0; i < n; i++) for (LIS_INT k = A->ptr[i]; k < A->ptr[i + 1]; k++)
+		if (A->index[k] < 0 || A->index[k] >= np) { err = LISI_ERR(LIS_ERR_ILL_ARG, "CSR matrix: column %D of row %D lies outside [0, %D)\n", A->index[k], i, np); goto fail; }
+	memset(seen, 0, sizeof(LIS_INT) * (size_t)nc);
+	/* the blocks of every block row and their values, counted */
+	size_t kv = 0;
+	LIS_INT kk = 0;
+	bptr[0] = 0;
+	for (LIS_INT bi = 0; bi < nr; bi++) {
+		const LIS_INT bnr = row[bi + 1] - row[bi];
+		LIS_INT nt = 0;
+		for (LIS_INT i = row[bi]; i < row[bi + 1]; i++)
+			for (LIS_INT k = A->ptr[i]; k < A->ptr[i + 1]; k++) {
+				const LIS_INT bj = of_col[A->index[k]];
+				if (!seen[bj]) { seen[bj] = 1; touched[nt++] = bj; kv += (size_t)bnr * (size_t)(col[bj + 1] - col[bj]); }
+			}
+		for (LIS_INT t = 0; t < nt; t++) seen[touched[t]] = 0;
+		kk += nt;
+		bptr[bi + 1] = kk;
+	}
+	if (kv >= 0x7fffffffu) { err = LISI_ERR(LIS_ERR_ILL_ARG, "VBR storage of this matrix would hold %D or more values\n", (LIS_INT)0x7fffffff); goto fail; }
+	NEW(ptr, LIS_INT, kk + 1); NEW(bindex, LIS_INT, kk); NEW(value, LIS_SCALAR, kv);
+	/* ... and filled: seen[bj] = 1 + where the block row's block in block column bj starts in value[] */
+	ptr[0] = 0; kk = 0; kv = 0;
+	for (LIS_INT bi = 0; bi < nr; bi++) {
+		const LIS_INT bnr = row[bi + 1] - row[bi], first = kk;
+		for (LIS_INT ii = 0; ii < bnr; ii++)
+			for (LIS_INT k = A->ptr[row[bi] + ii]; k < A->ptr[row[bi] + ii + 1]; k++) {
+				const LIS_INT bj = of_col[A->index[k]], j = A->index[k] - col[bj];
+				if (!seen[bj]) {
+					const size_t size = (size_t)bnr * (size_t)(col[bj + 1] - col[bj]);
+					memset(&value[kv], 0, sizeof(LIS_SCALAR) * size);
+					bindex[kk] = bj; seen[bj] = (LIS_INT)kv + 1;
+					kv += size; ptr[++kk] = (LIS_INT)kv;
+				}
+				value[(size_t)seen[bj] - 1 + (size_t)j * bnr + ii] = A->value[k];
+			}
+		for (LIS_INT b = first; b < kk; b++) seen[bindex[b]] = 0;
+	}
+	free(of_col); free(seen); free(touched);
+	return finish(B, lis_matrix_set_vbr((LIS_INT)kv, nr, nc, kk, row, col, ptr, bptr, bindex, value, B));
+fail:
+	free(row); free(col); free(ptr); free(bptr); free(bindex); free(of_col); free(seen); free(touched); free(cut); free(value);
+	return err;
+}
+
 LIS_INT lisi_convert_csr_to(LIS_MATRIX Ain, LIS_MATRIX Aout)
 {
 	switch (Aout->matrix_type) {
+	case LIS_MATRIX_VBR: return csr2vbr(Ain, Aout);
 	case LIS_MATRIX_COO: return csr2coo(Ain, Aout);
 	case LIS_MATRIX_DNS: return csr2dns(Ain, Aout);
 	case LIS_MATRIX_CSC: return csr2csc(Ain, Aout);
@@ -489,6 +619,28 @@ LIS_INT lisi_convert_to_csr(LIS_MATRIX A, LIS_MATRIX B)
 		memcpy(c.index, A->col, sizeof(LIS_INT) * (size_t)A->nnz);
 		memcpy(c.value, A->value, sizeof(LIS_SCALAR) * (size_t)A->nnz);
 		break;
+	case LIS_MATRIX_VBR:
+		/* ref lis_matrix_vbr.c:746-872: a row's entries block after block in stored order, ascending column inside a block, exact zeros dropped */
+		for (int pass = 0; pass < 2 && !err; pass++) {
+			if (pass == 1 && (err = csr_out_alloc(&c, n, count))) break;
+			for (LIS_INT bi = 0; bi < A->nr; bi++) {
+				const LIS_INT l = A->row[bi], bnr = A->row[bi + 1] - l;
+				for (LIS_INT i = 0; i < bnr; i++) {
+					LIS_INT k = pass ? c.ptr[l + i] : 0;
+					for (LIS_INT bj = A->bptr[bi]; bj < A->bptr[bi + 1]; bj++) {
+						const LIS_INT c0 = A->col[A->bindex[bj]], bnc = A->col[A->bindex[bj] + 1] - c0;
+						for (LIS_INT j = 0; j < bnc; j++) {
+							const LIS_SCALAR v = A->value[A->ptr[bj] + (size_t)j * bnr + i];
+							if (v == 0.0) continue;
+							if (pass) { c.value[k] = v; c.index[k] = c0 + j; }
+							k++;
+						}
+					}
+					if (!pass) count[l + i] = k;
+				}
+			}
+		}
+		break;
 	case LIS_MATRIX_DNS:
 		/* ref lis_matrix_dns.c:846-895: value != 0 is kept, columns ascending */
 		#pragma omp parallel for schedule(static) num_threads(lisi_host_threads())
@@ -546,6 +698,11 @@ LIS_INT lisi_matrix_deep_copy(LIS_MATRIX A, LIS_MATRIX B)
 	case LIS_MATRIX_DNS:
 		DUP(value, A->value, LIS_SCALAR, n * (size_t)A->np);
 		return finish(B, lis_matrix_set_dns(value, B));
+	case LIS_MATRIX_VBR: {      /* ref lis_matrix_vbr.c:221-258 */
+		LIS_INT *col = NULL;
+		DUP(row, A->row, LIS_INT, (size_t)A->nr + 1); DUP(col, A->col, LIS_INT, (size_t)A->nc + 1); DUP(ptr, A->ptr, LIS_INT, (size_t)A->bnnz + 1);
+		DUP(bptr, A->bptr, LIS_INT, (size_t)A->nr + 1); DUP(bindex, A->bindex, LIS_INT, A->bnnz); DUP(value, A->value, LIS_SCALAR, A->nnz);
+		return finish(B, lis_matrix_set_vbr(A->nnz, A->nr, A->nc, A->bnnz, row, col, ptr, bptr, bindex, value, B)); }
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	}
@@ -575,8 +732,8 @@ static LIS_INT convert_impl(LIS_MATRIX Ain, LIS_MATRIX Aout)
 	LISCHK(lisi_matrix_check(Ain, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisi_matrix_check(Aout, LISI_CHECK_NULL));
 	const LIS_INT want = Aout->matrix_type;
-	LISCHK(lisi_coo_dns_one_rank(Ain->matrix_type));        /* COO and DNS, as a source or as a target: one rank, refused before anything is touched */
-	LISCHK(lisi_coo_dns_one_rank(want));
+	LISCHK(lisi_one_rank_only(Ain->matrix_type));        /* COO, DNS and VBR, as a source or as a target: one rank, refused before anything is touched */
+	LISCHK(lisi_one_rank_only(want));
 	if (MDEV(Ain)->device_only) {          /* born in HBM: ELL, DIA, CSC and BSR are built there; what they leave to the host (JAD, rows out of order for DIA / CSC,
 		                                        * block rows of more than 96 blocks) runs on a host copy of the arrays, made for this conversion */
 		int done = 0;

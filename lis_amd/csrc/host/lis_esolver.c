@@ -366,8 +366,8 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 			                : "inner eigensolver %D (-ie) is not served by liblis_amd for -e %s (%s)\n", ninner, d->key, d->inner_keys);
 	}
 	/* (explicit: a COO copy looks like CSR in HBM, and lis_matrix_shift_matrix refuses both) */
-	if (B != NULL && (lisi_format_coo_dns(A->matrix_type) || lisi_format_coo_dns(B->matrix_type) || lisi_format_coo_dns(estorage)))
-		REFUSE(LIS_ERR_NOT_IMPLEMENTED, "lis_gesolve: A and B in COO or DNS storage (or -estorage coo | dns) are not served: lis_matrix_shift_matrix does not take them (A, B and x are untouched)\n");
+	if (B != NULL && (lisi_format_one_rank(A->matrix_type) || lisi_format_one_rank(B->matrix_type) || lisi_format_one_rank(estorage)))
+		REFUSE(LIS_ERR_NOT_IMPLEMENTED, "lis_gesolve: A and B in COO or DNS storage, or in VBR storage (or -estorage coo | dns | vbr), are not served: lis_matrix_shift_matrix does not take them (A, B and x are untouched)\n");
 	if (B != NULL && (A->is_splited || B->is_splited || !lisi_format_swept(B->matrix_type) || B->np != B->n || A->np != A->n))
 		REFUSE(LIS_ERR_NOT_IMPLEMENTED, "lis_gesolve: A and B must be unsplit matrices in a served storage format without ghost columns (lis_matrix_shift_matrix)\n");
 	if (MDEV(A)->device_only && A->matrix_type != LIS_MATRIX_CSR) REFUSE(LIS_ERR_NOT_IMPLEMENTED, "a matrix that lives in HBM only is shifted in CSR storage\n");

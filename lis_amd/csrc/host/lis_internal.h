@@ -93,6 +93,9 @@ typedef struct {
 	double *sx, *sy; size_t scap;
 	/* split JAD matrix (lis_split.c): d->ptr/index/value/plan hold L, these hold U, the diagonal and a work vector */
 	int coo_in_order;          /* COO: the rows of the copy list the triplets in ascending k over the whole matrix (row[] non-decreasing: the in-place row form, a copy built in HBM from CSR rows), so the transposed copy is the CSR transposition of these rows */
+	/* VBR (native arrays: row / col / ptr / bptr / bindex / value as the host holds them): the block row of every row, made in HBM; and, for the reference-order
+	 * mode at T > 1, the source-row borders of the T chunks of block rows of the transposed product (t_borders_T = the T they were made for) */
+	int *col, *brow, *t_borders; int t_borders_T;
 	int split_jad;
 	int *u_ptr, *u_index;
 	double *u_value, *dsplit, *jw;
@@ -304,10 +307,14 @@ LIS_INT lisc_allgather_host(const void *send, void *recv, size_t bytes);
 
 /* ---- matrix internals shared between files */
 LIS_INT lisi_matrix_check(LIS_MATRIX A, int level);
-int     lisi_format_served(LIS_INT type);                          /* one of the eight storage formats whose products are served (lis_matvec.c) */
+int     lisi_format_served(LIS_INT type);                          /* one of the nine storage formats whose products are served (lis_matvec.c) */
 int     lisi_format_swept(LIS_INT type);                           /* ... of the six that lis_matvec_optimize times, lis_matrix_shift_matrix and lis_gesolve take */
-int     lisi_format_coo_dns(LIS_INT type);                         /* COO or DNS: one rank, never split */
-LIS_INT lisi_coo_dns_one_rank(LIS_INT type);                       /* LIS_ERR_NOT_IMPLEMENTED for COO / DNS in a job of several ranks */
+int     lisi_format_one_rank(LIS_INT type);                        /* COO, DNS or VBR: one rank, never split */
+const char *lisi_format_name(LIS_INT type);                        /* "CSR" .. "DNS" */
+LIS_INT lisi_one_rank_only(LIS_INT type);                          /* LIS_ERR_NOT_IMPLEMENTED for COO / DNS / VBR in a job of several ranks */
+typedef struct { LIS_SCALAR *out; LIS_SCALAR sigma; } lisi_vbr_diag_t;
+void    lisi_vbr_diagonal_walk(LIS_MATRIX A, const lisi_vbr_diag_t *w);   /* the reference's diagonal search on VBR storage: read into out[], or shift by sigma (lis_matrix.c) */
+void    lisi_sort_id(LIS_INT lo, LIS_INT hi, LIS_INT *i1, LIS_SCALAR *d1);   /* the reference's ascending quicksort of a row, [lo, hi] inclusive (lis_convert.c) */
 void    lisi_raw_product(LIS_MATRIX A, LIS_INT fmt, LIS_SCALAR x[], LIS_SCALAR y[], int transposed);   /* lis_matvec_<fmt> / lis_matvech_<fmt> on raw host arrays (lis_matvec.c) */
 int     lisi_host_threads(void);      /* threads the host-side conversions may use: affinity mask capped by the cgroup CPU quota, at most 32 */
 /* ---- split form (lis_split.c) */

@@ -608,7 +608,7 @@ LIS_INT lis_input(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, char *filename)
 	memset(&h, 0, sizeof(h));
 	err = mm_banner(&s, "matrix", &h);
 	if (!err) err = mm_size(&s, &h);
-	if (!err && !h.coordinate && want == LIS_MATRIX_DNS) err = lisi_coo_dns_one_rank(want);
+	if (!err && !h.coordinate && want == LIS_MATRIX_DNS) err = lisi_one_rank_only(want);
 	if (!err) err = h.coordinate ? mm_read_csr(&s, &h, A, b, x) : (want == LIS_MATRIX_DNS ? mm_read_dns(&s, &h, A) : mm_read_dense(&s, &h, A));
 	free(s.buf);
 	if (err) return err;

@@ -134,10 +134,23 @@ LIS_INT lis_matrix_set_destroyflag(LIS_MATRIX A, LIS_INT flag)
 }
 
 LIS_INT lis_matrix_set_blocksize(LIS_MATRIX A, LIS_INT bnr, LIS_INT bnc, LIS_INT row[], LIS_INT col[])
-{	/* ref lis_matrix.c:1078: fixed block sizes for the BSR conversion (row/col: VBR only, not served) */
+{	/* ref lis_matrix_ops.c:71-124.  Without arrays: fixed block sizes for the BSR conversion.  With arrays: the block rows and block columns of the VBR conversion,
+	 * bnr = nr and bnc = nc their counts, as lis_matrix_convert_csr2vbr reads them from conv_bnr / conv_bnc.  The arrays are copied: row[0 .. nr] and col[0 .. nc],
+	 * the entries the conversion reads (the reference copies n entries of each, whatever their length, and does not store the counts in this call) */
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_NULL));
 	if (bnr <= 0 || bnc <= 0) return LISI_ERR(LIS_ERR_ILL_ARG, "bnr=%D <= 0 or bnc=%D <= 0\n", bnr, bnc);
-	if (row || col) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "variable block sizes (VBR) are not served\n");
+	if ((row == NULL) != (col == NULL)) return LISI_ERR(LIS_ERR_ILL_ARG, "either row[] or col[] is NULL\n");
+	if (row) {
+		LIS_INT *conv_row = (LIS_INT *)malloc(sizeof(LIS_INT) * ((size_t)bnr + 1)), *conv_col = (LIS_INT *)malloc(sizeof(LIS_INT) * ((size_t)bnc + 1));
+		if (!conv_row || !conv_col) { free(conv_row); free(conv_col); return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", bnr + bnc + 2); }
+		memcpy(conv_row, row, sizeof(LIS_INT) * ((size_t)bnr + 1));
+		memcpy(conv_col, col, sizeof(LIS_INT) * ((size_t)bnc + 1));
+		free(A->conv_row); free(A->conv_col);
+		A->conv_row = conv_row; A->conv_col = conv_col;
+	} else if (A->conv_row && (bnr != A->conv_bnr || bnc != A->conv_bnc)) {      /* other counts than the arrays were given with: they describe the arrays no longer */
+		free(A->conv_row); free(A->conv_col);
+		A->conv_row = NULL; A->conv_col = NULL;
+	}
 	A->conv_bnr = bnr; A->conv_bnc = bnc;
 	return LIS_SUCCESS;
 }
@@ -211,6 +224,14 @@ LIS_INT lis_matrix_malloc_dns(LIS_INT n, LIS_INT np, LIS_SCALAR **value)
 	const size_t count = (size_t)n * (size_t)np;
 	*value = (LIS_SCALAR *)matrix_array(sizeof(LIS_SCALAR) * (count ? count : 1));
 	if (!*value) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D x %D\n", n, np);
+	return LIS_SUCCESS;
+}
+LIS_INT lis_matrix_malloc_vbr(LIS_INT n, LIS_INT nnz, LIS_INT nr, LIS_INT nc, LIS_INT bnnz, LIS_INT **row, LIS_INT **col, LIS_INT **ptr, LIS_INT **bptr, LIS_INT **bindex, LIS_SCALAR **value)
+{	/* ref lis_matrix_vbr.c:106-162 */
+	(void)n;
+	*row = NULL; *col = NULL; *ptr = NULL; *bptr = NULL; *bindex = NULL; *value = NULL;
+	ALLOC_OR_FAIL(*row, LIS_INT, nr + 1); ALLOC_OR_FAIL(*col, LIS_INT, nc + 1); ALLOC_OR_FAIL(*ptr, LIS_INT, bnnz + 1);
+	ALLOC_OR_FAIL(*bptr, LIS_INT, nr + 1); ALLOC_OR_FAIL(*bindex, LIS_INT, bnnz); ALLOC_OR_FAIL(*value, LIS_SCALAR, nnz);
 	return LIS_SUCCESS;
 }
 
@@ -290,6 +311,15 @@ LIS_INT lis_matrix_set_dns(LIS_SCALAR *value, LIS_MATRIX A)
 	SET_GUARD(A);
 	A->value = value;
 	A->is_copy = LIS_FALSE; A->status = -LIS_MATRIX_DNS;
+	return LIS_SUCCESS;
+}
+
+LIS_INT lis_matrix_set_vbr(LIS_INT nnz, LIS_INT nr, LIS_INT nc, LIS_INT bnnz, LIS_INT *row, LIS_INT *col, LIS_INT *ptr, LIS_INT *bptr, LIS_INT *bindex, LIS_SCALAR *value, LIS_MATRIX A)
+{	/* ref lis_matrix_vbr.c:66-102: nnz counts the stored values, zeros of the blocks included */
+	SET_GUARD(A);
+	A->row = row; A->col = col; A->ptr = ptr; A->bptr = bptr; A->bindex = bindex; A->value = value;
+	A->is_copy = LIS_FALSE; A->status = -LIS_MATRIX_VBR; A->is_block = LIS_TRUE;
+	A->nnz = nnz; A->bnnz = bnnz; A->nr = nr; A->nc = nc;
 	return LIS_SUCCESS;
 }
 
@@ -500,6 +530,29 @@ LIS_INT lis_matrix_destroy(LIS_MATRIX A)
 }
 
 /* ------------------------------------------------------------------ diagonal */
+/* The reference's search for the diagonal of a VBR matrix (lis_matrix_vbr.c:908-928 get_diagonal, :969-989 shift_diagonal): block row bi, first row i, walks its
+ * blocks in stored order and takes a block as the diagonal one when i >= bjj*bnc && i < (bjj+1)*bnc, bjj the block COLUMN NUMBER and bnc that block's width --
+ * which is the block that holds column i only where all blocks before it are bnc wide.  On variable blocks it takes entries that are not on the diagonal, or none:
+ * those rows are not written (get) or not shifted.  Restated as it stands.  w->out != NULL: out[i] = the entry; else: the entry -= w->sigma */
+void lisi_vbr_diagonal_walk(LIS_MATRIX A, const lisi_vbr_diag_t *w)
+{
+	const LIS_INT n = A->n;
+	for (LIS_INT bi = 0; bi < A->nr; bi++) {
+		LIS_INT k = 0, i = A->row[bi];
+		const LIS_INT bnr = A->row[bi + 1] - A->row[bi];
+		for (LIS_INT bj = A->bptr[bi]; bj < A->bptr[bi + 1]; bj++) {
+			const LIS_INT bjj = A->bindex[bj], bnc = A->col[bjj + 1] - A->col[bjj];
+			if (i >= bjj * bnc && i < (bjj + 1) * bnc)
+				for (LIS_INT j = i % bnc; j < bnc && k < bnr && i < n; j++) {
+					LIS_SCALAR *v = &A->value[A->ptr[bj] + (size_t)j * bnr + k];
+					if (w->out) w->out[i] = *v; else *v -= w->sigma;
+					i++; k++;
+				}
+			if (k == bnr) break;
+		}
+	}
+}
+
 LIS_INT lis_matrix_get_diagonal(LIS_MATRIX A, LIS_VECTOR D)
 {	/* ref lis_matrix_ops.c:728 -> per-format get_diagonal; first stored entry with column == row, else 0 */
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
@@ -526,7 +579,8 @@ LIS_INT lis_matrix_get_diagonal(LIS_MATRIX A, LIS_VECTOR D)
 	}
 	const LIS_INT n = A->n;
 	LISCHK(lisp_fill_matrix(A));
-	const int coo_keeps = A->matrix_type == LIS_MATRIX_COO && !A->is_splited;    /* COO writes only the rows that store an (i,i): the others keep what D held (lis_matrix_coo.c:343-349) */
+	/* COO writes only the rows that store an (i,i), VBR only those its search finds: the others keep what D held (lis_matrix_coo.c:343-349, lis_matrix_vbr.c:908-928) */
+	const int coo_keeps = (A->matrix_type == LIS_MATRIX_COO || A->matrix_type == LIS_MATRIX_VBR) && !A->is_splited;
 	LISCHK(lisd_vec_host_write(D, coo_keeps || (size_t)(D->np + D->pad) > (size_t)n));   /* the host array is about to be written (entries beyond n keep what they hold) */
 	LIS_SCALAR *out = D->value;
 	if (!coo_keeps) for (LIS_INT i = 0; i < n; i++) out[i] = 0.0;
@@ -576,6 +630,10 @@ LIS_INT lis_matrix_get_diagonal(LIS_MATRIX A, LIS_VECTOR D)
 	case LIS_MATRIX_DNS:        /* ref lis_matrix_dns.c:223-241: value[i*n + i] */
 		for (LIS_INT i = 0; i < n; i++) out[i] = A->value[(size_t)i * n + i];
 		break;
+	case LIS_MATRIX_VBR: {      /* ref lis_matrix_vbr.c:908-928, its search restated (lisi_vbr_diagonal_walk) */
+		lisi_vbr_diag_t w = {out, 0.0};
+		lisi_vbr_diagonal_walk(A, &w);
+		break; }
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
 	}

@@ -15,22 +15,27 @@ int lisi_format_swept(LIS_INT type)
 {
 	return type == LIS_MATRIX_CSR || type == LIS_MATRIX_CSC || type == LIS_MATRIX_DIA || type == LIS_MATRIX_ELL || type == LIS_MATRIX_JAD || type == LIS_MATRIX_BSR;
 }
-/* triplets and dense: served on one rank, never split, never shifted by a matrix */
-int lisi_format_coo_dns(LIS_INT type) { return type == LIS_MATRIX_COO || type == LIS_MATRIX_DNS; }
-/* the eight storage formats whose products this library serves */
-int lisi_format_served(LIS_INT type) { return lisi_format_swept(type) || lisi_format_coo_dns(type); }
-/* COO and DNS in a job of several ranks: refused before anything is touched (their reference products are serial or whole-matrix loops over local arrays; no halo form is served) */
-LIS_INT lisi_coo_dns_one_rank(LIS_INT type)
+/* triplets, dense and variable blocks: served on one rank, never split, never shifted by a matrix */
+int lisi_format_one_rank(LIS_INT type) { return type == LIS_MATRIX_COO || type == LIS_MATRIX_DNS || type == LIS_MATRIX_VBR; }
+const char *lisi_format_name(LIS_INT type)
 {
-	if (lisi_format_coo_dns(type) && lisg.nprocs > 1)
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "%s storage is served on one rank only (this job has %D)\n", type == LIS_MATRIX_COO ? "COO" : "DNS", (LIS_INT)lisg.nprocs);
+	static const char *name[] = {"CSR", "CSC", "MSR", "DIA", "ELL", "JAD", "BSR", "BSC", "VBR", "COO", "DNS"};
+	return type >= LIS_MATRIX_CSR && type <= LIS_MATRIX_DNS ? name[type - 1] : "unknown";
+}
+/* the nine storage formats whose products this library serves */
+int lisi_format_served(LIS_INT type) { return lisi_format_swept(type) || lisi_format_one_rank(type); }
+/* COO, DNS and VBR in a job of several ranks: refused before anything is touched (their reference products are serial or whole-matrix loops over local arrays; no halo form is served) */
+LIS_INT lisi_one_rank_only(LIS_INT type)
+{
+	if (lisi_format_one_rank(type) && lisg.nprocs > 1)
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "%s storage is served on one rank only (this job has %D)\n", lisi_format_name(type), (LIS_INT)lisg.nprocs);
 	return LIS_SUCCESS;
 }
 
 LIS_INT lis_matvec(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 {
 	if (!lisi_format_served(A->matrix_type)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
-	LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
+	LISCHK(lisi_one_rank_only(A->matrix_type));
 	LISCHK(lisd_mat_ready(A));
 	/* like the reference (LIS_MATVEC_REALLOC, include/lis_matvec.h:32-43: lis_realloc of X->value to np + pad entries), X grows to hold the ghost and block
 	 * padding entries of A -- the host array too: a program that reads X->value[n ..) after a product in a multi-rank job must find memory there.  The new
@@ -88,6 +93,7 @@ void lis_matvec_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_pro
 void lis_matvec_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_BSR, x, y, 0); }
 void lis_matvec_coo(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_COO, x, y, 0); }
 void lis_matvec_dns(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_DNS, x, y, 0); }
+void lis_matvec_vbr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_VBR, x, y, 0); }
 
 /* ref src/matvec/lis_matvec.c:50-51 */
 LIS_MATVEC_FUNC LIS_MATVEC  = lis_matvec;

@@ -76,8 +76,35 @@ static void walk(LIS_INT type, LIS_MATRIX A, const LIS_INT *ptr, const LIS_INT *
 					for (LIS_INT i = 0; i < bnr; i++, k++) emit(w, bj + j, bi * bnr + i, value[k]);
 			}
 		break; }
+	case LIS_MATRIX_VBR:        /* ref lis_matvec_vbr.c:284-300: block row after block row, its blocks in stored order, j outer, i inner */
+		for (LIS_INT bi = 0; bi < A->nr; bi++)
+			for (LIS_INT bc = A->bptr[bi]; bc < A->bptr[bi + 1]; bc++) {
+				const LIS_INT bj = A->bindex[bc];
+				size_t k = (size_t)A->ptr[bc];
+				for (LIS_INT j = A->col[bj]; j < A->col[bj + 1]; j++)
+					for (LIS_INT i = A->row[bi]; i < A->row[bi + 1]; i++, k++) emit(w, j, i, value[k]);
+			}
+		break;
 	default: break;
 	}
+}
+
+/* VBR in the reference-order mode at T > 1: the threads of lis_matvech_vbr own chunks of BLOCK ROWS (the static schedule of its `omp for` over nr), so the chunk
+ * borders of the transposed sums are the source rows row[first block row of chunk t], kept in HBM for the T they were made for */
+static LIS_INT vbr_chunk_borders(LIS_MATRIX A, lisd_mat *d, int T)
+{
+	if (d->t_borders && d->t_borders_T == T) return LIS_SUCCESS;
+	(void)liship_free(d->t_borders); d->t_borders = NULL; d->t_borders_T = 0;
+	LISCHK(lisp_fill_matrix(A));
+	LIS_INT *b = (LIS_INT *)malloc(sizeof(LIS_INT) * ((size_t)T + 1));
+	if (!b) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", (LIS_INT)T + 1);
+	const LIS_INT q = A->nr / T, rem = A->nr % T;
+	for (int t = 0; t <= T; t++) b[t] = A->row[t < rem ? t * (q + 1) : t * q + rem];      /* LIS_GET_ISIE(t, T, nr) starts; t = T: nr */
+	LIS_INT err = lisd_upload_i(&d->t_borders, b, (size_t)T + 1);
+	if (!err) { const int rc = liship_stream_synchronize(lisg.stream); if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc); }
+	free(b);
+	if (!err) d->t_borders_T = T;
+	return err;
 }
 
 /* the walks of a split matrix (see the head of this file); CSR: off-diagonal parts only, the diagonal is added by lisd_spmv_t */
@@ -265,7 +292,10 @@ LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy)
 		HIPCHK(liship_spmv_dns_t_f64(A->n, A->np, lisg.ref_reductions > 1 ? lisg.ref_reductions : 1, d->value, dx, dy, lisg.stream));
 		return LIS_SUCCESS;
 	}
-	if (lisg.ref_reductions > 1 && A->matrix_type == LIS_MATRIX_CSR)
+	if (lisg.ref_reductions > 1 && A->matrix_type == LIS_MATRIX_VBR) {
+		LISCHK(vbr_chunk_borders(A, d, lisg.ref_reductions));
+		HIPCHK(liship_spmv_csr_transposed_bordered_f64(d->t_rows, lisg.ref_reductions, d->t_borders, d->t_ptr, d->t_index, d->t_value, dx, dy, lisg.stream));
+	} else if (lisg.ref_reductions > 1 && A->matrix_type == LIS_MATRIX_CSR)
 		/* reference-order mode at T > 1: the OpenMP build's per-thread scatter buffers group a column's terms by row chunk (lis_matvec_csr.c:207-236).
 		 * CSR here, ELL below; DIA, JAD and BSR keep the one-thread order (their threaded walks group differently again) */
 		HIPCHK(liship_spmv_csr_transposed_chunked_f64(d->t_rows, A->n, lisg.ref_reductions, d->t_ptr, d->t_index, d->t_value, dx, dy, lisg.stream));
@@ -284,7 +314,7 @@ LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy)
 LIS_INT lis_matvech(LIS_MATRIX A, LIS_VECTOR X, LIS_VECTOR Y)
 {	/* ref src/matvec/lis_matvec.c:191-349; Y grows to np+pad like LIS_MATVEC_REDUCE0 (lis_matvec.h:60-72) */
 	if (!lisi_format_served(A->matrix_type)) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
-	LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
+	LISCHK(lisi_one_rank_only(A->matrix_type));
 	LISCHK(lisd_mat_ready_t(A));
 	if (A->np + A->pad > Y->np + Y->pad) { Y->np = A->np; Y->pad = A->pad; }
 	double *dx, *dy;
@@ -305,3 +335,4 @@ void lis_matvech_jad(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_pr
 void lis_matvech_bsr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_BSR, x, y, 1); }
 void lis_matvech_coo(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_COO, x, y, 1); }
 void lis_matvech_dns(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_DNS, x, y, 1); }
+void lis_matvech_vbr(LIS_MATRIX A, LIS_SCALAR x[], LIS_SCALAR y[]) { lisi_raw_product(A, LIS_MATRIX_VBR, x, y, 1); }

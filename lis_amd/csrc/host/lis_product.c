@@ -84,6 +84,11 @@ static int split_jad_whole(PRODUCT)
 extern int liship_spmv_dns_f64(int n, int np, const double *value, const double *x, double *y, void *stream) __attribute__((weak));
 static int dns_whole(PRODUCT) { return liship_spmv_dns_f64 ? liship_spmv_dns_f64(d->n, d->np, d->value, x, y, lisg.stream) : LISHIP_ERR_ARG; }
 
+/* variable blocks: like dense, no row ranges and no fused dot; weak for the same reason */
+extern int liship_spmv_vbr_f64(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, const double *value,
+                               const double *x, double *y, void *stream) __attribute__((weak));
+static int vbr_whole(PRODUCT) { return liship_spmv_vbr_f64 ? liship_spmv_vbr_f64(d->n, d->row, d->col, d->ptr, d->bptr, d->bindex, d->brow, d->value, x, y, lisg.stream) : LISHIP_ERR_ARG; }
+
 static const fmt_ops csr_ops = {0, csr_whole, csr_rows, csr_dot, csr_whole};
 static const fmt_ops ell_ops = {0, ell_whole, ell_rows, ell_dot, ell_index};       /* (no second attempt with the codes, no strips again) */
 static const fmt_ops dia_ops = {0, dia_whole, dia_rows, dia_dot, dia_launch};
@@ -91,6 +96,7 @@ static const fmt_ops jad_ops = {0, jad_whole, NULL, NULL, NULL};
 static const fmt_ops bsr_ops = {1, bsr_whole, bsr_rows, bsr_dot, bsr_whole};
 static const fmt_ops split_jad_ops = {0, split_jad_whole, NULL, NULL, NULL};
 static const fmt_ops dns_ops = {0, dns_whole, NULL, NULL, NULL};
+static const fmt_ops vbr_ops = {0, vbr_whole, NULL, NULL, NULL};
 
 static const fmt_ops *ops_of(const lisd_mat *d)
 {
@@ -102,6 +108,7 @@ static const fmt_ops *ops_of(const lisd_mat *d)
 	case LIS_MATRIX_JAD: return &jad_ops;
 	case LIS_MATRIX_BSR: return &bsr_ops;
 	case LIS_MATRIX_DNS: return &dns_ops;
+	case LIS_MATRIX_VBR: return &vbr_ops;
 	default: return NULL;
 	}
 }

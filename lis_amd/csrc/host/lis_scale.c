@@ -7,7 +7,7 @@
  * (the truth in both residency modes) and drops the HBM copy, which is rebuilt on the next product.
  * The rounding of every entry is the reference's, including its per-format association:
  *     jacobi      v *= d[row]                                   (all formats)
- *     symm_diag   CSR: (v*d[row])*d[col]   CSC: (v*d[col])*d[row]   ELL/DIA/JAD/BSR/DNS: v*(d[row]*d[col])   COO: v*(d[row]*d[row]), the reference's own
+ *     symm_diag   CSR: (v*d[row])*d[col]   CSC: (v*d[col])*d[row]   ELL/DIA/JAD/BSR/DNS: v*(d[row]*d[col])   VBR: (v*d[row])*d[col]   COO: v*(d[row]*d[row]), the reference's own
  * with d = 1/diag (jacobi) or 1/sqrt|diag| (symm_diag); b is scaled by d; A and b stay scaled afterwards
  * (A->is_scaled, B->is_scaled), exactly as the reference leaves them.
  */
@@ -126,6 +126,17 @@ static LIS_INT scale_values(LIS_MATRIX A, const double *d, int symm)
 			else A->value[k] *= d[i];
 		}
 		break;
+	case LIS_MATRIX_VBR:        /* ref lis_matrix_vbr.c:1055-1069, :1097-1111: a block row's values lie one behind the other; value*d[i]*d[j] in that order */
+		for (LIS_INT bi = 0; bi < A->nr; bi++) {
+			size_t k = (size_t)A->ptr[A->bptr[bi]];
+			for (LIS_INT bj = A->bptr[bi]; bj < A->bptr[bi + 1]; bj++)
+				for (LIS_INT j = A->col[A->bindex[bj]]; j < A->col[A->bindex[bj] + 1]; j++)
+					for (LIS_INT i = A->row[bi]; i < A->row[bi + 1]; i++, k++) {
+						if (symm) A->value[k] = A->value[k] * d[i] * d[j];
+						else A->value[k] *= d[i];
+					}
+		}
+		break;
 	case LIS_MATRIX_DNS:        /* ref lis_matrix_dns.c:453-494 */
 		for (LIS_INT j = 0; j < A->np; j++)
 			for (LIS_INT i = 0; i < n; i++) {
@@ -218,11 +229,27 @@ LIS_INT lis_matrix_scale(LIS_MATRIX A, LIS_VECTOR B, LIS_VECTOR D, LIS_INT actio
 	} else {
 		for (LIS_INT i = 0; i < n; i++) d[i] = 1.0 / d[i];
 	}
-	LISCHK(scale_values(A, d, action == LIS_SCALE_SYMM_DIAG));
+	lisd_mat *m = MDEV(A);
+	const int vbr_in_hbm = m->ready && !m->host_written && A->matrix_type == LIS_MATRIX_VBR && m->type == LIS_MATRIX_VBR && !A->is_splited && m->value && m->brow && np == n;
+	if (vbr_in_hbm) {
+		/* VBR whose copy lives in HBM: one launch scales the copy's value[] (kernels/vbr.hip: the roundings of scale_values), the host arrays get the same edit
+		 * inside the edit bracket, and the copy stays */
+		double *dd;
+		lis_amd_vector_host_modified(D);
+		LISCHK(lisd_vec_in(D, &dd));
+		HIPCHK(liship_vbr_scale_f64(n, m->row, m->col, m->ptr, m->bptr, m->bindex, m->brow, m->value, dd, action == LIS_SCALE_SYMM_DIAG, lisg.stream));
+		LISCHK(lisd_mat_values_changed(A));
+		LISCHK(lisd_vec_host_write(D, 1));
+		d = D->value;
+		lisd_mat_host_edit_begin(A);
+	}
+	LIS_INT err = scale_values(A, d, action == LIS_SCALE_SYMM_DIAG);
+	if (vbr_in_hbm) lisd_mat_host_edit_end(A);
+	if (err) return err;
 	for (LIS_INT i = 0; i < n; i++) b[i] = b[i] * d[i];
 	lis_amd_vector_host_modified(D);
 	lis_amd_vector_host_modified(B);
-	lisd_mat_free(A);                                  /* HBM copy (and its transpose) are stale */
+	if (!vbr_in_hbm) lisd_mat_free(A);                 /* HBM copy (and its transpose) are stale */
 	A->is_scaled = LIS_TRUE;
 	B->is_scaled = LIS_TRUE;
 	return LIS_SUCCESS;

@@ -14,6 +14,7 @@
  *   BSR  lis_matrix_bsr.c:748   the diagonal entries of the blocks that cover rows i .. of each block row, the first covering block first
  *   COO  lis_matrix_coo.c:357   EVERY stored entry with row == col, duplicates each
  *   DNS  lis_matrix_dns.c:244   value[i n + i], every row
+ *   VBR  lis_matrix_vbr.c:937   the entries the reference's diagonal search finds: the diagonal where all blocks have one size, other entries or none on variable blocks
  * A split matrix (is_splited) shifts A->D only (for BSR the diagonals of its blocks), every row, whether the row had a diagonal entry or not.
  * value -= sigma rounds: shift(s) then shift(-s) does not give the bits back.  The reference has that drift and so has this library.
  *
@@ -24,6 +25,7 @@
  *                               was derived from the old values and makes the plan again from the HBM arrays.  The host arrays, where they exist, get the same edit on
  *                               the host inside lisd_mat_host_edit_begin / _end, so that the write watch (lis_pages.c) does not take it for the program's and throw the
  *                               copy away.  No matrix array crosses the bus.  The plan rebuild costs 10 ms per shift at 256^3, the host edit ~300 ms.
+ *   VBR (copy in HBM)           one launch on the copy's value[] (kernels/vbr.hip), the host arrays edited inside the same bracket; the transposed copy comes back on its next use
  *   the other seven formats     the host arrays are edited as above and the HBM copy is dropped (what lis_amd_matrix_host_modified does): the next product uploads.
  *   HBM-only and not CSR        refused (such a matrix has no host arrays to edit).
  */
@@ -82,6 +84,10 @@ static void shift_host(LIS_MATRIX A, LIS_SCALAR sigma)
 	case LIS_MATRIX_DNS:        /* ref lis_matrix_dns.c:268-271: value[i*n + i] */
 		for (LIS_INT i = 0; i < n; i++) A->value[(size_t)i * n + i] -= sigma;
 		break;
+	case LIS_MATRIX_VBR: {      /* ref lis_matrix_vbr.c:969-989: the entries its diagonal search finds (lisi_vbr_diagonal_walk) */
+		const lisi_vbr_diag_t w = {NULL, sigma};
+		lisi_vbr_diagonal_walk(A, &w);
+		break; }
 	default: break;
 	}
 }
@@ -102,6 +108,16 @@ LIS_INT lis_matrix_shift_diagonal(LIS_MATRIX A, LIS_SCALAR sigma)
 		HIPCHK(liship_csr_shift_diagonal_f64(d->n, d->ptr, d->index, d->value, sigma, lisg.stream));
 		LISCHK(lisd_mat_values_changed(A));
 		if (d->device_only) return LIS_SUCCESS;
+		lisd_mat_host_edit_begin(A);
+		shift_host(A, sigma);
+		lisd_mat_host_edit_end(A);
+		return LIS_SUCCESS;
+	}
+	if (d->ready && A->matrix_type == LIS_MATRIX_VBR && d->type == LIS_MATRIX_VBR && d->value && d->row) {
+		/* VBR: one launch on the copy's value[] (the search of shift_host, entry for entry), the same edit on the host arrays inside the edit bracket */
+		LISCHK(lisp_fill_matrix(A));
+		HIPCHK(liship_vbr_shift_diagonal_f64(A->n, d->nr, d->row, d->col, d->ptr, d->bptr, d->bindex, d->value, sigma, lisg.stream));
+		LISCHK(lisd_mat_values_changed(A));
 		lisd_mat_host_edit_begin(A);
 		shift_host(A, sigma);
 		lisd_mat_host_edit_end(A);
@@ -245,9 +261,9 @@ LIS_INT lis_matrix_shift_matrix(LIS_MATRIX A, LIS_MATRIX B, LIS_SCALAR sigma)
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	LISCHK(lisi_matrix_check(B, LISI_CHECK_ASSEMBLED));
 	if (A->n != B->n || A->gn != B->gn) return LISI_ERR(LIS_ERR_ILL_ARG, "matrix A (n = %D) and matrix B (n = %D) differ in size\n", A->n, B->n);
-	if (lisi_format_coo_dns(A->matrix_type) || lisi_format_coo_dns(B->matrix_type))      /* (a COO copy looks like CSR in HBM: the gate reads the matrix, not the copy) */
+	if (lisi_format_one_rank(A->matrix_type) || lisi_format_one_rank(B->matrix_type))      /* (a COO copy looks like CSR in HBM: the gate reads the matrix, not the copy) */
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_matrix_shift_matrix: %s storage is not shifted by a matrix -- convert to one of CSR, CSC, DIA, ELL, JAD, BSR first (A and B are untouched)\n",
-		                (lisi_format_coo_dns(A->matrix_type) ? A->matrix_type : B->matrix_type) == LIS_MATRIX_COO ? "COO" : "DNS");
+		                lisi_format_name(lisi_format_one_rank(A->matrix_type) ? A->matrix_type : B->matrix_type));
 	if (!lisi_format_swept(A->matrix_type) || !lisi_format_swept(B->matrix_type))
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", lisi_format_swept(A->matrix_type) ? B->matrix_type : A->matrix_type);
 	if (lisg.nprocs > 1 || A->nprocs > 1 || A->np != A->n || B->np != B->n)

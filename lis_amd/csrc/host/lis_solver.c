@@ -887,8 +887,8 @@ LIS_INT lis_solve(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER solver)
 	solver->A = A;
 	if (solver->options[LIS_OPTIONS_PRECON] < 0 || solver->options[LIS_OPTIONS_PRECON] > LIS_PRECONNAME_MAX)
 		return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_PRECON is %D (Set between 0 to %D)\n", solver->options[LIS_OPTIONS_PRECON], LIS_PRECONNAME_MAX);
-	LIS_INT err = lisi_coo_dns_one_rank(A->matrix_type);          /* COO / DNS, held or asked for with -storage: one rank, refused before A, b or x is touched */
-	if (!err) err = lisi_coo_dns_one_rank(solver->options[LIS_OPTIONS_STORAGE]);
+	LIS_INT err = lisi_one_rank_only(A->matrix_type);          /* COO / DNS, held or asked for with -storage: one rank, refused before A, b or x is touched */
+	if (!err) err = lisi_one_rank_only(solver->options[LIS_OPTIONS_STORAGE]);
 	if (!err) err = lis_precon_create(solver, &precon);
 	if (err) { solver->retcode = err; return err; }
 	err = lis_solve_kernel(A, b, x, solver, precon);

@@ -218,8 +218,8 @@ LIS_INT lis_matrix_split(LIS_MATRIX A)
 {
 	LISCHK(lisi_matrix_check(A, LISI_CHECK_ASSEMBLED));
 	if (A->is_splited) return LIS_SUCCESS;
-	if (lisi_format_coo_dns(A->matrix_type))      /* (the reference splits both; what rests on the split -- lis_matrix_solve -- it has for neither COO nor the preconditioners here) */
-		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_matrix_split: %s storage is not split by liblis_amd (A is untouched)\n", A->matrix_type == LIS_MATRIX_COO ? "COO" : "DNS");
+	if (lisi_format_one_rank(A->matrix_type))      /* (the reference splits both; what rests on the split -- lis_matrix_solve -- it has for neither COO nor the preconditioners here) */
+		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "lis_matrix_split: %s storage is not split by liblis_amd (A is untouched)\n", lisi_format_name(A->matrix_type));
 	LISCHK(lisp_fill_matrix(A));          /* the parts are built from the host arrays */
 	if (MDEV(A)->device_only) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "matrix lives in HBM only: split the host matrix before uploading\n");
 	if (A->matrix_type == LIS_MATRIX_BSR && A->bnr != A->bnc) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "split of non-square blocks is not implemented\n");   /* ref lis_matrix_bsr.c:1164 */

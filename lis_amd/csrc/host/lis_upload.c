@@ -13,14 +13,19 @@
  *             row[] non-decreasing: ptr[] from the row starts, col[] and value[] serve as index[] and value[] where they lie (d->row keeps the
  *             uploaded row[]); otherwise a stable grouping by row, after which the uploaded triplets are released
  *   DNS       value[np][n] column-major as the host holds it; the native kernel pair of kernels/dns.hip
+ *   VBR       row / col / ptr / bptr / bindex / value as the host holds them, checked in HBM before anything is launched on them (liship_vbr_check), plus the
+ *             block row of every row, made there (liship_vbr_block_rows); the native kernel of kernels/vbr.hip
  */
 #include <stdio.h>
 #include "lis_internal.h"
 
-/* what only the COO and DNS arms call is referenced weakly: tests/c/upload_cases.c links this file against stubs of the calls the six older formats make, and the
+/* what only the COO, DNS and VBR arms call is referenced weakly: tests/c/upload_cases.c links this file against stubs of the calls the six older formats make, and the
  * library always holds the real ones */
-extern LIS_INT lisi_coo_dns_one_rank(LIS_INT type) __attribute__((weak));
+extern LIS_INT lisi_one_rank_only(LIS_INT type) __attribute__((weak));
 extern int liship_coo_rows_f64(int n, int nnz, const int *row, const int *col, const double *value, int *ptr, int **index, double **out_value, void *stream) __attribute__((weak));
+extern int liship_vbr_check(int n, int np, int nnz, int nr, int nc, int bnnz, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex,
+                            int *flags_host, void *stream) __attribute__((weak));
+extern int liship_vbr_block_rows(int n, int nr, const int *row, int *brow, void *stream) __attribute__((weak));
 
 /* a fresh HBM array holding src[0 .. count), queued on the library's stream; the array is the caller's from the allocation on, whatever the copy answers */
 LIS_INT lisd_upload_i(int **dst, const int *src, size_t count)
@@ -480,6 +485,9 @@ static int host_arrays(LIS_MATRIX A, const void *arr[6], size_t bytes[6])
 	case LIS_MATRIX_BSR: ARR(A->bptr, 4 * ((size_t)A->nr + 1)); ARR(A->bindex, 4 * (size_t)A->bnnz); ARR(A->value, 8 * (size_t)A->bnnz * (size_t)A->bnr * (size_t)A->bnc); break;
 	case LIS_MATRIX_COO: ARR(A->row, 4 * (size_t)A->nnz); ARR(A->col, 4 * (size_t)A->nnz); ARR(A->value, 8 * (size_t)A->nnz); break;
 	case LIS_MATRIX_DNS: ARR(A->value, 8 * n * (size_t)A->np); break;
+	case LIS_MATRIX_VBR:
+		ARR(A->row, 4 * ((size_t)A->nr + 1)); ARR(A->col, 4 * ((size_t)A->nc + 1)); ARR(A->ptr, 4 * ((size_t)A->bnnz + 1));
+		ARR(A->bptr, 4 * ((size_t)A->nr + 1)); ARR(A->bindex, 4 * (size_t)A->bnnz); ARR(A->value, 8 * (size_t)A->nnz); break;
 	default: break;
 	}
 #undef ARR
@@ -515,6 +523,32 @@ static LIS_INT upload_coo_as_csr(LIS_MATRIX A, lisd_mat *d)
 	d->index = gidx; d->value = gval;
 	if (gidx == dcol) { d->row = drow; d->coo_in_order = 1; }
 	else { (void)liship_free(drow); (void)liship_free(dcol); (void)liship_free(dval); }
+	return LIS_SUCCESS;
+}
+
+/* VBR: the six arrays go up as they are.  One kernel then checks them -- the product's lanes take addresses from every one of them -- and a violation is
+ * LIS_ERR_ILL_ARG naming the array, with nothing launched on the arrays; then the block row of every row is made from the checked row[] */
+static LIS_INT upload_vbr(LIS_MATRIX A, lisd_mat *d)
+{
+	static const struct { int bit; const char *what; } bad[] = {
+		{LISHIP_VBR_BAD_ROW, "row[] must ascend strictly from 0 to n"}, {LISHIP_VBR_BAD_COL, "col[] must ascend strictly from 0 to np"},
+		{LISHIP_VBR_BAD_BPTR, "bptr[] must ascend from 0 to bnnz"}, {LISHIP_VBR_BAD_PTR, "ptr[] must ascend inside [0, nnz]"},
+		{LISHIP_VBR_BAD_BINDEX, "bindex[] holds a block column outside [0, nc)"}, {LISHIP_VBR_BAD_SIZE, "ptr[bc+1] - ptr[bc] is not the size of block bc"},
+	};
+	int flags = 0;
+	if (A->nnz < 0 || A->bnnz < 0 || A->nr < 1 || A->nc < 1) return LISI_ERR(LIS_ERR_ILL_ARG, "VBR matrix: nnz = %D, bnnz = %D, nr = %D, nc = %D\n", A->nnz, A->bnnz, A->nr, A->nc);
+	d->nr = A->nr; d->nc = A->nc;
+	LISCHK(lisd_upload_i(&d->row, A->row, (size_t)A->nr + 1));
+	LISCHK(lisd_upload_i(&d->col, A->col, (size_t)A->nc + 1));
+	LISCHK(lisd_upload_i(&d->ptr, A->ptr, (size_t)A->bnnz + 1));
+	LISCHK(lisd_upload_i(&d->bptr, A->bptr, (size_t)A->nr + 1));
+	LISCHK(lisd_upload_i(&d->bindex, A->bindex, (size_t)A->bnnz));
+	LISCHK(lisd_upload_d(&d->value, A->value, (size_t)A->nnz));
+	HIPCHK(liship_vbr_check(A->n, A->np, A->nnz, A->nr, A->nc, A->bnnz, d->row, d->col, d->ptr, d->bptr, d->bindex, &flags, lisg.stream));
+	for (size_t k = 0; k < sizeof(bad) / sizeof(bad[0]); k++)
+		if (flags & bad[k].bit) return LISI_ERR(LIS_ERR_ILL_ARG, "VBR matrix: %s (n = %D, np = %D, nr = %D, nc = %D, bnnz = %D, nnz = %D)\n", bad[k].what, A->n, A->np, A->nr, A->nc, A->bnnz, A->nnz);
+	HIPCHK(lisd_malloc((void **)&d->brow, sizeof(int) * ((size_t)A->n + 4)));
+	HIPCHK(liship_vbr_block_rows(A->n, A->nr, d->row, d->brow, lisg.stream));
 	return LIS_SUCCESS;
 }
 
@@ -596,15 +630,20 @@ static LIS_INT mat_upload(LIS_MATRIX A)
 		}
 		break;
 	case LIS_MATRIX_COO:
-		if (!lisi_coo_dns_one_rank || !liship_coo_rows_f64) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "COO storage: this build holds no row-form builder\n");
-		LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
+		if (!lisi_one_rank_only || !liship_coo_rows_f64) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "COO storage: this build holds no row-form builder\n");
+		LISCHK(lisi_one_rank_only(A->matrix_type));
 		LISCHK(upload_coo_as_csr(A, d));
 		d->type = LIS_MATRIX_CSR;
 		LISCHK(lisd_csr_plan(&d->plan, A->n, d->ptr, d->index, d->value));
 		break;
 	case LIS_MATRIX_DNS:
-		if (lisi_coo_dns_one_rank) LISCHK(lisi_coo_dns_one_rank(A->matrix_type));
+		if (lisi_one_rank_only) LISCHK(lisi_one_rank_only(A->matrix_type));
 		LISCHK(lisd_upload_d(&d->value, A->value, n * (size_t)A->np));
+		break;
+	case LIS_MATRIX_VBR:
+		if (!lisi_one_rank_only || !liship_vbr_check || !liship_vbr_block_rows) return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "VBR storage: this build holds no checking kernel\n");
+		LISCHK(lisi_one_rank_only(A->matrix_type));
+		LISCHK(upload_vbr(A, d));
 		break;
 	default:
 		return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "storage format %D is not served by liblis_amd\n", A->matrix_type);
@@ -628,6 +667,7 @@ void lisd_mat_free(LIS_MATRIX A)
 	(void)liship_free(d->t_ptr); (void)liship_free(d->t_index); (void)liship_free(d->t_value); (void)liship_free(d->wr); (void)liship_free(d->t_diag);
 	(void)liship_free(d->ell_codes); (void)liship_free(d->ell_dict);
 	(void)liship_free(d->ptr); (void)liship_free(d->index); (void)liship_free(d->row);
+	(void)liship_free(d->col); (void)liship_free(d->brow); (void)liship_free(d->t_borders);
 	(void)liship_free(d->bptr); (void)liship_free(d->bindex); (void)liship_free(d->value);
 	(void)liship_free(d->export_index); (void)liship_free(d->ws); free(d->export_run);
 	(void)liship_free(d->sx); (void)liship_free(d->sy);
@@ -636,8 +676,8 @@ void lisd_mat_free(LIS_MATRIX A)
 	lisp_matrix_release(A, 0);         /* no copy left that a host write could leave stale: the watched arrays are plain memory again */
 }
 
-/* ------------------------------------------------------------------ values edited in place (lis_matrix_shift_diagonal, lis_shift.c)
- * A kernel changed d->value of a CSR copy where it lies: everything derived from the old values goes -- the plan with its value records and its renumbered
+/* ------------------------------------------------------------------ values edited in place (lis_matrix_shift_diagonal, lis_shift.c; lis_matrix_scale of VBR, lis_scale.c)
+ * A kernel changed d->value of a CSR (or VBR) copy where it lies: everything derived from the old values goes -- the plan with its value records and its renumbered
  * form, the transposed copies in both numberings, what the preconditioners cached on the copy -- and the plan is made again from the HBM arrays, by the
  * call that made it at upload time (mat_upload / upload_split / lis_amd_matrix_set_csr_device).  The transposed copy and the caches come back on their
  * next use.  No matrix array crosses the bus. */
@@ -653,6 +693,10 @@ LIS_INT lisd_mat_values_changed(LIS_MATRIX A)
 	d->rt_ptr = NULL; d->rt_index = NULL; d->rt_value = NULL; d->rt_ready = 0; d->rt_nnz = 0;
 	lisi_precon_release(d, NULL, NULL);
 	d->reorder_tried = 0; d->served = 0;
+	if (d->type == LIS_MATRIX_VBR) {             /* (no plan: the VBR kernel reads value[] itself; the chunk borders of A^T x depend on row[] alone) */
+		HIPCHK(liship_stream_synchronize(lisg.stream));
+		return LIS_SUCCESS;
+	}
 	if (A->is_splited) {
 		LISCHK(lisd_csr_plan(&d->plan, d->n, d->ptr, d->index, d->value));
 		HIPCHK(liship_csr_plan_set_first_term_initialises(d->plan, 1));      /* (CSR chain rows: upload_rows, from_zero = 0) */

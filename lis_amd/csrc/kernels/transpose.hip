@@ -387,7 +387,40 @@ void spmv_t_chunked_unordered_kernel(int rows, int nsrc, int T, const int *__res
     }
     y[c] = total;
 }
+// The same sums for chunks that are not LIS_GET_ISIE of the source rows: chunk k owns the source rows borders[k] .. borders[k + 1] (T + 1 ascending ints in HBM).
+// lis_matvech_vbr's threads own chunks of BLOCK ROWS (src/matvec/lis_matvec_vbr.c:284-300): borders[k] = row[first block row of chunk k].  A transposed row lists
+// its terms block row after block row, so the chunk of its entries never decreases.
+__global__ __launch_bounds__(BLOCK)
+void spmv_t_bordered_kernel(int rows, int T, const int *__restrict__ borders, const int *__restrict__ tptr, const int *__restrict__ tidx,
+                            const double *__restrict__ tval, const double *__restrict__ x, double *__restrict__ y, const double *skip)
+{
+    if (skip && skip[0] != 0.0) return;
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= rows) return;
+    double total = 0.0, part = 0.0;
+    int chunk = 0;
+    for (int k = tptr[c]; k < tptr[c + 1]; k++) {
+        const int j = tidx[k];
+        if (j >= borders[chunk + 1]) {
+            total += part; part = 0.0;                       // (the chunks without entries in between add +0.0: nothing)
+            do chunk++; while (chunk < T - 1 && j >= borders[chunk + 1]);
+        }
+        part += tval[k] * x[j];
+    }
+    total += part;
+    y[c] = total;
+}
 } // namespace
+
+extern "C" int liship_spmv_csr_transposed_bordered_f64(int rows, int T, const int *borders, const int *tptr, const int *tidx, const double *tval,
+                                                       const double *x, double *y, void *stream)
+{
+    if (rows < 0 || T < 1 || !borders) return LISHIP_ERR_ARG;
+    if (rows == 0) return 0;
+    spmv_t_bordered_kernel<<<(rows + BLOCK - 1) / BLOCK, BLOCK, 0, as_stream(stream)>>>(rows, T, borders, tptr, tidx, tval, x, y, liship_internal_guard());
+    LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int liship_spmv_csr_transposed_chunked_unordered_f64(int rows, int nsrc, int T, const int *tptr, const int *tidx, const double *tval,
                                                                 const double *x, double *y, void *stream)
