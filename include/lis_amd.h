@@ -46,8 +46,13 @@ LIS_INT lis_amd_set_coherence(LIS_INT lazy);
 /* arrays of A (a matrix made by lis_matrix_convert in HBM) that no host access has asked for yet: they exist in HBM only (tests) */
 LIS_INT lis_amd_matrix_lazy_arrays(LIS_MATRIX A);
 /* lis_matrix_convert of a CSR matrix that lives in HBM builds ELL / DIA / CSC / BSR there (kernels/convert.hip: the reference's arrays, bit for
- * bit) and leaves the new matrix's host arrays to their first touch (1, default); 0 (env LIS_AMD_NO_DEVICE_CONVERT=1): always on the host arrays */
+ * bit) and leaves the new matrix's host arrays to their first touch (1, default); 0 (env LIS_AMD_NO_DEVICE_CONVERT=1): always on the host arrays.
+ * The way back -- ELL / DIA / BSR / DNS / VBR / CSC / JAD -> CSR -- is built in HBM as well, from wherever the source's arrays are (lis_convert_tocsr.c); a COO
+ * source is converted on the host, where the reference sorts it in place */
 LIS_INT lis_amd_set_device_convert(LIS_INT on);
+/* which way lis_matrix_convert went: out[0] = conversion steps served by kernels in HBM, out[1] = steps served by a host routine, since lis_initialize.  X -> Y between
+ * two formats that are not CSR is two steps (X -> CSR -> Y); a copy into the same format is none.  The switch above covers both directions: CSR -> X and X -> CSR */
+LIS_INT lis_amd_convert_stats(LIS_INT out[2]);
 LIS_INT lis_amd_vector_page_state(LIS_VECTOR v);
 LIS_INT lis_amd_vector_page_protect(LIS_VECTOR v, LIS_INT state);      /* force a protection (tests of the fault handler without a GPU) */
 LIS_INT lis_amd_page_faults(LIS_INT *reads, LIS_INT *writes);

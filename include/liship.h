@@ -701,6 +701,34 @@ int  liship_csr_to_jad(int n, const int *perm, const int *jptr, const int *ptr, 
  * zero-filled here, then every entry in stored order, so that a duplicate (i, j) leaves its last value (lis_matrix_dns.c:784-797) */
 int  liship_csr_to_coo(int n, const int *ptr, int *row, void *stream);
 int  liship_csr_to_dns_f64(int n, int np, const int *ptr, const int *index, const double *value, double *dns, void *stream);
+/* ---- the way back: CSR rows from an ELL, DIA, BSR, DNS or VBR matrix that lives in HBM (kernels/convert.hip), the arrays of lis_matrix_convert_<fmt>2csr bit for
+ * bit.  A row lists its stored entries in the source's own order -- ELL: slots j = 0 .. maxnzr-1 of value[j*n+i]; DIA: diagonals d = 0 .. nnd-1 with
+ * 0 <= i + offsets[d] < ncols; BSR: the block row's blocks in stored order, columns ascending inside a block, padding columns left out; DNS: j = 0 .. np-1 of
+ * value[j*n+i]; VBR: blocks in stored order, columns ascending inside a block -- and leaves out every entry with value == 0.0 (the C comparison: +0.0 and -0.0 go,
+ * NaN, infinities and subnormals stay).  Values are copied, never computed with; offsets into the source are 64-bit.
+ *   liship_<fmt>_csr_count  count[i] = kept entries of row i (n ints), rptr[0 .. n] = their exclusive scan (rptr[n] = the total, in HBM), *nnz = the total on the
+ *                           host; scratch: (n / 4096 + 2) long long.  LISHIP_ERR_OVERFLOW when the total does not fit an int (rptr is then not to be read).
+ *                           Synchronizes the stream.
+ *   liship_<fmt>_to_csr     rindex[] / rvalue[] (*nnz entries each) from that rptr; a lane writes inside [rptr[i], rptr[i+1]) only
+ * DNS cuts every row into slabs of info[1] columns: count[] holds n * nslab ints (nslab = ceil(np / info[1])), offsets[] their scan (n * nslab + 1 ints, row i's
+ * slabs one after another), scratch (n * nslab / 4096 + 2) long long; the fill entry reads offsets[].  VBR takes arrays that passed liship_vbr_check and the
+ * brow[] of liship_vbr_block_rows.  liship_tocsr_tile_info: {rows per workgroup, columns per DNS slab, counts per scan tile} -- ONE entry for the five families:
+ * they share the workgroup of 256 rows and the scan, and the slab is the only figure that belongs to one of them. */
+#define LISHIP_ERR_OVERFLOW (-3)
+int  liship_tocsr_tile_info(int info[3]);
+int  liship_ell_csr_count(int n, int maxnzr, const double *value, int *count, int *rptr, long long *scratch, int *nnz, void *stream);
+int  liship_ell_to_csr(int n, int maxnzr, const int *index, const double *value, const int *rptr, int *rindex, double *rvalue, void *stream);
+int  liship_dia_csr_count(int n, int ncols, int nnd, const int *offsets, const double *value, int *count, int *rptr, long long *scratch, int *nnz, void *stream);
+int  liship_dia_to_csr(int n, int ncols, int nnd, const int *offsets, const double *value, const int *rptr, int *rindex, double *rvalue, void *stream);
+int  liship_bsr_csr_count(int n, int bnr, int bnc, const int *bptr, const int *bindex, const double *value, int *count, int *rptr, long long *scratch,
+                          int *nnz, void *stream);
+int  liship_bsr_to_csr(int n, int bnr, int bnc, const int *bptr, const int *bindex, const double *value, const int *rptr, int *rindex, double *rvalue, void *stream);
+int  liship_dns_csr_count(int n, int np, const double *value, int *count, int *offsets, int *rptr, long long *scratch, int *nnz, void *stream);
+int  liship_dns_to_csr(int n, int np, const double *value, const int *offsets, int *rindex, double *rvalue, void *stream);
+int  liship_vbr_csr_count(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, const double *value,
+                          int *count, int *rptr, long long *scratch, int *nnz, void *stream);
+int  liship_vbr_to_csr(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, const double *value,
+                       const int *rptr, int *rindex, double *rvalue, void *stream);
 /* reverse halo: y[export_index[i]] += wr[i], indices unique within one call  (lis_reduce, lis_matrix_mpi.c:988-996) */
 int  liship_scatter_add_f64(int count, const int *export_index, const double *wr, double *y, void *stream);
 

@@ -230,6 +230,17 @@ _LISHIP = {
     "liship_vbr_scale_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),
     "liship_csr_to_coo": (_ci, [_ci, _vp, _vp, _vp]),
     "liship_csr_to_dns_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "liship_tocsr_tile_info": (_ci, [C.POINTER(_ci)]),
+    "liship_ell_csr_count": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_ell_to_csr": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_dia_csr_count": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_dia_to_csr": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_bsr_csr_count": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_bsr_to_csr": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_dns_csr_count": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_dns_to_csr": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "liship_vbr_csr_count": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_ci), _vp]),
+    "liship_vbr_to_csr": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_gather_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_scatter_add_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
     "liship_poisson3d_nnz": (C.c_longlong, [_ci, _ci, _ci, _ci, _ci]),

@@ -301,6 +301,7 @@ _AMD_PROTOS = {
     "lis_amd_is_psolve": (LIS_INT, [PM, C.c_double, LIS_INT, PV, PV, LIS_INT]),
     "lis_amd_last_solve_is": (LIS_INT, [P_INT]),
     "lis_amd_last_shift_matrix": (LIS_INT, [P_INT]),
+    "lis_amd_convert_stats": (LIS_INT, [P_INT]),
     "lis_amd_matrix_device_csr": (LIS_INT, [PM, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
 }
 

@@ -727,6 +727,31 @@ LIS_INT lis_matrix_convert(LIS_MATRIX Ain, LIS_MATRIX Aout)
 	return LIS_SUCCESS;
 }
 
+/* the two halves of every conversion: in HBM where a gate takes the case (lis_convert_hbm.c: CSR -> X from the source's copy; lis_convert_tocsr.c: X -> CSR from
+ * wherever the source's arrays are), else by the host routines above, which read the source's host arrays from several threads: those come home first.
+ * lis_amd_convert_stats counts which way each half went.  (COO -> CSR is the host routine's alone: it sorts the source in place, as the reference does.) */
+static LIS_INT from_csr(LIS_MATRIX Ain, LIS_MATRIX Aout)
+{
+	int done = 0;
+	LISCHK(lisd_convert_csr(Ain, Aout, &done));
+	if (done) { lisg.converted_in_hbm++; return LIS_SUCCESS; }
+	LISCHK(lisp_fill_matrix(Ain));
+	LISCHK(lisi_convert_csr_to(Ain, Aout));
+	lisg.converted_on_host++;
+	return LIS_SUCCESS;
+}
+
+static LIS_INT to_csr(LIS_MATRIX Ain, LIS_MATRIX Aout)
+{
+	int done = 0;
+	LISCHK(lisd_convert_to_csr(Ain, Aout, &done));
+	if (done) { lisg.converted_in_hbm++; return LIS_SUCCESS; }
+	LISCHK(lisp_fill_matrix(Ain));
+	LISCHK(lisi_convert_to_csr(Ain, Aout));
+	lisg.converted_on_host++;
+	return LIS_SUCCESS;
+}
+
 static LIS_INT convert_impl(LIS_MATRIX Ain, LIS_MATRIX Aout)
 {
 	LISCHK(lisi_matrix_check(Ain, LISI_CHECK_ASSEMBLED));
@@ -738,30 +763,24 @@ static LIS_INT convert_impl(LIS_MATRIX Ain, LIS_MATRIX Aout)
 		                                        * block rows of more than 96 blocks) runs on a host copy of the arrays, made for this conversion */
 		int done = 0;
 		if (Ain->matrix_type == LIS_MATRIX_CSR && want != LIS_MATRIX_CSR) LISCHK(lisd_convert_csr(Ain, Aout, &done));
-		if (done) return LIS_SUCCESS;
+		if (done) { lisg.converted_in_hbm++; return LIS_SUCCESS; }
 		if (Ain->matrix_type != LIS_MATRIX_CSR || want == LIS_MATRIX_CSR)
 			return LISI_ERR(LIS_ERR_NOT_IMPLEMENTED, "matrix lives in HBM only: this conversion runs on host arrays -- convert the host matrix before uploading\n");
 		LIS_MATRIX home;
 		LISCHK(lisd_csr_home(Ain, &home));
 		LIS_INT err = lisi_convert_csr_to(home, Aout);
 		lis_matrix_destroy(home);
+		if (!err) lisg.converted_on_host++;
 		return err;
 	}
 	LISCHK(lis_matrix_merge(Ain));         /* ref lis_matrix_ops.c:142: a split input is merged first */
 	if (Ain->matrix_type == want && !Ain->is_block) { LISCHK(lisp_fill_matrix(Ain)); return lisi_matrix_deep_copy(Ain, Aout); }
-	if (Ain->matrix_type == LIS_MATRIX_CSR) {
-		int done = 0;                          /* in HBM when Ain lives there (lis_convert_hbm.c), else on the host arrays */
-		LISCHK(lisd_convert_csr(Ain, Aout, &done));
-		if (done) return LIS_SUCCESS;
-		LISCHK(lisp_fill_matrix(Ain));
-		return lisi_convert_csr_to(Ain, Aout);
-	}
-	LISCHK(lisp_fill_matrix(Ain));         /* the host routines below read Ain's arrays from several threads: they come home first */
-	if (want == LIS_MATRIX_CSR) return lisi_convert_to_csr(Ain, Aout);
-	LIS_MATRIX tmp;                                            /* X -> CSR -> Y */
+	if (Ain->matrix_type == LIS_MATRIX_CSR) return from_csr(Ain, Aout);
+	if (want == LIS_MATRIX_CSR) return to_csr(Ain, Aout);
+	LIS_MATRIX tmp;                                            /* X -> CSR -> Y: the CSR matrix in the middle stays in HBM when both halves are built there */
 	LISCHK(lis_matrix_duplicate(Ain, &tmp));
-	LIS_INT err = lisi_convert_to_csr(Ain, tmp);
-	if (!err) err = lisi_convert_csr_to(tmp, Aout);
+	LIS_INT err = to_csr(Ain, tmp);
+	if (!err) err = from_csr(tmp, Aout);
 	lis_matrix_destroy(tmp);
 	return err;
 }

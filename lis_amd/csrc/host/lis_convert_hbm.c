@@ -334,17 +334,50 @@ LIS_INT lisd_convert_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done)
 		drop_target(c.d);
 		return err;
 	}
-	/* the tail: Aout's header holds its arrays from here on, so a failure takes the storage down with the copy */
-	rc = liship_stream_synchronize(lisg.stream);
-	if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
-	else {
-		c.d->inner_begin = 0; c.d->inner_end = c.n;
-		c.d->ready = 1;                                    /* the HBM copy exists: lis_matrix_assemble's eager upload finds nothing to do */
-		err = lis_matrix_assemble(Aout);
-	}
-	if (err) { lisi_matrix_storage_destroy(Aout); return err; }
+	LISCHK(lisd_convert_tail(Aout, c.d, c.n));
 	*done = 1;
 	return LIS_SUCCESS;
+}
+
+/* the tail of this gate and of lisd_convert_to_csr (lis_convert_tocsr.c): Aout's header holds its arrays from here on, so a failure takes the storage down with the copy */
+LIS_INT lisd_convert_tail(LIS_MATRIX Aout, lisd_mat *d, int n)
+{
+	LIS_INT err;
+	const int rc = liship_stream_synchronize(lisg.stream);
+	if (rc) err = lisi_hip_error(__FILE__, __func__, __LINE__, rc);
+	else {
+		d->inner_begin = 0; d->inner_end = n;
+		d->ready = 1;                                      /* the HBM copy exists: lis_matrix_assemble's eager upload finds nothing to do */
+		err = lis_matrix_assemble(Aout);
+	}
+	if (err) lisi_matrix_storage_destroy(Aout);
+	return err;
+}
+
+/* the same for a CSR target (lis_convert_tocsr.c), with what comes before it: the three buffers become Aout's HBM copy with their plan, Aout's host arrays are bound
+ * to them (lazy_bind, not owning), lis_matrix_set_csr, then the tail above.  The buffers are taken whatever happens: after a failure they are freed with the copy */
+LIS_INT lisd_convert_adopt_csr(LIS_MATRIX Aout, int n, int np, int nnz, int *ptr, int *index, double *value)
+{
+	conv_t c = { .Aout = Aout, .d = MDEV(Aout), .n = n, .np = np, .nnz = nnz };
+	lisd_mat *d = c.d;
+	memset(d, 0, sizeof(*d));
+	d->n = n; d->np = np; d->nnz = nnz; d->type = LIS_MATRIX_CSR;
+	d->ptr = ptr; d->index = index; d->value = value;
+	LIS_INT err = lisd_csr_plan_cols(&d->plan, n, np, ptr, index, value);
+	if (!err) err = lazy_bind(&c, sizeof(int) * ((size_t)n + 1), ptr, 0);
+	if (!err) err = lazy_bind(&c, sizeof(int) * (size_t)nnz, index, 0);
+	if (!err) err = lazy_bind(&c, sizeof(double) * (size_t)nnz, value, 0);
+	if (!err) {
+		Aout->pad = 0; Aout->pad_comm = 0;                      /* as lisi_convert_to_csr: a CSR matrix has no padding, whatever the (duplicated) tables of a BSR source said */
+		if (Aout->commtable) Aout->commtable->pad = 0;
+		err = lis_matrix_set_csr(nnz, (LIS_INT *)c.lazy[0], (LIS_INT *)c.lazy[1], (LIS_SCALAR *)c.lazy[2], Aout);
+	}
+	if (err) {
+		while (c.nlazy > 0) (void)lisp_free_array(c.lazy[--c.nlazy]);
+		drop_target(d);
+		return err;
+	}
+	return lisd_convert_tail(Aout, d, n);
 }
 
 /* A host copy of a CSR matrix that lives in HBM only (lis_amd_matrix_set_csr_device / lis_amd_matrix_poisson3d): what lis_matrix_convert hands to the host routines

@@ -207,6 +207,7 @@ typedef struct {
 	int last_ssor_bn;                                                                                  /* lis_amd_last_solve_ssor_block: 1 for the point form, bn for block sweeps */
 	int last_sainv, last_sainv_wnnz, last_sainv_znnz, last_sainv_blocks;                               /* lis_amd_last_solve_sainv */
 	int last_is, last_is_m;                                                                            /* lis_amd_last_solve_is */
+	long long converted_in_hbm, converted_on_host;                                                     /* lis_amd_convert_stats: steps of lis_matrix_convert served by kernels / by a host routine since lis_initialize */
 	long long sainv_builds;                                                                            /* host builds of a SAINV factor since lis_initialize (lis_amd_sainv_info) */
 } lisi_globals;
 extern lisi_globals lisg;
@@ -227,6 +228,7 @@ void *lisp_alloc_lazy(void *matrix, size_t bytes_used, void *dev, int own_dev); 
 int  lisp_free_array(void *p);                                /* 1: p lived on such pages (unmapped), 0: plain memory (caller frees) */
 LIS_INT lisp_fill_matrix(void *matrix);
 int  lisp_lazy_arrays(void *matrix);
+void *lisp_lazy_device(const void *array);                    /* the device buffer behind a host array still held in HBM only, else NULL */
 void lisp_reown(void *from, void *to);
 void *lisp_alloc_tracked(size_t bytes_used);                  /* an array of lis_matrix_malloc_<fmt>: pages whose writes are seen once a matrix adopted and uploaded it */
 int  lisp_adopt(void *matrix, void *array);
@@ -390,6 +392,9 @@ LIS_INT lisi_convert_csr_to(LIS_MATRIX Ain, LIS_MATRIX Aout);  /* Aout->matrix_t
 LIS_INT lisi_convert_to_csr(LIS_MATRIX Ain, LIS_MATRIX Aout);
 LIS_INT lisi_jad_order(LIS_MATRIX A, LIS_INT *maxnzr, LIS_INT **perm, LIS_INT **ptr);      /* the reference's length-sorted row order + jagged-diagonal starts */
 LIS_INT lisd_convert_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done);   /* csr -> ell / dia / csc / jad / bsr in HBM when Ain lives there (lis_convert_hbm.c) */
+LIS_INT lisd_convert_tail(LIS_MATRIX Aout, lisd_mat *d, int n);        /* the end of both gates: the stream drained, the copy declared built, lis_matrix_assemble (lis_convert_hbm.c) */
+LIS_INT lisd_convert_adopt_csr(LIS_MATRIX Aout, int n, int np, int nnz, int *ptr, int *index, double *value);   /* three HBM buffers become the CSR matrix Aout: copy, plan, lazy host arrays, set_csr, the tail */
+LIS_INT lisd_convert_to_csr(LIS_MATRIX Ain, LIS_MATRIX Aout, int *done); /* ell / dia / bsr / dns / vbr / csc / jad -> csr in HBM, the source's arrays staying where they are (lis_convert_tocsr.c) */
 LIS_INT lisd_csr_home(LIS_MATRIX Ain, LIS_MATRIX *home);               /* a host copy of a CSR matrix born in HBM, for the conversions the host routines serve (lis_convert_hbm.c) */
 LIS_INT lisi_matrix_deep_copy(LIS_MATRIX Ain, LIS_MATRIX Aout);
 

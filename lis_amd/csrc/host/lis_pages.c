@@ -523,6 +523,21 @@ int lisp_lazy_arrays(void *matrix)
 	return c;
 }
 
+/* the device buffer behind a host array that is still held in HBM only (NULL: the array is at home, or no array of the library's).  For readers that work in HBM
+ * themselves (lis_convert_tocsr.c): the array stays where it is.  The pointer is good only while no other thread touches that host array: a first touch fills
+ * the pages and, where the pages own the buffer (the native arrays behind a row-form copy), frees it (region_fill) -- the lock is not held past this call.  As
+ * everywhere in this library, one matrix is not to be used from two threads at once; a conversion of X must not race a program thread that reads X's arrays */
+void *lisp_lazy_device(const void *array)
+{
+	void *dev = NULL;
+	if (!array) return NULL;
+	pthread_mutex_lock(&region_lock);
+	lisp_region *r = region_at(array);
+	if (r && !r->owner && !r->filling && r->prot == LISP_NONE) dev = r->dev;
+	pthread_mutex_unlock(&region_lock);
+	return dev;
+}
+
 /* value[] grows to `doubles` entries (old contents kept, new entries zero), whatever memory it lived in; the caller made it current */
 LIS_INT lisp_grow(LIS_VECTOR v, size_t doubles)
 {
@@ -602,6 +617,12 @@ LIS_INT lis_amd_set_coherence(LIS_INT lazy)
 LIS_INT lis_amd_matrix_lazy_arrays(LIS_MATRIX A) { return lisp_lazy_arrays(A); }
 LIS_INT lis_amd_matrix_protected_arrays(LIS_MATRIX A) { return lisp_protected_arrays(A); }
 LIS_INT lis_amd_set_device_convert(LIS_INT on) { lisg.no_device_convert = on ? 0 : 1; return LIS_SUCCESS; }
+LIS_INT lis_amd_convert_stats(LIS_INT out[2])
+{
+	if (!out) return LISI_ERR(LIS_ERR_ILL_ARG, "out is NULL\n");
+	out[0] = (LIS_INT)lisg.converted_in_hbm; out[1] = (LIS_INT)lisg.converted_on_host;
+	return LIS_SUCCESS;
+}
 LIS_INT lis_amd_vector_page_state(LIS_VECTOR v) { return lisp_state(v); }
 LIS_INT lis_amd_vector_page_protect(LIS_VECTOR v, LIS_INT state) { lisp_protect(v, (int)state); return lisp_state(v) == (int)state ? LIS_SUCCESS : LIS_ERR_ILL_ARG; }
 

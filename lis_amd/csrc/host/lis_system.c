@@ -278,6 +278,7 @@ LIS_INT lis_initialize(int *argc, char **argv[])
 		lisg.no_value_records = (r && r[0] == '1');
 		r = getenv("LIS_AMD_NO_DEVICE_CONVERT");
 		lisg.no_device_convert = (r && r[0] == '1');
+		lisg.converted_in_hbm = 0; lisg.converted_on_host = 0;
 		r = getenv("LIS_AMD_NO_ROW_FORM");
 		lisg.no_row_form = (r && r[0] == '1');
 		r = getenv("LIS_AMD_NO_UNIFORM_JACOBI");

@@ -148,16 +148,24 @@ void csr_to_dia(int n, const int *__restrict__ ptr, const int *__restrict__ idx,
     if (i >= n) return;
     for (int k = ptr[i]; k < ptr[i + 1]; k++) dval[(size_t)slot[idx[k] - i + n] * n + i] = val[k];
 }
-// row form: the diagonals that reach row i (0 <= i + offset < ncols), ascending, explicit zeros included (lis_matvec_dia.c:154-160)
+// row form: the diagonals that reach row i (0 <= i + offset < ncols), ascending, explicit zeros included (lis_matvec_dia.c:154-160).
+// FILTER: the rows of lis_matrix_convert_dia2csr instead -- the same walk, entries with value == 0.0 left out (dval is read by the count too)
+template <bool FILTER>
 __global__ __launch_bounds__(BLOCK)
-void dia_row_counts(int n, int ncols, int nnd, const int *__restrict__ offs, int *__restrict__ count)
+void dia_row_counts(int n, int ncols, int nnd, const int *__restrict__ offs, const double *__restrict__ dval, int *__restrict__ count)
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     int c = 0;
-    for (int d = 0; d < nnd; d++) { const long long j = (long long)i + offs[d]; c += (j >= 0 && j < ncols); }
+    for (int d = 0; d < nnd; d++) {
+        const long long j = (long long)i + offs[d];
+        if (j < 0 || j >= ncols) continue;
+        if (FILTER && !(dval[(size_t)d * n + i] != 0.0)) continue;
+        c++;
+    }
     count[i] = c;
 }
+template <bool FILTER>
 __global__ __launch_bounds__(BLOCK)
 void dia_to_rows(int n, int ncols, int nnd, const int *__restrict__ offs, const double *__restrict__ dval,
                  const int *__restrict__ rptr, int *__restrict__ ridx, double *__restrict__ rval)
@@ -165,9 +173,13 @@ void dia_to_rows(int n, int ncols, int nnd, const int *__restrict__ offs, const 
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     int at = rptr[i];
+    const int end = FILTER ? rptr[i + 1] : 0x7fffffff;      // (a filtered row never writes past the range its count gave it, whatever happened to dval since)
     for (int d = 0; d < nnd; d++) {
         const long long j = (long long)i + offs[d];
-        if (j >= 0 && j < ncols) { ridx[at] = (int)j; rval[at] = dval[(size_t)d * n + i]; at++; }
+        if (j < 0 || j >= ncols) continue;
+        const double v = dval[(size_t)d * n + i];
+        if (FILTER && (!(v != 0.0) || at >= end)) continue;
+        ridx[at] = (int)j; rval[at] = v; at++;
     }
 }
 
@@ -243,6 +255,30 @@ namespace {
 // the row form of a BSR matrix: scalar row r = bi * bnr + i lists, block after block of block row bi and column after column of the block, the terms
 // lis_matvec_bsr adds to y[r] -- value[bc * bs + j * bnr + i] * x[bindex[bc] * bnc + j], explicit zeros included -- in that order (src/matvec/
 // lis_matvec_bsr.c:57-150 generic, :293-343 2x2 ...).  Rows of one block row have the same length, so rptr is a closed form of bptr.
+// the walk of scalar row i of block row bi, shared with the filtered rows of lis_matrix_convert_bsr2csr below.  FILTER: value == 0.0 and the padding columns
+// are left out (lis_matrix_bsr.c convert loop; the column rule of lis_convert.c), WRITE: the entries go to ridx / rval from `at` on, never at or past `end`.  Returns the next free slot
+template <bool FILTER, bool WRITE>
+__device__ __forceinline__ int bsr_walk_row(int n, int bnr, int bnc, int pad, int i, int b0, int nbk, const int *__restrict__ bidx, const double *__restrict__ val,
+                                            int at, int end, int *__restrict__ ridx, double *__restrict__ rval)
+{
+    const size_t bs = (size_t)bnr * (size_t)bnc;
+    for (int bc = b0; bc < b0 + nbk; bc++) {
+        const int c0 = bidx[bc] * bnc;
+        for (int j = 0; j < bnc; j++) {
+            int col = c0 + j;
+            double v = 0.0;
+            if (FILTER || WRITE) v = val[(size_t)bc * bs + (size_t)j * bnr + i];
+            if (FILTER) {
+                if (!(v != 0.0)) continue;
+                if (col >= n + pad) col -= pad; else if (col >= n) continue;
+                if (WRITE && at >= end) continue;
+            }
+            if (WRITE) { ridx[at] = col; rval[at] = v; }
+            at++;
+        }
+    }
+    return at;
+}
 __global__ __launch_bounds__(BLOCK)
 void bsr_to_rows(int n, int bnr, int bnc, const int *__restrict__ bptr, const int *__restrict__ bidx, const double *__restrict__ val,
                  int *__restrict__ rptr, int *__restrict__ ridx, double *__restrict__ rval)
@@ -255,13 +291,10 @@ void bsr_to_rows(int n, int bnr, int bnc, const int *__restrict__ bptr, const in
         return;
     }
     const int bi = (int)(r / bnr), i = (int)(r - (long long)bi * bnr);
-    const int b0 = bptr[bi], nbk = bptr[bi + 1] - b0, bs = bnr * bnc;
-    int at = bnc * (bnr * b0 + i * nbk);
+    const int b0 = bptr[bi], nbk = bptr[bi + 1] - b0;
+    const int at = bnc * (bnr * b0 + i * nbk);
     rptr[r] = at;
-    for (int bc = b0; bc < b0 + nbk; bc++) {
-        const int c0 = bidx[bc] * bnc;
-        for (int j = 0; j < bnc; j++, at++) { ridx[at] = c0 + j; rval[at] = val[(size_t)bc * bs + (size_t)j * bnr + i]; }
-    }
+    (void)bsr_walk_row<false, true>(n, bnr, bnc, 0, i, b0, nbk, bidx, val, at, 0x7fffffff, ridx, rval);
 }
 } // namespace
 
@@ -316,7 +349,7 @@ extern "C" int liship_csr_to_dia(int n, int ncols, int nnd, const int *ptr, cons
 extern "C" int liship_dia_row_counts(int n, int ncols, int nnd, const int *offs, int *count, int *rptr, long long *scratch, int *rnnz, void *stream)
 {
     hipStream_t st = as_stream(stream);
-    if (n > 0) { dia_row_counts<<<grid_for(n), BLOCK, 0, st>>>(n, ncols, nnd, offs, count); LAUNCH_CHECK(); }
+    if (n > 0) { dia_row_counts<false><<<grid_for(n), BLOCK, 0, st>>>(n, ncols, nnd, offs, nullptr, count); LAUNCH_CHECK(); }
     const int rc = exclusive_scan(n, count, rptr, scratch, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rnnz, rptr + n, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -325,7 +358,7 @@ extern "C" int liship_dia_row_counts(int n, int ncols, int nnd, const int *offs,
 }
 extern "C" int liship_dia_to_rows(int n, int ncols, int nnd, const int *offs, const double *dval, const int *rptr, int *ridx, double *rval, void *stream)
 {
-    if (n > 0) { dia_to_rows<<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, ncols, nnd, offs, dval, rptr, ridx, rval); LAUNCH_CHECK(); }
+    if (n > 0) { dia_to_rows<false><<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, ncols, nnd, offs, dval, rptr, ridx, rval); LAUNCH_CHECK(); }
     return 0;
 }
 
@@ -404,6 +437,210 @@ extern "C" int liship_csr_to_dns_f64(int n, int np, const int *ptr, const int *i
     if (n == 0 || np == 0) return 0;
     HIP_TRY(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n * (size_t)np, as_stream(stream)));
     csr_to_dns<<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, np, ptr, idx, val, dns);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- X -> CSR for a source that lives in HBM: the rows of lis_matrix_convert_{ell,dia,bsr,dns,vbr}2csr (lis_convert.c lisi_convert_to_csr restates them).  Every
+// source yields, row by row, its stored entries in one fixed order with value == 0.0 (the C comparison: both zeros go, NaN, infinities and subnormals stay) left
+// out.  A count entry and a fill entry per source, one lane per row (ELL, DIA and DNS are column-major: the lanes of a wavefront read consecutive addresses);
+// DNS cuts its rows into slabs of columns, counted per (row, slab) and scanned in row-major order, so that a matrix of a few thousand rows still fills the device.
+// No arithmetic: values are loaded and stored.  Offsets into the sources are 64-bit.  A fill lane writes inside [ptr[i], ptr[i+1]) only.
+namespace {
+constexpr int TOCSR_SLAB = 64;        // columns of a DNS slab
+
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK)
+void ell_to_csr(int n, int maxnzr, const int *__restrict__ eidx, const double *__restrict__ eval, int *__restrict__ count,
+                const int *__restrict__ rptr, int *__restrict__ ridx, double *__restrict__ rval)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    int at = WRITE ? rptr[i] : 0;
+    const int end = WRITE ? rptr[i + 1] : 0;
+    for (int j = 0; j < maxnzr; j++) {
+        const size_t k = (size_t)j * (size_t)n + (size_t)i;
+        const double v = eval[k];
+        if (!(v != 0.0)) continue;
+        if (WRITE) { if (at < end) { ridx[at] = eidx[k]; rval[at] = v; } }
+        at++;
+    }
+    if (!WRITE) count[i] = at;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK)
+void bsr_to_csr(int n, int bnr, int bnc, int pad, const int *__restrict__ bptr, const int *__restrict__ bidx, const double *__restrict__ val,
+                int *__restrict__ count, const int *__restrict__ rptr, int *__restrict__ ridx, double *__restrict__ rval)
+{
+    const int r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= n) return;
+    const int bi = r / bnr, i = r - bi * bnr, b0 = bptr[bi], nbk = bptr[bi + 1] - b0;
+    if (WRITE) (void)bsr_walk_row<true, true>(n, bnr, bnc, pad, i, b0, nbk, bidx, val, rptr[r], rptr[r + 1], ridx, rval);
+    else count[r] = bsr_walk_row<true, false>(n, bnr, bnc, pad, i, b0, nbk, bidx, val, 0, 0, nullptr, nullptr);
+}
+
+// (row i, slab s) = columns s * SLAB .. of row i; its count / offset sits at [i * nslab + s], so the scan of the counts lists a row's slabs one after another
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK)
+void dns_to_csr(int n, int np, int nslab, const double *__restrict__ dns, int *__restrict__ count, const int *__restrict__ off,
+                int *__restrict__ ridx, double *__restrict__ rval)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x, s = blockIdx.y;
+    if (i >= n) return;
+    const size_t cell = (size_t)i * (size_t)nslab + (size_t)s;
+    const int j0 = s * TOCSR_SLAB, j1 = min(np, j0 + TOCSR_SLAB);
+    int at = WRITE ? off[cell] : 0;
+    const int end = WRITE ? off[cell + 1] : 0;
+    for (int j = j0; j < j1; j++) {
+        const double v = dns[(size_t)j * (size_t)n + (size_t)i];
+        if (!(v != 0.0)) continue;
+        if (WRITE) { if (at < end) { ridx[at] = j; rval[at] = v; } }
+        at++;
+    }
+    if (!WRITE) count[cell] = at;
+}
+__global__ __launch_bounds__(BLOCK)
+void dns_row_starts(int n, int nslab, const int *__restrict__ off, int *__restrict__ rptr)
+{
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i <= n) rptr[i] = off[(size_t)i * (size_t)nslab];
+}
+
+// brow[i]: the block row of row i (liship_vbr_block_rows); the arrays have passed liship_vbr_check
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK)
+void vbr_to_csr(int n, const int *__restrict__ row, const int *__restrict__ col, const int *__restrict__ ptr, const int *__restrict__ bptr,
+                const int *__restrict__ bindex, const int *__restrict__ brow, const double *__restrict__ val, int *__restrict__ count,
+                const int *__restrict__ rptr, int *__restrict__ ridx, double *__restrict__ rval)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int bi = brow[i], l = row[bi], bnr = row[bi + 1] - l, ii = i - l;
+    int at = WRITE ? rptr[i] : 0;
+    const int end = WRITE ? rptr[i + 1] : 0;
+    for (int bj = bptr[bi]; bj < bptr[bi + 1]; bj++) {
+        const int bc = bindex[bj], c0 = col[bc], bnc = col[bc + 1] - c0;
+        const size_t base = (size_t)ptr[bj] + (size_t)ii;
+        for (int j = 0; j < bnc; j++) {
+            const double v = val[base + (size_t)j * (size_t)bnr];
+            if (!(v != 0.0)) continue;
+            if (WRITE) { if (at < end) { ridx[at] = c0 + j; rval[at] = v; } }
+            at++;
+        }
+    }
+    if (!WRITE) count[i] = at;
+}
+
+// the tail of every count entry: rptr[0 .. m] = exclusive scan of count[0 .. m), the 64-bit total to the host (the scan keeps it behind its tile offsets)
+int tocsr_scan(int m, const int *count, int *rptr, long long *scratch, int *nnz, hipStream_t st)
+{
+    const int rc = exclusive_scan(m, count, rptr, scratch, st);
+    if (rc) return rc;
+    long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, scratch + (m + TILE - 1) / TILE, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (total > 0x7fffffffLL) return LISHIP_ERR_OVERFLOW;
+    *nnz = (int)total;
+    return 0;
+}
+} // namespace
+
+extern "C" int liship_tocsr_tile_info(int info[3])
+{
+    if (!info) return LISHIP_ERR_ARG;
+    info[0] = BLOCK; info[1] = TOCSR_SLAB; info[2] = TILE;
+    return 0;
+}
+
+extern "C" int liship_ell_csr_count(int n, int maxnzr, const double *value, int *count, int *rptr, long long *scratch, int *nnz, void *stream)
+{
+    if (n <= 0 || maxnzr < 0 || !value || !count || !rptr || !scratch || !nnz) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    ell_to_csr<false><<<grid_for(n), BLOCK, 0, st>>>(n, maxnzr, nullptr, value, count, nullptr, nullptr, nullptr);
+    LAUNCH_CHECK();
+    return tocsr_scan(n, count, rptr, scratch, nnz, st);
+}
+extern "C" int liship_ell_to_csr(int n, int maxnzr, const int *index, const double *value, const int *rptr, int *rindex, double *rvalue, void *stream)
+{
+    if (n <= 0 || maxnzr < 0 || !index || !value || !rptr || !rindex || !rvalue) return LISHIP_ERR_ARG;
+    ell_to_csr<true><<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, maxnzr, index, value, nullptr, rptr, rindex, rvalue);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int liship_dia_csr_count(int n, int ncols, int nnd, const int *offsets, const double *value, int *count, int *rptr, long long *scratch, int *nnz, void *stream)
+{
+    if (n <= 0 || ncols <= 0 || nnd < 0 || !offsets || !value || !count || !rptr || !scratch || !nnz) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    dia_row_counts<true><<<grid_for(n), BLOCK, 0, st>>>(n, ncols, nnd, offsets, value, count);
+    LAUNCH_CHECK();
+    return tocsr_scan(n, count, rptr, scratch, nnz, st);
+}
+extern "C" int liship_dia_to_csr(int n, int ncols, int nnd, const int *offsets, const double *value, const int *rptr, int *rindex, double *rvalue, void *stream)
+{
+    if (n <= 0 || ncols <= 0 || nnd < 0 || !offsets || !value || !rptr || !rindex || !rvalue) return LISHIP_ERR_ARG;
+    dia_to_rows<true><<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, ncols, nnd, offsets, value, rptr, rindex, rvalue);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int liship_bsr_csr_count(int n, int bnr, int bnc, const int *bptr, const int *bindex, const double *value, int *count, int *rptr, long long *scratch,
+                                    int *nnz, void *stream)
+{
+    if (n <= 0 || bnr < 1 || bnc < 1 || !bptr || !bindex || !value || !count || !rptr || !scratch || !nnz) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    bsr_to_csr<false><<<grid_for(n), BLOCK, 0, st>>>(n, bnr, bnc, (bnc - n % bnc) % bnc, bptr, bindex, value, count, nullptr, nullptr, nullptr);
+    LAUNCH_CHECK();
+    return tocsr_scan(n, count, rptr, scratch, nnz, st);
+}
+extern "C" int liship_bsr_to_csr(int n, int bnr, int bnc, const int *bptr, const int *bindex, const double *value, const int *rptr, int *rindex, double *rvalue,
+                                 void *stream)
+{
+    if (n <= 0 || bnr < 1 || bnc < 1 || !bptr || !bindex || !value || !rptr || !rindex || !rvalue) return LISHIP_ERR_ARG;
+    bsr_to_csr<true><<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, bnr, bnc, (bnc - n % bnc) % bnc, bptr, bindex, value, nullptr, rptr, rindex, rvalue);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int liship_dns_csr_count(int n, int np, const double *value, int *count, int *offsets, int *rptr, long long *scratch, int *nnz, void *stream)
+{
+    if (n <= 0 || np <= 0 || !value || !count || !offsets || !rptr || !scratch || !nnz) return LISHIP_ERR_ARG;
+    const int nslab = (np + TOCSR_SLAB - 1) / TOCSR_SLAB;
+    if (nslab > 65535 || (long long)n * nslab >= 0x7fffffffLL) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    dns_to_csr<false><<<dim3(grid_for(n), nslab), BLOCK, 0, st>>>(n, np, nslab, value, count, nullptr, nullptr, nullptr);
+    LAUNCH_CHECK();
+    const int rc = tocsr_scan(n * nslab, count, offsets, scratch, nnz, st);
+    if (rc) return rc;
+    dns_row_starts<<<grid_for((long long)n + 1), BLOCK, 0, st>>>(n, nslab, offsets, rptr);
+    LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int liship_dns_to_csr(int n, int np, const double *value, const int *offsets, int *rindex, double *rvalue, void *stream)
+{
+    if (n <= 0 || np <= 0 || !value || !offsets || !rindex || !rvalue) return LISHIP_ERR_ARG;
+    const int nslab = (np + TOCSR_SLAB - 1) / TOCSR_SLAB;
+    if (nslab > 65535 || (long long)n * nslab >= 0x7fffffffLL) return LISHIP_ERR_ARG;
+    dns_to_csr<true><<<dim3(grid_for(n), nslab), BLOCK, 0, as_stream(stream)>>>(n, np, nslab, value, nullptr, offsets, rindex, rvalue);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int liship_vbr_csr_count(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, const double *value,
+                                    int *count, int *rptr, long long *scratch, int *nnz, void *stream)
+{
+    if (n <= 0 || !row || !col || !ptr || !bptr || !bindex || !brow || !value || !count || !rptr || !scratch || !nnz) return LISHIP_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    vbr_to_csr<false><<<grid_for(n), BLOCK, 0, st>>>(n, row, col, ptr, bptr, bindex, brow, value, count, nullptr, nullptr, nullptr);
+    LAUNCH_CHECK();
+    return tocsr_scan(n, count, rptr, scratch, nnz, st);
+}
+extern "C" int liship_vbr_to_csr(int n, const int *row, const int *col, const int *ptr, const int *bptr, const int *bindex, const int *brow, const double *value,
+                                 const int *rptr, int *rindex, double *rvalue, void *stream)
+{
+    if (n <= 0 || !row || !col || !ptr || !bptr || !bindex || !brow || !value || !rptr || !rindex || !rvalue) return LISHIP_ERR_ARG;
+    vbr_to_csr<true><<<grid_for(n), BLOCK, 0, as_stream(stream)>>>(n, row, col, ptr, bptr, bindex, brow, value, nullptr, rptr, rindex, rvalue);
     LAUNCH_CHECK();
     return 0;
 }
