@@ -83,6 +83,18 @@ LIS_INT lis_amd_set_loop_mode(LIS_INT mode);
  * rank order).  0 (default): the fixed trees, whose results are reproducible but not the reference's last bits.  Slow: one lane adds per chunk. */
 LIS_INT lis_amd_set_reference_reductions(LIS_INT T);
 LIS_INT lis_amd_get_reference_reductions(void);
+/* Quad precision (env LIS_AMD_QUAD_PRECISION=1): the switch that plays the part of the reference's configure --enable-quad.  Off (the default) every answer
+ * is that of the reference built without it: -f quad | switch and -ef quad | switch are LIS_ERR_ILL_ARG, "Quad precision is not enabled".  On, lis_solve
+ * serves -f quad in double-double arithmetic (two doubles per vector element, the reference's SSE2 forms; kernels/dd.hpp) for -i cg | bicg | cgs | bicgstab,
+ * -p none | jacobi, an unsplit CSR matrix, one rank, no -scale; anything else under -f quad, -f switch and -ef quad | switch answer LIS_ERR_NOT_IMPLEMENTED
+ * before A, b or x is touched.  With lis_amd_set_reference_reductions(T) a quad solve carries the reference's bits at T threads (BiCG: T = 1, the reference's
+ * A^T x has no defined bits beyond).  lis_amd_last_solve_quad: 1 when the last lis_solve ran a double-double loop, else 0.
+ * lis_amd_quad_scalar: the scalar steps between the dots as the host runs them, out = a op b on (hi, lo) pairs: op 0 lis_quad_add, 1 lis_quad_mul,
+ * 2 lis_quad_div, 3 lis_quad_minus (b unused). */
+LIS_INT lis_amd_set_quad_precision(LIS_INT on);
+LIS_INT lis_amd_get_quad_precision(void);
+LIS_INT lis_amd_last_solve_quad(void);
+LIS_INT lis_amd_quad_scalar(LIS_INT op, const double *a, const double *b, double *out);
 /* 1 when the last lis_solve ran CG + Jacobi on a matrix with a constant diagonal and its fused passes took 1/diag as one double
  * instead of reading the array (bit-identical; LIS_AMD_NO_UNIFORM_JACOBI=1 switches it off), else 0 */
 LIS_INT lis_amd_last_solve_uniform_jacobi(void);

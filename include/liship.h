@@ -835,6 +835,39 @@ int  liship_bsweep_chunk(int bn);
 int  liship_bdiag_inverse_f64(int n, int nr, int bn, double *d, double *work, void *stream);
 int  liship_bdiag_matvec_f64(int n, int nr, int bn, int transposed, const double *d, const double *x, double *y, void *stream);
 
+/* ------------------------------------------------------------------ double-double ("quad", -f quad) vectors and products (kernels/quad.hip on kernels/dd.hpp)
+ * A vector is two arrays (hi, lo), a scalar two doubles, the matrix plain CSR.  The arithmetic is the reference's SSE2 build's (dd.hpp): the sloppy add, Dekker's
+ * product with the error term from one fma, the packed form of the product (mul2) for the elements the reference takes in pairs and the scalar form (mul) for
+ * the odd last element of a thread's chunk LIS_GET_ISIE(t, T, n), T that of liship_set_reference_reductions (0 and 1: one chunk).
+ *   axpy   y = y + a*x        xpay   y = x + a*y        axpyz   z = y + a*x        (outputs may be inputs)
+ *   muld   x = b * d, d double (Jacobi's psolve and psolveh; x may be b)           widen   hi = v, lo = 0
+ *   dot    result[0 .. 2) = <x, y>, every term mul2(y_i, x_i) (the scalar form for a chunk's odd last element in the reference-order mode).  T = 0: lane g of
+ *          G * 256 (G = liship_dot_dd_grid(n)) chains elements g, g + G*256, ... from (0, 0); 64 lanes fold by taking lane l + off for off = 32 .. 1, a
+ *          workgroup's 4 wavefronts are added in order, the G partials go through one more workgroup the same way (lane l chains partials l, l + 256, ...).
+ *          T > 0: per chunk accumulator 0 / 1 chain the terms at even / odd places, acc0 + acc1, then the odd last element; the chunk sums are added in
+ *          order from (0, 0).  work: liship_dot_dd_work_bytes() of HBM
+ *   spmv_csr     per row: entries j, j+1 to accumulators 0 and 1 from (0, 0) (each add(acc, muld(x[col], value))), y = acc0 + acc1, then an odd last entry is
+ *                added to y.  Rows in workgroups of liship_spmv_csr_dd_rows_per_block(), their entries through LDS in stages of liship_spmv_csr_dd_stage()
+ *   spmv_csr_t   y = A^T x from the transposed CSR copy (rows = the columns of A, a row's entries in ascending row of A): one chain per output from (0, 0),
+ *                then one add onto (0, 0) -- the reference at one thread; at more threads the reference's A^T x has no defined bits
+ * liship_dd_scalar: dd.hpp as the host compiler built it (op 0 add, 1 mul, 2 mul2, 3 muld by b.hi, 4 div, 5 two-prod by fma, 6 two-prod by Dekker's split). */
+int  liship_axpy_dd_f64(int n, double ahi, double alo, const double *xhi, const double *xlo, double *yhi, double *ylo, void *stream);
+int  liship_xpay_dd_f64(int n, const double *xhi, const double *xlo, double ahi, double alo, double *yhi, double *ylo, void *stream);
+int  liship_axpyz_dd_f64(int n, double ahi, double alo, const double *xhi, const double *xlo, const double *yhi, const double *ylo,
+                         double *zhi, double *zlo, void *stream);
+int  liship_muld_dd_f64(int n, const double *bhi, const double *blo, const double *d, double *xhi, double *xlo, void *stream);
+int  liship_widen_dd_f64(int n, const double *v, double *hi, double *lo, void *stream);
+int  liship_dot_dd_grid(int n);
+size_t liship_dot_dd_work_bytes(void);
+int  liship_dot_dd_f64(int n, const double *xhi, const double *xlo, const double *yhi, const double *ylo, double *result, void *work, void *stream);
+int  liship_spmv_csr_dd_rows_per_block(void);
+int  liship_spmv_csr_dd_stage(void);
+int  liship_spmv_csr_dd_f64(int n, const int *ptr, const int *index, const double *value, const double *xhi, const double *xlo,
+                            double *yhi, double *ylo, void *stream);
+int  liship_spmv_csr_t_dd_f64(int rows, const int *tptr, const int *tindex, const double *tvalue, const double *xhi, const double *xlo,
+                              double *yhi, double *ylo, void *stream);
+int  liship_dd_scalar(int op, double ahi, double alo, double bhi, double blo, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,6 +253,19 @@ _LISHIP = {
     "liship_is_psolve_f64": (_ci, [_ci, _vp, _vp, _vp, _cd, _vp, _vp, _vp]),
     "liship_is_psolveh_f64": (_ci, [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liship_is_truncate_f64": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _cd, _vp, _vp, _vp, _vp]),
+    "liship_axpy_dd_f64": (_ci, [_ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp]),
+    "liship_xpay_dd_f64": (_ci, [_ci, _vp, _vp, _cd, _cd, _vp, _vp, _vp]),
+    "liship_axpyz_dd_f64": (_ci, [_ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_muld_dd_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_widen_dd_f64": (_ci, [_ci, _vp, _vp, _vp, _vp]),
+    "liship_dot_dd_grid": (_ci, [_ci]),
+    "liship_dot_dd_work_bytes": (_sz, []),
+    "liship_dot_dd_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_spmv_csr_dd_rows_per_block": (_ci, []),
+    "liship_spmv_csr_dd_stage": (_ci, []),
+    "liship_spmv_csr_dd_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_spmv_csr_t_dd_f64": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liship_dd_scalar": (_ci, [_ci, _cd, _cd, _cd, _cd, C.POINTER(_cd)]),
 }
 
 

@@ -303,6 +303,10 @@ _AMD_PROTOS = {
     "lis_amd_last_shift_matrix": (LIS_INT, [P_INT]),
     "lis_amd_convert_stats": (LIS_INT, [P_INT]),
     "lis_amd_matrix_device_csr": (LIS_INT, [PM, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "lis_amd_set_quad_precision": (LIS_INT, [LIS_INT]),
+    "lis_amd_get_quad_precision": (LIS_INT, []),
+    "lis_amd_last_solve_quad": (LIS_INT, []),
+    "lis_amd_quad_scalar": (LIS_INT, [LIS_INT, P_DBL, P_DBL, P_DBL]),
 }
 
 

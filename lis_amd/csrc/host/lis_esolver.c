@@ -351,7 +351,10 @@ LIS_INT lis_gesolve(LIS_MATRIX A, LIS_MATRIX B, LIS_VECTOR x, LIS_SCALAR *evalue
 		                : "eigensolver %s (-e %s) with a subspace of one vector (-ss 1, the default) is not served by liblis_amd: one eigenpair is what -e pi / -e ii serve\n",
 		                d->name, d->key);
 	if (lisg.nprocs > 1 || A->nprocs > 1) REFUSE(LIS_ERR_NOT_IMPLEMENTED, "lis_esolve is served on one rank (this job has %D)\n", (LIS_INT)lisg.nprocs);
-	if (eprecision != LIS_PRECISION_DOUBLE) REFUSE(LIS_ERR_ILL_ARG, "Quad precision is not enabled\n");
+	if (eprecision != LIS_PRECISION_DOUBLE) {
+		if (lisg.quad_precision) REFUSE(LIS_ERR_NOT_IMPLEMENTED, "-ef %s: quad precision eigensolvers are not served by liblis_amd\n", eprecision == LIS_PRECISION_QUAD ? "quad" : "switch");
+		REFUSE(LIS_ERR_ILL_ARG, "Quad precision is not enabled\n");
+	}
 	if (estorage > 0 && estorage != A->matrix_type && !lisi_format_served(estorage))
 		REFUSE(LIS_ERR_NOT_IMPLEMENTED, "-estorage %D: storage format is not served by liblis_amd\n", estorage);
 	if (emaxiter < 0) REFUSE(LIS_ERR_ILL_ARG, "Parameter LIS_EOPTIONS_MAXITER(=%D) is less than 0\n", emaxiter);

@@ -208,6 +208,8 @@ typedef struct {
 	int last_sainv, last_sainv_wnnz, last_sainv_znnz, last_sainv_blocks;                               /* lis_amd_last_solve_sainv */
 	int last_is, last_is_m;                                                                            /* lis_amd_last_solve_is */
 	long long converted_in_hbm, converted_on_host;                                                     /* lis_amd_convert_stats: steps of lis_matrix_convert served by kernels / by a host routine since lis_initialize */
+	int quad_precision;        /* LIS_AMD_QUAD_PRECISION=1 / lis_amd_set_quad_precision(1): -f quad is served (lis_solver_quad.c); off: "Quad precision is not enabled", the reference built without --enable-quad */
+	int last_quad;             /* the last lis_solve ran a double-double loop (lis_amd_last_solve_quad) */
 	long long sainv_builds;                                                                            /* host builds of a SAINV factor since lis_initialize (lis_amd_sainv_info) */
 } lisi_globals;
 extern lisi_globals lisg;
@@ -257,6 +259,7 @@ void    lisd_pool_put(void *p, size_t bytes);
 int     lisd_malloc(void **out, size_t bytes);                /* liship_malloc that hands the pool back and retries when HBM is full; HIP code */
 int     lis_amd_trim_count(void);                             /* lis_amd_trim(), returning the number of buffers released */
 LIS_INT lisd_mat_ready_t(LIS_MATRIX A);                       /* build / upload the transposed operator */
+LIS_INT lisq_gate(LIS_MATRIX A, LIS_SOLVER solver);           /* -f quad | switch with the switch on: LIS_ERR_NOT_IMPLEMENTED for what lis_solver_quad.c does not serve, nothing touched */
 LIS_INT lisd_spmv_t(LIS_MATRIX A, double *dx, double *dy);    /* y[0..np) = A^T x, ghost rows reduced to owners */
 LIS_INT lisd_spmv(LIS_MATRIX A, double *dx, double *dy);      /* y = A x on device pointers (halo included); lis_product.c, like the two fused forms below */
 LIS_INT lisd_spmv_dot_launch(LIS_MATRIX A, double *dx, double *dy, const double *dw, int want_sumsq); /* sums -> reduce_out */

@@ -61,19 +61,15 @@ static inline void note(ctx_t *c, LIS_INT iter, double nrm)
 	if (c->output & LIS_PRINT_OUT) lis_printf(LIS_COMM_WORLD, "iteration: %5d  relative residual = %e\n", (int)iter, nrm);
 }
 
-/* r = b - A x (or b when x0 = 0), scaling 1/||r||, early exit when already converged: lis_solver.c:957-1091.
+/* the norms of the initial residual r (its high part in a quad solve), the scaling 1/||.||, the tolerance, the early exit: lis_solver.c:1037-1081.
+ * quad: the iteration-0 entry of the history and of the printed log, which the reference writes for a quad r only (:1069-1073).
  * returns 1 when the caller must stop (converged), 0 to iterate, <0 on error (-err) */
-static inline int initial_residual(ctx_t *c, double *r)
+static inline int initial_norms(ctx_t *c, const double *r, int quad)
 {
 	LIS_SOLVER s = c->s;
 	const int conv = s->options[LIS_OPTIONS_CONV_COND];
 	const double tol = s->params[LIS_PARAMS_RESID - LIS_OPTIONS_LEN], tol_w = s->params[LIS_PARAMS_RESID_WEIGHT - LIS_OPTIONS_LEN];
 	LIS_INT err = 0;
-	if (!s->options[LIS_OPTIONS_INITGUESS_ZEROS]) {
-		err = d_matvec(c, c->x, r);
-		if (!err && liship_xpay_f64(c->n, c->b, -1.0, r, lisg.stream)) err = LIS_ERR_NOT_IMPLEMENTED;
-	} else err = d_copy(c, c->b, r);
-	if (err) return -(int)err;
 	double nrm = 0.0, bn = 0.0;
 	switch (conv) {
 	case LIS_CONV_COND_NRM2_R: err = lisd_nrm2(c->n, r, &nrm); bn = nrm; s->tol = tol; break;
@@ -85,8 +81,24 @@ static inline int initial_residual(ctx_t *c, double *r)
 	bn = (bn == 0.0) ? 1.0 : 1.0 / bn;
 	s->bnrm = bn; c->bnrm = bn; c->tol = s->tol;
 	nrm = nrm * bn;
+	if (quad && c->output) {
+		if (c->output & LIS_PRINT_MEM) s->rhistory[0] = nrm;
+		if (c->output & LIS_PRINT_OUT) lis_printf(LIS_COMM_WORLD, "iteration: %5d  relative residual = %e\n", 0, nrm);
+	}
 	if (nrm <= fabs(tol)) { s->retcode = LIS_SUCCESS; s->iter = 1; s->resid = nrm; return 1; }
 	return 0;
+}
+
+/* r = b - A x (or b when x0 = 0), then the norms above: lis_solver.c:957-1091 */
+static inline int initial_residual(ctx_t *c, double *r)
+{
+	LIS_INT err = 0;
+	if (!c->s->options[LIS_OPTIONS_INITGUESS_ZEROS]) {
+		err = d_matvec(c, c->x, r);
+		if (!err && liship_xpay_f64(c->n, c->b, -1.0, r, lisg.stream)) err = LIS_ERR_NOT_IMPLEMENTED;
+	} else err = d_copy(c, c->b, r);
+	if (err) return -(int)err;
+	return initial_norms(c, r, 0);
 }
 
 /* GMRES and FGMRES, host scalars (lis_solver_gmres.c:254-290).  The new Hessenberg column hc (entries 0 .. ii + 1) takes the earlier rotations, which lie
@@ -162,5 +174,7 @@ LIS_INT lisk_minres(ctx_t *c);
 LIS_INT lisk_idrs(ctx_t *c);
 LIS_INT lisk_bicgstabl(ctx_t *c);
 LIS_INT lisk_jacobi(ctx_t *c);
+/* lis_solver_quad.c: the double-double loops of -f quad */
+LIS_INT lisq_dispatch(ctx_t *c);
 
 #endif

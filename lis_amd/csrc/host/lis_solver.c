@@ -885,10 +885,12 @@ LIS_INT lis_solve(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER solver)
 {
 	LIS_PRECON precon;
 	solver->A = A;
+	lisg.last_quad = 0;
 	if (solver->options[LIS_OPTIONS_PRECON] < 0 || solver->options[LIS_OPTIONS_PRECON] > LIS_PRECONNAME_MAX)
 		return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_PRECON is %D (Set between 0 to %D)\n", solver->options[LIS_OPTIONS_PRECON], LIS_PRECONNAME_MAX);
 	LIS_INT err = lisi_one_rank_only(A->matrix_type);          /* COO / DNS, held or asked for with -storage: one rank, refused before A, b or x is touched */
 	if (!err) err = lisi_one_rank_only(solver->options[LIS_OPTIONS_STORAGE]);
+	if (!err && lisg.quad_precision) err = lisq_gate(A, solver);       /* -f quad | switch: what is not served is refused before a preconditioner splits or scales anything */
 	if (!err) err = lis_precon_create(solver, &precon);
 	if (err) { solver->retcode = err; return err; }
 	err = lis_solve_kernel(A, b, x, solver, precon);
@@ -935,12 +937,15 @@ static LIS_INT check_options(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVE
 	}
 	if (maxiter < 0) return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_MAXITER(=%D) is less than 0\n", maxiter);
 	if (conv > 0 && (nsolver == LIS_SOLVER_GMRES || nsolver == LIS_SOLVER_TFQMR || nsolver == LIS_SOLVER_FGMRES || nsolver == LIS_SOLVER_MINRES || nsolver == LIS_SOLVER_JACOBI)) return LISI_ERR(LIS_ERR_ILL_ARG, "Option conv_cond is not implemented for solver %s\n", solver_names[nsolver]);
-	if (solver->options[LIS_OPTIONS_PRECISION] != LIS_PRECISION_DOUBLE) return LISI_ERR(LIS_ERR_ILL_ARG, "Quad precision is not enabled\n");
+	if (solver->options[LIS_OPTIONS_PRECISION] != LIS_PRECISION_DOUBLE) {     /* the reference's two builds: without --enable-quad (the default here), and with it (lis_amd_set_quad_precision) */
+		if (!lisg.quad_precision) return LISI_ERR(LIS_ERR_ILL_ARG, "Quad precision is not enabled\n");
+		LISCHK(lisq_gate(A, solver));
+	}
 	if ((nsolver == LIS_SOLVER_GMRES || nsolver == LIS_SOLVER_ORTHOMIN || nsolver == LIS_SOLVER_FGMRES) && solver->options[LIS_OPTIONS_RESTART] < 0)
 		return LISI_ERR(LIS_ERR_ILL_ARG, "Parameter LIS_OPTIONS_RESTART(=%D) is less than 0\n", solver->options[LIS_OPTIONS_RESTART]);
 	if (A->n != b->n || A->n != x->n) return LISI_ERR(LIS_ERR_ILL_ARG, "sizes of A, b and x do not match\n");
 	solver->A = A; solver->b = b;
-	solver->precision = LIS_PRECISION_DOUBLE;
+	solver->precision = solver->options[LIS_OPTIONS_PRECISION];
 	free(solver->rhistory);
 	solver->rhistory = (LIS_REAL *)calloc((size_t)(maxiter + 2), sizeof(LIS_REAL));   /* zeroed: an iteration that breaks down before its residual is formed leaves 0, not heap contents */
 	if (!solver->rhistory) return LISI_ERR(LIS_ERR_OUT_OF_MEMORY, "malloc size = %D\n", maxiter + 2);
@@ -988,7 +993,7 @@ static LIS_INT scale_system(LIS_MATRIX A, LIS_VECTOR b, LIS_SOLVER solver, LIS_I
 static void banner(LIS_MATRIX A, LIS_SOLVER solver, LIS_PRECON precon)
 {
 	lis_printf(LIS_COMM_WORLD, "initial vector x      : %s\n", solver->options[LIS_OPTIONS_INITGUESS_ZEROS] ? "all components set to 0" : "user defined");
-	lis_printf(LIS_COMM_WORLD, "precision             : double\n");
+	lis_printf(LIS_COMM_WORLD, "precision             : %s\n", precision_keys[solver->precision]);
 	lis_printf(LIS_COMM_WORLD, "linear solver         : %s\n", solver_names[solver->options[LIS_OPTIONS_SOLVER]]);
 	lis_printf(LIS_COMM_WORLD, "preconditioner        : %s\n", precon_names[precon->precon_type]);
 	if (solver->options[LIS_OPTIONS_CONV_COND] == LIS_CONV_COND_NRM2_R) lis_printf(LIS_COMM_WORLD, "convergence condition : ||b-Ax||_2 <= %6.1e * ||b-Ax_0||_2\n", solver->params[LIS_PARAMS_RESID - LIS_OPTIONS_LEN]);
@@ -1101,6 +1106,7 @@ static LIS_INT precon_begin(ctx_t *c, LIS_PRECON precon, renumber_t *rn)
 {
 	lisg.last_uniform_jacobi = 0;
 	lisg.last_graph_replays = 0;
+	lisg.last_quad = 0;
 	lisg.last_renumbered = rn->on;
 	lisg.last_ssor = lisg.last_ilu = lisg.last_bjacobi = lisg.last_sainv = lisg.last_is = 0;
 	lisg.last_bjacobi_fallback = precon && lisi_is_registered(precon) && PPRIV(precon)->from_bjacobi && precon->precon_type == LIS_PRECON_TYPE_JACOBI;
@@ -1108,7 +1114,7 @@ static LIS_INT precon_begin(ctx_t *c, LIS_PRECON precon, renumber_t *rn)
 	if (c->pk->type != LIS_PRECON_TYPE_JACOBI) return LIS_SUCCESS;
 	if (rn->on) { LISCHK(renumber_gather(rn, c->n, c->ps.dinv, &rn->d)); c->ps.dinv = rn->d; }
 	c->dinv = c->ps.dinv;
-	if (c->s->options[LIS_OPTIONS_SOLVER] == LIS_SOLVER_CG && !lisg.no_uniform_jacobi) LISCHK(jacobi_uniform(c));
+	if (c->s->options[LIS_OPTIONS_SOLVER] == LIS_SOLVER_CG && !lisg.no_uniform_jacobi && c->s->precision != LIS_PRECISION_QUAD) LISCHK(jacobi_uniform(c));
 	return LIS_SUCCESS;
 }
 
@@ -1184,14 +1190,16 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	/* may this solve run renumbered?  Not with a preconditioner that depends on the numbering (by_calls), nor scaled, nor in the reference-order mode.  A^T x: the
 	 * HBM copy is transposed in HBM (lis_matvech.c) -- of an unsplit CSR matrix, that is P A P^T's while it is swapped in; it gets a set of fields of its own */
 	const int t_ok = !solver_needs_transpose(nsolver) || (A->matrix_type == LIS_MATRIX_CSR && !A->is_splited);
-	const int may_renumber = !c.pk->by_calls && !scale && !A->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok;
+	const int quad = solver->precision == LIS_PRECISION_QUAD;               /* (a quad solve never runs renumbered, fused or device-driven: lis_solver_quad.c) */
+	const int may_renumber = !quad && !c.pk->by_calls && !scale && !A->is_scaled && !lisg.ref_reductions && !lisg.no_reorder && t_ok;
 	if (may_renumber && (err = renumber_enter(A, &rn))) goto out;
 	if ((err = vectors_in(&c, b, x, &rn))) goto out;
 	solver->precon = precon;
 	if ((err = precon_begin(&c, precon, &rn))) goto out;
 	solver->x = NULL; solver->xx = x;
 
-	err = dispatch(&c);
+	lisg.last_quad = quad;
+	err = quad ? lisq_dispatch(&c) : dispatch(&c);
 	const LIS_INT solver_code = err;
 	if (err == LIS_MAXITER || err == LIS_BREAKDOWN) err = 0;    /* reported through retcode only (ref :874,952) */
 	else if (err) goto out;
@@ -1201,7 +1209,7 @@ LIS_INT lis_solve_kernel(LIS_MATRIX A, LIS_VECTOR b, LIS_VECTOR x, LIS_SOLVER so
 	t_itime = lis_wtime() - t_itime;
 	solver->itime = t_itime; solver->p_i_time = 0.0; solver->p_c_time = 0.0; solver->ptime = 0.0;
 	solver->time = t_itime;
-	solver->iter2 = solver->iter;
+	solver->iter2 = quad ? 0 : solver->iter;                                /* ref :936-943: the double iterations of the count */
 	if (output) {
 		if (solver_code) lis_printf(LIS_COMM_WORLD, "linear solver status  : %s(code=%D)\n\n", retcode_names[solver_code], solver_code);
 		else lis_printf(LIS_COMM_WORLD, "linear solver status  : normal end\n\n");

@@ -309,6 +309,8 @@ LIS_INT lis_initialize(int *argc, char **argv[])
 		r = getenv("LIS_AMD_REFERENCE_REDUCTIONS");   /* T: every sum in the reference's order for OMP_NUM_THREADS = T (parity mode, slow) */
 		lisg.ref_reductions = (r && atoi(r) > 0) ? atoi(r) : 0;
 		if (lisg.device_ready) (void)liship_set_reference_reductions(lisg.ref_reductions);      /* (a second lis_initialize in one process) */
+		r = getenv("LIS_AMD_QUAD_PRECISION");         /* -f quad is served (configure's --enable-quad, at run time); off: today's refusal */
+		lisg.quad_precision = (r && r[0] == '1');
 		r = getenv("LIS_AMD_GRAPHS");
 		lisg.graphs = (r && r[0] == '1');
 		r = getenv("LIS_AMD_HOST_SCALARS");
